@@ -1,14 +1,22 @@
 #!/usr/bin/env python
 """Headline benchmark: x-vectors/s for 4 s @ 16 kHz utterances, HalfResNet34, bf16 trunk.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the extraction hot path (Xtractor.forward(is_eval=True): wav -> 256-d
 x-vector) over one batch of 256 synthetic utterances already resident in HBM (BASELINE.json
 configs[1]); with N > 1 every rank (one process per GPU, launched by torch.distributed.run)
 extracts its own shard and the x-vectors are all-gathered over RCCL, as the scoring step needs
 them.  Timing: barrier + synchronize on both sides of exactly K steps, MAX over ranks, rank 0
-prints ONE JSON line.  Two extra objects ride on that line:
+prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set-up, W warm-up steps, ONE timed region of
+exactly K steps (`ms_per_step` = its time / K), the outputs if asked for, the line.  `--dump-outputs DIR`
+writes what rank 0's last timed step returned -- `logits.npy` (B x n_spk) and `embeddings.npy` (B x 256),
+plus `embeddings_gathered.npy` with a process group -- as float32, inputs seeded so that two runs with the
+same arguments see the same waveforms.  `--full` adds what takes runs of its own: `--regions` (5) timed
+regions with the MEDIAN one reported, the same steps issued one forward at a time (`value_one_at_a_time`),
+and two extra objects on the line:
 
   roofline     the dominant kernel (the trunk convolution shape with the largest summed device
                time), its algorithmic bytes or FLOPs per launch over its mean launch duration
@@ -258,6 +266,23 @@ def free_port():
         return sk.getsockname()[1]
 
 
+DUMP_LIMIT = 64 << 20   # bytes written by --dump-outputs, all files together
+
+
+def dump_outputs(path, arrays):
+    """`arrays`: name -> host array with one row per utterance, written as float32 to `path`/<name>.npy.  Where the whole set would
+    pass DUMP_LIMIT, each array keeps a fixed, seeded sample of its rows (in order; arrays of equal length keep the same rows)."""
+    import numpy
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: numpy.ascontiguousarray(v, dtype=numpy.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT:
+            keep = max(1, int(a.shape[0] * (DUMP_LIMIT - (4 << 10) * len(arrays)) / total))   # 4 KB per file for the .npy header
+            a = a[numpy.sort(numpy.random.RandomState(0).choice(a.shape[0], keep, replace=False))]
+        numpy.save(os.path.join(path, name + ".npy"), a)
+
+
 def launch_ranks(n, argv):
     """Start `n` ranks of this script under torch.distributed.run as a fresh child process and relay its output.  Called
     before anything in this process has touched the GPU (no exec of a GPU-initialised process, no fork after HIP init)."""
@@ -305,6 +330,8 @@ def dry_run(args):
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         assert torch.equal(gathered[rank * B:(rank + 1) * B], emb)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": emb.numpy(), **({"embeddings_gathered": gathered.numpy()} if use_dist else {})})
     if rank == 0:
         print(json.dumps({"metric": "x-vectors/sec (4 s @ 16 kHz)", "value": world * B * args.steps / t.item(), "unit": "x-vectors/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": t.item() / args.steps * 1e3,
@@ -329,13 +356,18 @@ def main():
     ap.add_argument("--pipeline", type=int, default=0, choices=[0, 1, 2, 3], help="0 (default): the steps are issued through Xtractor.submit / collect with the library's "
                     "default number of whole batches in flight (Xtractor.pipeline_depth = 2; what the streaming extractor does); 2 / 3: that many; 1: one forward at a time "
                     "(the two-lane split of a batch)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: --regions timed regions (default 5), the roofline object, the one-forward-at-a-time "
+                    "comparison and the CPU baseline (each can be dropped with --no-profile / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write rank 0's outputs of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo stand-in of the loop (plumbing test, not a measurement)")
-    ap.add_argument("--regions", type=int, default=5, help="the timed region of exactly --steps steps is repeated this many times (barrier + synchronize on both sides of each); "
-                    "value / ms_per_step are those of the MEDIAN region, regions_ms lists all of them")
+    ap.add_argument("--regions", type=int, default=None, help="the timed region of exactly --steps steps is repeated this many times (barrier + synchronize on both sides of each); "
+                    "value / ms_per_step are those of the MEDIAN region, regions_ms lists all of them.  Default: 1, with --full 5")
     ap.add_argument("--inputs", type=int, default=5, help="distinct resident input batches the steps cycle through (5 x 65.5 MB > the 256-MB Infinity Cache)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # launched like the N = 1 command: start the ranks ourselves, as fresh child processes created before any GPU call
@@ -402,25 +434,26 @@ def main():
         counter[0] += 1
         if pipelined:
             pending.append(model.submit(wav, lengths=lens))
-            emb = None
+            out = None
             if len(pending) == model.pipeline_depth:
-                emb = model.collect(pending.pop(0))[1]
+                out = model.collect(pending.pop(0))
         else:
-            _, emb = model(wav, is_eval=True, lengths=lens)
+            out = model(wav, is_eval=True, lengths=lens)
+        emb = None if out is None else out[1]
         if use_dist and emb is not None:
             gather(emb)
         if emb is not None:
-            last[0] = emb
+            last[0] = out
         return emb
 
-    last = [None]
+    last = [None]          # (logits, x-vectors) of the batch collected last
 
     def drain():
         while pending:
-            emb = model.collect(pending.pop(0))[1]
-            last[0] = emb
+            out = model.collect(pending.pop(0))
+            last[0] = out
             if use_dist:
-                gather(emb)
+                gather(out[1])
         while in_flight:
             in_flight.pop(0)[0].wait()
 
@@ -456,7 +489,7 @@ def main():
     # region, 3 steps with every class bracketed give the per-class table, K more steps with the two largest classes bracketed
     # give the roofline object.
     per_class, focus, n_prof, prof, serial_ms, one_at_a_time_ms = None, None, 0, None, None, None
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
 
     def pick_focus(prof_w, n):
         pc = {k: round(v[0] / n, 4) for k, v in prof_w.items()}
@@ -482,10 +515,15 @@ def main():
     n_regions = max(1, args.regions if not (profile and not overlapped) else 1)   # a bracketed (serial, profiled) timed region is measured once
     region_dt, enq = [], []
     for _ in range(n_regions):
-        dt_r, emb = timed_region(args.steps)
+        dt_r, (logits, emb) = timed_region(args.steps)
         region_dt.append(dt_r)
         enq.append(host_enqueue[0])
     assert bool(torch.isfinite(emb).all()), "non-finite x-vectors"
+    if rank == 0 and args.dump_outputs:
+        dumped = {"logits": logits.cpu().numpy(), "embeddings": emb.cpu().numpy()}
+        if use_dist:
+            dumped["embeddings_gathered"] = gathered[(gathers[0] - 1) % 2].cpu().numpy()
+        dump_outputs(args.dump_outputs, dumped)
     t = torch.tensor(region_dt, dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)        # per region: the slowest rank
@@ -586,7 +624,7 @@ def main():
                                  "serial_ms_per_step": serial_ms, "of_value": (f"pipelined: {model.pipeline_depth} whole batches in flight, each on a stream of the handle" if pipelined else f"one forward at a time, {lanes} lane(s)"),
                                  "value_ms_per_step": dt / args.steps * 1e3, "one_forward_at_a_time_ms_per_step": one_at_a_time_ms}
             out["roofline"] = r
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.seconds, arch=args.arch, lens=lens)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -20,6 +20,38 @@ def test_bench_gpus2_starts_its_own_ranks():
     assert d["value"] > 0 and abs(d["value"] - 2 * 8 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
 
 
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """`--dump-outputs DIR` writes rank 0's outputs of the last timed step as float32 .npy files; the same arguments give the same files."""
+    import numpy
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "1",
+                              "--batch", "8", "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])["steps"] == 4
+        dumps.append({n: numpy.load(tmp_path / run / f"{n}.npy") for n in ("embeddings", "embeddings_gathered")})
+    a, b = dumps
+    assert a["embeddings"].shape == (8, 256) and a["embeddings_gathered"].shape == (16, 256)
+    for n in a:
+        assert a[n].dtype == numpy.float32 and numpy.array_equal(a[n], b[n]), n
+    assert numpy.array_equal(a["embeddings_gathered"][:8], a["embeddings"])
+
+
+def test_bench_dump_outputs_samples_rows_above_the_limit(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1 << 20)
+    x = numpy.arange(1000 * 512, dtype=numpy.float64).reshape(1000, 512)     # 4 MB as float64, 2 MB as float32
+    bench.dump_outputs(str(tmp_path), {"logits": x, "embeddings": x[:, :4]})
+    lg, em = numpy.load(tmp_path / "logits.npy"), numpy.load(tmp_path / "embeddings.npy")
+    assert lg.dtype == em.dtype == numpy.float32 and lg.nbytes + em.nbytes <= 1 << 20
+    assert 0 < lg.shape[0] == em.shape[0] < 1000 and numpy.array_equal(lg[:, :4], em)      # the same rows of both arrays
+    rows = lg[:, 0] / 512
+    assert numpy.all(numpy.diff(rows) > 0)                                                 # in order
+
+
 def test_bench_launcher_propagates_failure():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "1", "--arch", "nope"],

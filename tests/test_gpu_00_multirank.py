@@ -66,7 +66,7 @@ def test_bench_one_rank_over_rccl_matches_the_plain_run():
     1.14 x the plain step and observed 1.02-1.03 once it was fixed, so the bound is 1.12, one-sided.  The two numbers come from two cold
     processes on a chip whose clock a power governor sets; each run times FIVE regions of K steps (bench.py `regions_ms`), and the ratio is
     taken between the two runs' FASTEST regions -- a stall behind the collective is in every region, a cold clock is not."""
-    common = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-profile"]
+    common = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-profile"]
     d = _json_line(_torchrun(common))
     p = _json_line(_plain(common))
     assert "RCCL all-gather" in d["config"]["parallelism"] and "RCCL" not in p["config"]["parallelism"]

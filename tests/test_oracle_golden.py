@@ -146,7 +146,9 @@ def test_frontend_building_blocks():
 
 def test_asnorm_oracle_matches_reference(golden_dir):
     fx = numpy.load(os.path.join(golden_dir, "asnorm.npz"))
-    numpy.testing.assert_allclose(osc.asnorm(fx["enrol"], fx["cohort"]), fx["snorm"], atol=1e-6)
+    # float32 scores up to 26: the fixture itself is up to 1.2e-5 from the same formula in float64, and the float32 GEMMs' summation
+    # order follows the CPU's BLAS kernels (MKL's AVX2 path: 1.3e-5 from the fixture), so the bound is twice the fixture's own rounding
+    numpy.testing.assert_allclose(osc.asnorm(fx["enrol"], fx["cohort"]), fx["snorm"], atol=2.5e-5)
 
 
 def test_oracle_reproduces_examples_decode_embeddings(golden_dir):
