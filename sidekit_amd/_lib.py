@@ -13,25 +13,20 @@ if os.environ.get("SIDEKIT_AMD_LIB"):   # tuning aid: another build of the SAME 
     LIB_PATH = os.path.abspath(os.environ["SIDEKIT_AMD_LIB"])
     import warnings
     warnings.warn(f"SIDEKIT_AMD_LIB is set: loading {LIB_PATH} instead of the shipped csrc/libsidekit_amd.so (A/B tuning aid)", RuntimeWarning)
-# The product library reads SIDEKIT_AMD_LANES and SIDEKIT_AMD_SMALL_GRID (csrc/common.h); every other SIDEKIT_AMD_* switch exists only in the A/B
-# build (csrc/Makefile `make ab` -> libsidekit_amd_ab.so, loaded through SIDEKIT_AMD_LIB).  Say so instead of silently ignoring or obeying one.
+# The library reads SIDEKIT_AMD_LANES and SIDEKIT_AMD_SMALL_GRID (csrc/xt_api.hip); the Python side SIDEKIT_AMD_LIB and SIDEKIT_AMD_PIPELINE_DEPTH.
+# Say so instead of silently ignoring any other SIDEKIT_AMD_* variable.
 _PRODUCT_VARS = {"SIDEKIT_AMD_LIB", "SIDEKIT_AMD_LANES", "SIDEKIT_AMD_SMALL_GRID", "SIDEKIT_AMD_PIPELINE_DEPTH"}
-_IS_AB_BUILD = os.path.basename(LIB_PATH) != "libsidekit_amd.so"
 for _tuning in sorted(k for k in os.environ if k.startswith("SIDEKIT_AMD_") and k not in _PRODUCT_VARS):
     import warnings
-    if _IS_AB_BUILD:
-        warnings.warn(f"{_tuning}={os.environ[_tuning]!r} is set: kernels may differ from the product configuration (A/B tuning aid)", RuntimeWarning)
-    else:
-        warnings.warn(f"{_tuning} is set but the product library ignores it: A/B switches exist only in libsidekit_amd_ab.so "
-                      f"(make -C sidekit_amd/csrc ab; SIDEKIT_AMD_LIB=<that file>)", RuntimeWarning)
+    warnings.warn(f"{_tuning} is set but the library ignores it", RuntimeWarning)
 
 SK_OK, SK_EARG, SK_ESHAPE, SK_EHIP, SK_EWORKSPACE, SK_ESTATE = 0, -1, -2, -3, -4, -5
 XT_ARCH_HALFRESNET34, XT_ARCH_TDNN = 0, 1
 XT_F32, XT_BF16, XT_F64, XT_I64, XT_I16 = 0, 1, 2, 3, 4
 XT_LOSS_AAM, XT_LOSS_CCE = 0, 1
-XT_PROF_SLOTS = 17
+XT_PROF_SLOTS = 16
 PROF_NAMES = ("conv_L1", "conv_L1S", "conv_L2A", "conv_L2S", "conv_L2", "conv_L3A", "conv_L3S", "conv_L3", "conv_L4A", "conv_L4S",
-              "conv_L4", "frontend", "stem", "se_residual", "pool_tail", "tdnn", "conv_pair_L1")
+              "conv_L4", "frontend", "stem", "se_residual", "pool_tail", "tdnn")
 
 
 class XtConfig(ctypes.Structure):

@@ -1,7 +1,7 @@
 // Generic fp32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32: bit-exact f32 FMA chain, no
-// reduced-precision path on gfx950) with pluggable A-operand loaders and a fused epilogue.
+// reduced-precision path on gfx950) with a fused epilogue.
 // Serves every dense contraction of the path that is NOT a 3x3 trunk convolution:
-//   STFT-as-DFT and mel / DCT projections (torchaudio MelSpectrogram / MFCC semantics),
+//   mel / DCT projections (torchaudio MelSpectrogram / MFCC semantics),
 //   attentive-pooling 1x1 convs (pooling.py:136-141), embedding linears (xvector.py:489-491,
 //   578-581), AAM cosine logits (loss.py:307-310), TDNN dilated conv1d stack (xvector.py:467-483),
 //   cosine trial scoring (iv_scoring.py:108-109).
@@ -21,53 +21,17 @@ GemmArgs gemm_args() {
 
 constexpr int BM = 64, BN = 64, BK = 32, LDT = BK + 4;
 
-struct LoadPlain {
-  __device__ static inline float4 load(const GemmArgs& g, int m, int k) {
-    long row = m;
-    int c = k;
-    if (g.kc) { row += (long)(k / g.kc) * g.dil; c = k % g.kc; }
-    if (m >= g.M || k >= g.K || row >= g.a_rows) return make_float4(0.f, 0.f, 0.f, 0.f);
-    if (g.a_bf16) {
-      const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(g.A) + row * g.lda + c);
-      return make_float4(bf16_to_f32(v.x & 0xffff), bf16_to_f32(v.x >> 16), bf16_to_f32(v.y & 0xffff), bf16_to_f32(v.y >> 16));
-    }
-    return *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(g.A) + row * g.lda + c);
+__device__ inline float4 load_a(const GemmArgs& g, int m, int k) {
+  long row = m;
+  int c = k;
+  if (g.kc) { row += (long)(k / g.kc) * g.dil; c = k % g.kc; }
+  if (m >= g.M || k >= g.K || row >= g.a_rows) return make_float4(0.f, 0.f, 0.f, 0.f);
+  if (g.a_bf16) {
+    const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(g.A) + row * g.lda + c);
+    return make_float4(bf16_to_f32(v.x & 0xffff), bf16_to_f32(v.x >> 16), bf16_to_f32(v.y & 0xffff), bf16_to_f32(v.y >> 16));
   }
-};
-
-struct LoadFrames {
-  // augmentation.py:70-74 pre-emphasis (reflect pad 1 on the left) folded into the STFT framing
-  // (torch.stft center=True, pad_mode='reflect'; hann window centred in the n_fft frame).
-  __device__ static inline float sample(const float* w, int L, int i, float coef) {
-    if (i < 0) i = -i;
-    if (i >= L) i = 2 * (L - 1) - i;
-    const int p = (i == 0) ? 1 : i - 1;
-    return w[i] - coef * w[p];
-  }
-  __device__ static inline float4 load(const GemmArgs& g, int m, int k) {
-    if (m >= g.M || k >= g.K) return make_float4(0.f, 0.f, 0.f, 0.f);
-    int b, t;
-    if (g.row_b) { b = g.row_b[m]; t = g.row_t[m]; } else { b = m / g.t_max; t = m % g.t_max; }
-    const int L = g.nsamples ? g.nsamples[b] : g.nsamples_uniform;
-    if (t > L / g.hop) return make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* w = reinterpret_cast<const float*>(g.A) + (long)b * g.wav_ld;
-    const int i0 = t * g.hop - g.K / 2 + k;
-    const float4 win = *reinterpret_cast<const float4*>(g.window + k);
-    return make_float4(win.x * sample(w, L, i0, g.preemph), win.y * sample(w, L, i0 + 1, g.preemph),
-                       win.z * sample(w, L, i0 + 2, g.preemph), win.w * sample(w, L, i0 + 3, g.preemph));
-  }
-};
-
-struct LoadPower {
-  __device__ static inline float4 load(const GemmArgs& g, int m, int k) {
-    if (m >= g.M || k >= g.K) return make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* p = reinterpret_cast<const float*>(g.A) + (long)m * g.lda + k;
-    const float4 re = *reinterpret_cast<const float4*>(p);
-    const float4 im = *reinterpret_cast<const float4*>(p + g.kc);
-    return make_float4(re.x * re.x + im.x * im.x, re.y * re.y + im.y * im.y, re.z * re.z + im.z * im.z,
-                       re.w * re.w + im.w * im.w);
-  }
-};
+  return *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(g.A) + row * g.lda + c);
+}
 
 __device__ inline float gemm_epilogue(const GemmArgs& g, float v, int m, int n) {
   if (g.bias) v += g.bias[n];
@@ -84,7 +48,6 @@ __device__ inline float gemm_epilogue(const GemmArgs& g, float v, int m, int n) 
   return v * g.alpha;
 }
 
-template <class LA>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float As[BM * LDT];
   __shared__ __attribute__((aligned(16))) float Ws[BN * LDT];
@@ -99,7 +62,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int row = srow + q * 32;
-      ra[q] = LA::load(g, m0 + row, k0 + sk4);
+      ra[q] = load_a(g, m0 + row, k0 + sk4);
       const int n = n0 + row, k = k0 + sk4;
       rw[q] = (n < g.N && k < g.K) ? *reinterpret_cast<const float4*>(g.W + (long)n * g.ldw + k)
                                    : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -226,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(GemmArgs g) {
         *reinterpret_cast<float4*>(&Ws[(srow + q * 32) * LDT + sk4]) = rw[q];
       }
       __syncthreads();
-      if (kt + 1 < kt1 && !(g.dbg & 1)) fetch();
+      if (kt + 1 < kt1) fetch();
 #pragma unroll
       for (int kk = 0; kk < BK; kk += 8) {
         float4 a[2], b[2];
@@ -279,7 +242,8 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(GemmArgs g) {
 }
 
 // ---- bf16 form: 32 x 64 tile, two waves, k-tile of 64 bf16, v_mfma_f32_32x32x16_bf16 ---------------------------------
-// A rows are bf16 already (trunk output) or f32 converted on the way to LDS; W comes pre-converted.  LDS rows are
+// A rows are bf16 (trunk output); W comes pre-converted.  (A_BF16 = false, f32 rows converted on the way to LDS, has no caller and is not
+// instantiated; the template stays because the compiler's code for the bf16 form depends on it: a plain-function rewrite spilled 208 B.)  LDS rows are
 // 128 B + 16 B pad (9 slots: conflict-free ds_read_b128).  The problems this serves are skinny (attention.0: 13 056 x 128 x 2 560 at
 // B = 256): with 64 x 64 tiles there were 1.6 workgroups per CU, each a chain of 40 k-tiles that waited a full memory latency per tile
 // (45 us, 190 TFLOP/s).  Small tiles (816 workgroups) and operands fetched TWO k-tiles ahead keep several latencies in flight per CU;
@@ -442,16 +406,14 @@ int launch_gemm(const GemmArgs& g_in, hipStream_t s) {
   GemmArgs g = g_in;
   if (g.l2_done) *g.l2_done = 0;
   g.ksplit = 1; g.kslices = 1;
-  g.dbg = SK_AB_ENV_INT("SIDEKIT_AMD_GEMM_DBG", 0);
   SK_CHECK(g.M > 0 && g.N > 0 && g.K > 0, SK_EARG, "gemm: empty problem %dx%dx%d", g.M, g.N, g.K);
-  if (g.W_bf16 && g.a_mode == A_PLAIN && g.kc == 0 && g.K % BKH == 0 && g.lda % 8 == 0 && g.ldw % 8 == 0) {   // whole k-tiles on the bf16 matrix cores (the model's two: K = 2560, 128)
+  if (g.W_bf16 && g.kc == 0 && g.K % BKH == 0 && g.lda % 8 == 0 && g.ldw % 8 == 0) {   // whole k-tiles on the bf16 matrix cores (attention.0: K = 2560)
     const int nkh = g.K / BKH;
     g.kslices = (nkh >= 16 && nkh % 8 == 0) ? 8 : 1;                               // K alone decides how the sum is grouped ...
     g.ksplit = (g.kslices > 1 && g.M <= 512 && g.splitk_ws) ? g.kslices : 1;      // ... M only where the slices run
-    SK_CHECK(g.lda % 4 == 0, SK_EARG, "gemm: lda alignment");
+    SK_CHECK(g.a_bf16, SK_EARG, "gemm: the bf16 form takes bf16 A rows");
     const dim3 gridh((unsigned)(cdiv(cdiv(g.M, BMH), 8) * 8 * cdiv(g.N, BN)), (unsigned)g.ksplit);
-    if (g.a_bf16) hipLaunchKernelGGL(gemm_bf16_kernel<true>, gridh, dim3(128), 0, s, g);
-    else hipLaunchKernelGGL(gemm_bf16_kernel<false>, gridh, dim3(128), 0, s, g);
+    hipLaunchKernelGGL(gemm_bf16_kernel<true>, gridh, dim3(128), 0, s, g);
     SK_HIP(hipGetLastError());
     if (g.ksplit > 1) {
       hipLaunchKernelGGL(gemm_splitk_epilogue_kernel, dim3((unsigned)(((long)g.M * g.N + 255) / 256)), dim3(256), 0, s, g);
@@ -465,8 +427,8 @@ int launch_gemm(const GemmArgs& g_in, hipStream_t s) {
     if (g.M <= 512) g.ksplit = g.kslices;
   }
   SK_CHECK(g.K % 4 == 0 && g.ldw % 4 == 0, SK_EARG, "gemm: K=%d / ldw=%ld must be multiples of 4", g.K, g.ldw);
-  SK_CHECK(g.a_mode != A_PLAIN || (g.lda % 4 == 0 && g.kc % 4 == 0), SK_EARG, "gemm: lda/kc alignment");
-  if (g.ksplit == 1 && g.M >= 2048 && g.N >= 128 && g.a_mode == A_PLAIN && !g.a_bf16 && !SK_AB_GETENV("SIDEKIT_AMD_GEMM64")) {   // large problem: 128 x 128 tiles (same numbers)
+  SK_CHECK(g.lda % 4 == 0 && g.kc % 4 == 0, SK_EARG, "gemm: lda/kc alignment");
+  if (g.ksplit == 1 && g.M >= 2048 && g.N >= 128 && !g.a_bf16) {   // large problem: 128 x 128 tiles (same numbers)
     dim3 grid2(cdiv(g.M, BM2), cdiv(g.N, BN2));
     if (g.kslices > 1) hipLaunchKernelGGL(gemm128_kernel<true>, grid2, dim3(256), 0, s, g);
     else hipLaunchKernelGGL(gemm128_kernel<false>, grid2, dim3(256), 0, s, g);
@@ -474,12 +436,7 @@ int launch_gemm(const GemmArgs& g_in, hipStream_t s) {
     return SK_OK;
   }
   dim3 grid(cdiv(g.M, BM), cdiv(g.N, BN), g.ksplit);
-  switch (g.a_mode) {
-    case A_PLAIN: hipLaunchKernelGGL(gemm_kernel<LoadPlain>, grid, dim3(256), 0, s, g); break;
-    case A_FRAMES: hipLaunchKernelGGL(gemm_kernel<LoadFrames>, grid, dim3(256), 0, s, g); break;
-    case A_POWER: hipLaunchKernelGGL(gemm_kernel<LoadPower>, grid, dim3(256), 0, s, g); break;
-    default: set_error("gemm: bad a_mode %d", g.a_mode); return SK_EARG;
-  }
+  hipLaunchKernelGGL(gemm_kernel, grid, dim3(256), 0, s, g);
   SK_HIP(hipGetLastError());
   if (g.ksplit > 1) {
     if (g.l2_out && g.l2_done && g.N <= 1024) {

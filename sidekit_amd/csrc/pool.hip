@@ -152,12 +152,10 @@ __global__ __launch_bounds__(256) void att_stats_kernel(const void* __restrict__
   }
 }
 
-int launch_att_stats(const void* x, int x_bf16, const float* e, long ld, int D, RowSpan rs, float* out, int B, hipStream_t s) {
-  const int VEC = x_bf16 ? 8 : 4;
-  SK_CHECK(D % VEC == 0 && ld % VEC == 0, SK_EARG, "att_stats: D=%d, ld=%ld must be multiples of %d", D, ld, VEC);
-  const dim3 grid(B, cdiv(D, POOL_CG * VEC));
-  if (x_bf16) hipLaunchKernelGGL(att_stats_kernel<8>, grid, dim3(256), 0, s, x, e, ld, D, rs, out);
-  else hipLaunchKernelGGL(att_stats_kernel<4>, grid, dim3(256), 0, s, x, e, ld, D, rs, out);
+int launch_att_stats(const float* x, const float* e, long ld, int D, RowSpan rs, float* out, int B, hipStream_t s) {
+  SK_CHECK(D % 4 == 0 && ld % 4 == 0, SK_EARG, "att_stats: D=%d, ld=%ld must be multiples of 4", D, ld);
+  const dim3 grid(B, cdiv(D, POOL_CG * 4));
+  hipLaunchKernelGGL(att_stats_kernel<4>, grid, dim3(256), 0, s, x, e, ld, D, rs, out);
   SK_HIP(hipGetLastError());
   return SK_OK;
 }

@@ -106,22 +106,8 @@ static int lane_parts(int lanes, int B, int lane_min) {
 using namespace sk;
 
 struct xt_handle {
-  bool shortcut_tensor = SK_AB_GETENV("SIDEKIT_AMD_SHORTCUT_TENSOR") != nullptr;   // A/B builds only (common.h), see half_from_feats
-  bool mel_gemm = SK_AB_GETENV("SIDEKIT_AMD_MEL_GEMM") != nullptr;                 // A/B switch: mel projection as a separate GEMM
-  bool mfcc_dft_gemm = SK_AB_GETENV("SIDEKIT_AMD_MFCC_DFT_GEMM") != nullptr;       // A/B switch: MFCC spectrum as a DFT contraction (round-1 form) instead of the FFT
-  // SE gate computed inside conv2 instead of by a launch of its own (se_gate_inl.h).  Two forms were built in round 5; both give se_pre_kernel's
-  // bits (tests/test_gpu_halfresnet.py) and NEITHER pays (profiles/r05_latency_matrix.txt), so the default is 0 = the launch:
-  //  - prologue (3 = small grids, 4 = always; the round-4 verdict's specification: a separate instantiation in which every workgroup of an
-  //    utterance reduces the sums in se_pre_kernel's order before its k-loop): the gate is a chain of dependent L2 round trips and barriers
-  //    that takes 5-6 us whether it runs as a kernel (5.7-7.3 us) or at the head of conv2 (+5.4-6.3 us per conv2, +23 us for layer 4):
-  //    0.690 vs 0.687 ms per 4-s utterance on one box, 0.663 vs 0.618 on another;
-  //  - gate wave (1 = small grids, 2 = always; layers 1-2): a fifth wave computes the gate WHILE the four convolution waves stage the tile and
-  //    run the k-loop, joining their barriers.  Concurrent, no launch -- but ONE wave walks the chain in ~10 us where the 16-wave kernel
-  //    needs 1-2, longer than the convolution it hides behind: 0.636 vs 0.618 ms.
-  int gate_prologue = SK_AB_ENV_INT("SIDEKIT_AMD_GATE_PROLOGUE", 0);   // A/B builds only: the product has no in-convolution gate form
   // small-grid tilings for conv2 of layers 3-4 (conv3x3.hip, "Small-grid forms"): 1 (default) at most SMALL_GRID_MAX_B utterances, 0 never, 2 always
   static constexpr int SMALL_GRID_MAX_B = 12;      // crossover with the product tilings between 12 and 16 utterances (profiles/r05_small_grid_sweep.txt)
-  static constexpr int GATE_AB_MAX_B = 8;          // A/B builds: the in-convolution gate forms keep their own bound (SIDEKIT_AMD_GATE_PROLOGUE = 1 / 3)
   int small_grid = getenv("SIDEKIT_AMD_SMALL_GRID") ? atoi(getenv("SIDEKIT_AMD_SMALL_GRID")) : 1;
   xt_config cfg;
   int device = 0;
@@ -133,7 +119,6 @@ struct xt_handle {
   FrontCfg fc;
   int nbp = 0;             // DFT bins padded to a multiple of 4
   float* d_window = nullptr;
-  float* d_basis = nullptr;  // [2*nbp][win]
   float* d_fbT = nullptr;    // [n_mels][nbp]
   float* d_mel_cw = nullptr; int* d_mel_ck0 = nullptr; int* d_mel_fmeta = nullptr; int mel_chunks = 0; bool mel_fused = false;   // bank as 8-tap chunks (frontend_fft.hip)
   float* d_dctT = nullptr;   // [n_out][n_mels] (MFCC)
@@ -219,6 +204,26 @@ struct StreamScope {
   xt_handle* h; hipStream_t st;
   StreamScope(xt_handle* h_, hipStream_t st_) : h(h_), st(st_) {}
   ~StreamScope() { leave_stream(h, st); }
+};
+
+// sk_bench_conv's device buffers and events, released on every return (the early ones of SK_HIP / SK_TRY included)
+struct BenchAllocs {
+  std::vector<void*> bufs;
+  std::vector<hipEvent_t> events;
+  template <class P> int alloc(P** p, size_t bytes) {
+    SK_HIP(hipMalloc((void**)p, bytes));
+    bufs.push_back(*p);
+    return SK_OK;
+  }
+  int event(hipEvent_t* e) {
+    SK_HIP(hipEventCreate(e));
+    events.push_back(*e);
+    return SK_OK;
+  }
+  ~BenchAllocs() {
+    for (void* p : bufs) (void)hipFree(p);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  }
 };
 
 // ---- expected checkpoint keys ------------------------------------------------------------------
@@ -347,17 +352,6 @@ static int build_frontend(xt_handle* h) {
   const std::string wk = mel ? "preprocessor.MelSpec.spectrogram.window" : "preprocessor.MFCC.MelSpectrogram.spectrogram.window";
   const std::string fk = mel ? "preprocessor.MelSpec.mel_scale.fb" : "preprocessor.MFCC.MelSpectrogram.mel_scale.fb";
   SK_TRY(upload_f(h, T(h, wk), &h->d_window));
-  // real-DFT basis restricted to the window support: frame sample k sits at n = left + k of the n_fft frame
-  const int left = (f.n_fft - f.win) / 2;
-  std::vector<float> basis((size_t)2 * h->nbp * f.win, 0.f);
-  for (int j = 0; j < nb; ++j)
-    for (int k = 0; k < f.win; ++k) {
-      const long ph = ((long)j * (left + k)) % f.n_fft;
-      const double ang = 2.0 * M_PI * (double)ph / (double)f.n_fft;
-      basis[(size_t)j * f.win + k] = (float)cos(ang);
-      basis[((size_t)h->nbp + j) * f.win + k] = (float)(-sin(ang));
-    }
-  SK_TRY(upload_f(h, basis, &h->d_basis));
   const auto& fb = T(h, fk);  // [nb][n_mels]
   std::vector<float> fbT((size_t)f.n_mels * h->nbp, 0.f);
   for (int j = 0; j < nb; ++j)
@@ -653,46 +647,29 @@ static int frontend_rows(xt_handle* h, Lane& ln, const void* d_wav, int pcm16, i
   const int M = m.R ? m.R : m.B * m.T;
   const bool mfcc = h->cfg.arch == XT_ARCH_TDNN;
   float* logmel = mfcc ? (float*)ln.ws_act[3].p : d_feat_rows;   // MFCC: the DCT follows
-  GemmArgs p = gemm_args();
-  bool have_logmel = false;
-  if (!(mfcc && h->mfcc_dft_gemm)) {
-    // 1) |rFFT(window * preemph(frame))|^2, one wavefront per frame (frontend_fft.hip)
-    FftArgs fa;
-    fa.n_fft = f.n_fft;
-    fa.wav = d_wav; fa.pcm16 = pcm16; fa.wav_ld = wav_ld; fa.nsamples = m.d_nsamples; fa.nsamples_uniform = m.nsamples_uniform; fa.window = h->d_window;
-    fa.tw512 = h->d_tw512; fa.tw1024 = h->d_tw1024; fa.P = (float*)ln.ws_S.p; fa.ldp = h->nbp; fa.M = M; fa.t_max = m.T; fa.hop = f.hop;
-    fa.row_b = m.d_row_b; fa.row_t = m.d_row_t; fa.preemph = 0.97f;
-    SK_CHECK((size_t)M * h->nbp * 4 <= ln.ws_S.bytes, SK_EWORKSPACE, "spectrum workspace too small (xt_reserve)");
-    fa.mel_cw = nullptr; fa.mel_ck0 = nullptr; fa.mel_fmeta = nullptr; fa.mel_chunks = 0; fa.n_mels = 0; fa.logmel = nullptr; fa.ldl = 0;
-    if (h->mel_fused && !h->mel_gemm) {  // power spectrum stays in LDS, the kernel writes log-mel rows
-      fa.mel_cw = h->d_mel_cw; fa.mel_ck0 = h->d_mel_ck0; fa.mel_fmeta = h->d_mel_fmeta; fa.mel_chunks = h->mel_chunks; fa.n_mels = f.n_mels;
-      fa.logmel = logmel; fa.ldl = f.n_mels;
-      have_logmel = true;
-    }
-    { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_stft_power_fft(fa, st)); }
-    // 2) power x mel filterbank, log(. + 1e-6)
-    p.a_mode = A_PLAIN; p.A = ln.ws_S.p; p.lda = h->nbp; p.a_rows = M;
-  } else {
-    // 1) frames x DFT basis -> [re | im]   (A/B form of the MFCC front-end: n_fft 2048, win 1024)
-    SK_CHECK(!pcm16, SK_EARG, "the DFT-GEMM A/B form of the MFCC front-end takes float32 samples only");
-    GemmArgs g = gemm_args();
-    g.a_mode = A_FRAMES; g.A = d_wav; g.wav_ld = wav_ld; g.window = h->d_window; g.nsamples = m.d_nsamples;
-    g.nsamples_uniform = m.nsamples_uniform; g.hop = f.hop; g.t_max = m.T; g.row_b = m.d_row_b; g.row_t = m.d_row_t;
-    g.preemph = 0.97f;
-    g.W = h->d_basis; g.ldw = f.win; g.C = (float*)ln.ws_S.p; g.ldc = 2 * h->nbp; g.M = M; g.N = 2 * h->nbp; g.K = f.win;
-    SK_CHECK((size_t)M * 2 * h->nbp * 4 <= ln.ws_S.bytes, SK_EWORKSPACE, "spectrum workspace too small (xt_reserve)");
-    { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_gemm(g, st)); }
-    // 2) |.|^2 x mel filterbank, log(. + 1e-6)
-    p.a_mode = A_POWER; p.A = ln.ws_S.p; p.lda = 2 * h->nbp; p.kc = h->nbp;
+  // 1) |rFFT(window * preemph(frame))|^2, one wavefront per frame (frontend_fft.hip)
+  FftArgs fa;
+  fa.n_fft = f.n_fft;
+  fa.wav = d_wav; fa.pcm16 = pcm16; fa.wav_ld = wav_ld; fa.nsamples = m.d_nsamples; fa.nsamples_uniform = m.nsamples_uniform; fa.window = h->d_window;
+  fa.tw512 = h->d_tw512; fa.tw1024 = h->d_tw1024; fa.P = (float*)ln.ws_S.p; fa.ldp = h->nbp; fa.M = M; fa.t_max = m.T; fa.hop = f.hop;
+  fa.row_b = m.d_row_b; fa.row_t = m.d_row_t; fa.preemph = 0.97f;
+  SK_CHECK((size_t)M * h->nbp * 4 <= ln.ws_S.bytes, SK_EWORKSPACE, "spectrum workspace too small (xt_reserve)");
+  fa.mel_cw = nullptr; fa.mel_ck0 = nullptr; fa.mel_fmeta = nullptr; fa.mel_chunks = 0; fa.n_mels = 0; fa.logmel = nullptr; fa.ldl = 0;
+  if (h->mel_fused) {  // power spectrum stays in LDS, the kernel writes log-mel rows
+    fa.mel_cw = h->d_mel_cw; fa.mel_ck0 = h->d_mel_ck0; fa.mel_fmeta = h->d_mel_fmeta; fa.mel_chunks = h->mel_chunks; fa.n_mels = f.n_mels;
+    fa.logmel = logmel; fa.ldl = f.n_mels;
   }
-  if (!have_logmel) {
+  { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_stft_power_fft(fa, st)); }
+  if (!h->mel_fused) {  // 2) power x mel filterbank, log(. + 1e-6)
+    GemmArgs p = gemm_args();
+    p.A = ln.ws_S.p; p.lda = h->nbp; p.a_rows = M;
     p.W = h->d_fbT; p.ldw = h->nbp; p.M = M; p.N = f.n_mels; p.K = h->nbp; p.act = ACT_LOG_EPS;
     p.C = logmel; p.ldc = f.n_mels;
     { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_gemm(p, st)); }
   }
   if (mfcc) {  // 3) DCT-II (ortho) 100 -> 80
     GemmArgs d = gemm_args();
-    d.a_mode = A_PLAIN; d.A = logmel; d.lda = f.n_mels; d.a_rows = M; d.W = h->d_dctT; d.ldw = f.n_mels;
+    d.A = logmel; d.lda = f.n_mels; d.a_rows = M; d.W = h->d_dctT; d.ldw = f.n_mels;
     d.C = d_feat_rows; d.ldc = f.n_out; d.M = M; d.N = f.n_out; d.K = f.n_mels;
     { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_gemm(d, st)); }
   }
@@ -730,16 +707,9 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
   for (int l = 0; l < 4; ++l) Hl[l] = halve(T, l);
   const size_t act_bytes = (size_t)B * T * 80 * 32 * EB;
   for (int i = 0; i < 4; ++i) SK_CHECK(act_bytes <= ln.ws_act[i].bytes, SK_EWORKSPACE, "activation workspace too small: call xt_reserve(%d, >= %d frames)", B, T);
-  void *X = ln.ws_act[0].p, *O1 = ln.ws_act[1].p, *O2 = ln.ws_act[2].p, *SC = ln.ws_act[3].p;
+  void *X = ln.ws_act[0].p, *O1 = ln.ws_act[1].p, *O2 = ln.ws_act[2].p;
   { ProfScope ps(h, XT_PROF_STEM, st); SK_TRY(launch_stem(feats, sb, sf, stt, h->stem_w, h->stem_shift, X, dt, m.lens, B, T, st)); }
   SK_TRY(tap(h, "stem", X, act_bytes, st));
-  int prev_li = 0;
-  // A/B builds, SIDEKIT_AMD_PAIR=1 (round 6): layer 1, bf16: conv2 of block k and conv1 of block k + 1 as ONE kernel (conv_pair.hip) -- Y_k reaches
-  // conv1 through LDS and HBM sees 13 instead of 15 activation passes for the layer.  Same bits as the two launches, and slower (1.84 vs 1.58 ms per
-  // step for the layer: the fused workgroup's chain of barrier-separated memory phases is twice as long and a CU still holds only two of them,
-  // profiles/r06_conv_pair_L1.txt): not in the product library.
-  const bool use_pair = dt == DT_BF16 && !h->shortcut_tensor && !h->gate_prologue && SK_AB_GETENV("SIDEKIT_AMD_PAIR") != nullptr;
-  bool o1_ready = false;   // this block's conv1 has already run (second half of the previous block's pair kernel)
   for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
     Block& b = h->blocks[bi];
     const int li = b.li;
@@ -753,13 +723,6 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
     a.in = X; a.wpack = b.c1.wpack; a.scale = b.c1.scale; a.shift = b.c1.shift; a.out = O1;
     a.se_part = (float*)ln.ws_se.p; a.col_part = (float*)ln.ws_col.p; a.edge = (float*)ln.ws_edge.p;
     a.halvings_in = lin; a.Hin = Hl[lin]; a.Hout = Hl[li]; a.relu = 1;
-    // shortcut rides on conv1's centre tap where that costs no occupancy (the stride-2 shapes already run one workgroup per CU)
-    // first block of a layer: by default conv2's epilogue evaluates the 1x1 shortcut conv itself from the block input
-    // (no shortcut tensor at all); the older forms -- riding on conv1's centre tap, or a separate 1x1 launch -- remain
-    // in A/B builds (make ab; SIDEKIT_AMD_SHORTCUT_TENSOR=1)
-    const bool inplace_sc = first && !h->shortcut_tensor;
-    const bool fuse_sc = first && !inplace_sc && b.c1.g.stride == 2 && b.c1.g.nw == 1 && b.sc.g.ck == b.c1.g.ck && !b.c1.g.m16;   // (the 16x16x32 k-loop has no fused-shortcut form)
-    if (fuse_sc) { a.sc_wpack = b.sc.wpack; a.sc_scale = b.sc.scale; a.sc_shift = b.sc.shift; a.sc_out = SC; }
     {
       const size_t tiles1 = (size_t)cdiv(Hl[li], b.c1.g.th);
       SK_CHECK((size_t)B * tiles1 * b.c1.g.wm * b.C * 4 <= ln.ws_se.bytes && (size_t)B * tiles1 * 2 * b.C * 4 <= ln.ws_col.bytes &&
@@ -776,72 +739,29 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
     se.se_part = (const float*)ln.ws_se.p; se.col_part = (const float*)ln.ws_col.p; se.edge = (const float*)ln.ws_edge.p;
     se.tiles = cdiv(Hl[li], b.c1.g.th); se.wm = b.c1.g.wm; se.th = b.c1.g.th; se.w2t = b.w2t; se.w2t_bf16 = h->cfg.dtype == XT_BF16; se.scale2 = b.c2.scale; se.shift2 = b.c2.shift;
     se.fc1 = b.se_w1; se.fc2 = b.se_w2; se.gate = (float*)ln.ws_gate.p; se.lens = m.lens; se.halvings = li; se.wout = wout; se.C = b.C; se.B = B;
-    if (!o1_ready) { ProfScope ps(h, b.c1.shape, st); SK_TRY(launch_conv(b.c1.shape, dt, a, st)); }
-    a.sc_wpack = nullptr;
-    const void* shortcut = first ? SC : X;
-    if (first && !fuse_sc && !inplace_sc) {  // 1x1 conv (stride s) + bn on the block input
-      a.wpack = b.sc.wpack; a.scale = b.sc.scale; a.shift = b.sc.shift; a.out = SC;
-      a.se_part = nullptr; a.col_part = nullptr; a.edge = nullptr; a.relu = 0;
-      { ProfScope ps(h, b.sc.shape, st); SK_TRY(launch_conv(b.sc.shape, dt, a, st)); }
-    }
+    { ProfScope ps(h, b.c1.shape, st); SK_TRY(launch_conv(b.c1.shape, dt, a, st)); }
+    { ProfScope ps(h, XT_PROF_SE_RES, st); SK_TRY(launch_se_pre(se, st)); }
     // small grids (at most SMALL_GRID_MAX_B utterances; 1 is the reference driver's call shape, sidekit/bin/extract_xvectors.py:146): a forward is a
     // chain of dependent launches, each as long as ONE wave's work: conv2 of layers 3-4 runs in 3- / 2-row tiles (more, shorter workgroups).  Same bits.
-    // (A/B builds: a SIDEKIT_AMD_SHAPE_MAP may remap conv2's shape to a geometry the T shapes' weight pack does not match -- no small grids then.)
-    const bool small = dt == DT_BF16 && !SK_AB_GETENV("SIDEKIT_AMD_SHAPE_MAP") &&
+    const bool small = dt == DT_BF16 &&
                        (h->small_grid == 2 || (h->small_grid == 1 && B <= xt_handle::SMALL_GRID_MAX_B && (long)B * Hl[li] <= 4096));
     const int c2shape = !small ? b.c2.shape : (li == 2 ? (int)CONV_L3T : (li == 3 ? (int)CONV_L4T : b.c2.shape));
-    // the gate inside conv2 (A/B forms, off by default: see xt_handle::gate_prologue).  1 / 2: layers 1-2, conv2's fifth wave computes it beside the k-loop
-    // (small grids / always); 3 / 4: every layer, every workgroup computes it before its k-loop (small grids / always)
-    const bool small_b = B <= xt_handle::GATE_AB_MAX_B && (long)B * Hl[li] <= 4096;
-    const int gate_pro = (h->gate_prologue == 2 || (h->gate_prologue == 1 && small_b)) ? (b.C <= 64 ? 2 : 0)
-                         : ((h->gate_prologue == 4 || (h->gate_prologue == 3 && small_b)) ? 1 : 0);
-    if (!gate_pro) {
-      ProfScope ps(h, XT_PROF_SE_RES, st);
-      SK_TRY(launch_se_pre(se, st));
-    }
-#ifdef SK_AB
-    const bool pair = use_pair && li == 0 && bi + 1 < h->blocks.size() && h->blocks[bi + 1].li == li && (!first || inplace_sc);
-    if (pair) {
-      const Block& nb = h->blocks[bi + 1];
-      ConvPairArgs pa;
-      memset(&pa, 0, sizeof(pa));
-      pa.C = b.C; pa.W = wout;
-      pa.in = O1; pa.w2pack = b.c2.wpack; pa.scale2 = b.c2.scale; pa.shift2 = b.c2.shift; pa.gate = (const float*)ln.ws_gate.p;
-      if (first) { pa.sc_in = X; pa.sc_wpack = b.sc_wfold; pa.sc_shift = b.sc.shift; } else { pa.shortcut = X; }
-      pa.y_out = O2;
-      pa.w1pack = nb.c1.wpack; pa.scale1 = nb.c1.scale; pa.shift1 = nb.c1.shift; pa.o_out = SC;
-      pa.se_part = (float*)ln.ws_se.p; pa.col_part = (float*)ln.ws_col.p; pa.edge = (float*)ln.ws_edge.p;
-      pa.zeros = h->d_zeros; pa.lens = m.lens; pa.B = B; pa.H = Hl[li]; pa.persist_cap = ln.persist_cap;
-      { ProfScope ps(h, b.c2.shape, st); SK_TRY(launch_conv_pair(pa, st)); }
-      // Y_k (O2) is the next block's input, O1_{k+1} (SC) its conv1 output; the two buffers just read are free
-      void *old_x = X, *old_o1 = O1;
-      X = O2; O1 = SC; O2 = old_x; SC = old_o1;
-      o1_ready = true;
-      prev_li = li;
-      continue;
-    }
-#endif
-    (void)use_pair;
-    o1_ready = false;
     // conv2 + bn2, * gate, + shortcut, relu -> O2 (the block output)
     a.in = O1; a.wpack = b.c2.wpack; a.scale = b.c2.scale; a.shift = b.c2.shift; a.out = O2;
-    a.se_part = nullptr; a.col_part = nullptr; a.edge = nullptr; a.gate = (const float*)ln.ws_gate.p; a.shortcut = shortcut;
+    a.se_part = nullptr; a.col_part = nullptr; a.edge = nullptr; a.gate = (const float*)ln.ws_gate.p; a.shortcut = X;
     a.halvings_in = li; a.Hin = Hl[li]; a.Hout = Hl[li]; a.relu = 0;
-    if (gate_pro) { a.gate_pro = gate_pro; a.se = se; }     // every workgroup of conv2 derives its utterance's gate itself; ws_gate is not read
-    if (inplace_sc) {
+    if (first) {   // first block of a layer: conv2's epilogue evaluates the 1x1 shortcut conv itself from the block input (no shortcut tensor)
       a.shortcut = nullptr; a.sc_in = X; a.sc_hin = Hl[lin];
       a.sc_wpack = b.sc_wfold; a.sc_scale = b.sc.scale; a.sc_shift = b.sc.shift;
     }
-    { ProfScope ps(h, b.c2.shape, st); SK_TRY(launch_conv((gate_pro == 2 && li == 0 && dt == DT_BF16) ? (int)CONV_L1G : c2shape, dt, a, st)); }
+    { ProfScope ps(h, b.c2.shape, st); SK_TRY(launch_conv(c2shape, dt, a, st)); }
     std::swap(X, O2);
     const bool last_of_layer = (bi + 1 == h->blocks.size()) || (h->blocks[bi + 1].li != li);
     if (last_of_layer) {
       const std::string nm = "layer" + std::to_string(li + 1);
       SK_TRY(tap(h, nm.c_str(), X, (size_t)B * Hl[li] * wout * b.C * EB, st));
     }
-    prev_li = li;
   }
-  (void)prev_li;
   // ---- attentive statistics pooling (pooling.py:151-171), rows = (b, t'), columns d' = f*256 + c
   const int H4 = Hl[3], D = 2560, R = B * H4;
   const int xbf = dt == DT_BF16;
@@ -858,14 +778,15 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
   g1.act = ACT_RELU_BN_TANH; g1.scale = h->att_bn_scale; g1.shift = h->att_bn_shift; g1.W_bf16 = h->att_w1x_bf16;
   if (xbf && (size_t)8 * 512 * 128 * 4 <= ln.ws_splitk.bytes) g1.splitk_ws = (float*)ln.ws_splitk.p;   // bf16 path, at most 512 rows (a few utterances): K in eight slices side by side (gemm.hip)
   SK_TRY(launch_gemm(g1, st));
-  if (xbf && !SK_AB_GETENV("SIDEKIT_AMD_ATT_SEPARATE")) {   // bf16 path: attention.4 + softmax + statistics fused, e never leaves the accumulators
+  SK_TRY(tap(h, "att_h", ln.ws_h.p, (size_t)R * 128 * 4, st));
+  if (xbf) {   // bf16 path: attention.4 + softmax + statistics fused, e never leaves the accumulators
     SK_TRY(launch_att_fused(X, (const float*)ln.ws_h.p, h->att_w2_bf16, h->att_b2, D, D, rs, (float*)ln.ws_pooled.p, B, st));
-  } else {
-  GemmArgs g2 = gemm_args();  // attention.4
-  g2.A = ln.ws_h.p; g2.lda = 128; g2.a_rows = R; g2.W = h->att_w2; g2.ldw = 128; g2.C = (float*)ln.ws_e.p; g2.ldc = D;
-  g2.M = R; g2.N = D; g2.K = 128; g2.bias = h->att_b2; g2.W_bf16 = h->att_w2_bf16;
-  SK_TRY(launch_gemm(g2, st));
-  SK_TRY(launch_att_stats(X, xbf, (const float*)ln.ws_e.p, D, D, rs, (float*)ln.ws_pooled.p, B, st));
+  } else {   // fp32 path: attention.4 as a GEMM, then softmax + statistics
+    GemmArgs g2 = gemm_args();
+    g2.A = ln.ws_h.p; g2.lda = 128; g2.a_rows = R; g2.W = h->att_w2; g2.ldw = 128; g2.C = (float*)ln.ws_e.p; g2.ldc = D;
+    g2.M = R; g2.N = D; g2.K = 128; g2.bias = h->att_b2;
+    SK_TRY(launch_gemm(g2, st));
+    SK_TRY(launch_att_stats((const float*)X, (const float*)ln.ws_e.p, D, D, rs, (float*)ln.ws_pooled.p, B, st));
   }
   SK_TRY(tap(h, "pooled", ln.ws_pooled.p, (size_t)B * 2 * D * 4, st));
   GemmArgs e = gemm_args();  // lin_be + bn_be (xvector.py:578-581)
@@ -1051,13 +972,23 @@ int xt_finalize(xt_handle* h) {
   return SK_OK;
 }
 
+// a lane's / slot's own stream, at the lowest priority (reserve_side_lanes explains why), with its fork / join events
+static int create_lane_stream(Lane& lk) {
+  int least = 0, greatest = 0;
+  SK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+  SK_HIP(hipStreamCreateWithPriority(&lk.stream, hipStreamNonBlocking, least));
+  SK_HIP(hipEventCreateWithFlags(&lk.fork, hipEventDisableTiming));
+  SK_HIP(hipEventCreateWithFlags(&lk.join, hipEventDisableTiming));
+  return SK_OK;
+}
+
 static int reserve_lane(xt_handle* h, Lane& ln, int32_t max_batch, int64_t max_samples) {
   const FrontCfg& f = h->fc;
   const size_t B = (size_t)max_batch;
   const size_t T = 1 + (size_t)(max_samples / f.hop);
   const size_t nbp = (size_t)((f.n_fft / 2 + 1 + 3) / 4 * 4);
   const size_t R = B * T;
-  SK_TRY(ln.ws_S.ensure(R * 2 * nbp * 4));
+  SK_TRY(ln.ws_S.ensure(R * nbp * 4));
   SK_TRY(ln.ws_feat.ensure(R * f.n_out * 4));
   const size_t int_bytes = (4 * B + 2 * R + 16) * 4;
   SK_TRY(ln.ws_int.ensure(int_bytes));
@@ -1126,14 +1057,8 @@ static int reserve_side_lanes(xt_handle* h, int32_t max_batch, int64_t max_sampl
       // SLOWER than the serial one (round 4, one rank under torch.distributed.run: 6.41-6.60 vs 5.93-6.08 ms,
       // scripts/rccl_step_probe.py).  Queues are pooled per priority, so lanes of another priority get queues of their own; and
       // they must all have the SAME priority: one high-priority lane beside the caller's normal stream ran ahead of it instead of
-      // beside it and the overlap was gone (5.92 vs 5.73 ms).  Product: low; A/B builds: SIDEKIT_AMD_LANE_PRIORITY = low | high | normal.
-      static const char* pe = SK_AB_GETENV("SIDEKIT_AMD_LANE_PRIORITY");
-      int least = 0, greatest = 0;
-      SK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      const int prio = (pe && !strcmp(pe, "normal")) ? 0 : ((pe && !strcmp(pe, "high")) ? greatest : least);
-      SK_HIP(hipStreamCreateWithPriority(&lk.stream, hipStreamNonBlocking, prio));
-      SK_HIP(hipEventCreateWithFlags(&lk.fork, hipEventDisableTiming));
-      SK_HIP(hipEventCreateWithFlags(&lk.join, hipEventDisableTiming));
+      // beside it and the overlap was gone (5.92 vs 5.73 ms).  So: the lowest priority (create_lane_stream).
+      SK_TRY(create_lane_stream(lk));
     }
     if (k == 0) continue;   // lane 0's workspace is the handle's full-size one
     const int part = (max_batch + k) / (k + 1);
@@ -1271,15 +1196,7 @@ int xt_forward_pcm16(xt_handle* h, const int16_t* d_pcm, int64_t pcm_ld, const i
 // xt_forward_end makes a stream wait for that forward.  A caller keeps `slots` batches in flight: begin(k), end(k - slots + 1), ...
 static int reserve_slot(xt_handle* h, int slot, int32_t max_batch, int64_t max_samples) {
   Lane& lk = h->lane[slot];
-  if (!lk.stream) {
-    static const char* pe = SK_AB_GETENV("SIDEKIT_AMD_LANE_PRIORITY");
-    int least = 0, greatest = 0;
-    SK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const int prio = (pe && !strcmp(pe, "normal")) ? 0 : ((pe && !strcmp(pe, "high")) ? greatest : least);
-    SK_HIP(hipStreamCreateWithPriority(&lk.stream, hipStreamNonBlocking, prio));
-    SK_HIP(hipEventCreateWithFlags(&lk.fork, hipEventDisableTiming));
-    SK_HIP(hipEventCreateWithFlags(&lk.join, hipEventDisableTiming));
-  }
+  if (!lk.stream) SK_TRY(create_lane_stream(lk));
   SK_TRY(reserve_lane(h, lk, max_batch, max_samples));
   if (slot > 0 && !lk.covers(max_batch, max_samples)) lk.reserved.push_back({max_batch, max_samples});
   return SK_OK;
@@ -1307,8 +1224,7 @@ int xt_forward_begin(xt_handle* h, int32_t slot, const void* d_wav, int32_t in_d
   StreamScope scope_(h, (hipStream_t)stream);
   SK_HIP(hipEventRecord(lk.fork, (hipStream_t)stream));
   SK_HIP(hipStreamWaitEvent(lk.stream, lk.fork, 0));
-  static const int cap = SK_AB_ENV_INT("SIDEKIT_AMD_SLOT_PERSIST_CAP", 1);
-  lk.persist_cap = cap;
+  lk.persist_cap = 1;   // one persistent workgroup per CU: room for the other batch in flight (launch_cfg)
   BatchMeta m;
   int rc = lane_frontend(h, lk, d_wav, in_dtype == XT_I16 ? 1 : 0, wav_ld, h_nsamples, B, L, m, lk.stream);
   if (rc == SK_OK) rc = lane_trunk(h, lk, m, d_emb, d_logits, lk.stream);
@@ -1415,94 +1331,20 @@ int xt_get_profile(xt_handle* h, double* ms, int64_t* launches, int32_t reset) {
 }
 
 // Kernel-level timing harness for tuning (diagnostic; not used by the product path): runs one trunk
-// convolution shape `iters` times on zero-initialised buffers and returns the mean device time.
-#ifdef SK_AB
-// shape 48 (A/B builds): the layer-1 pair kernel (conv_pair.hip) on random operands; variant bit 0: the first block's in-place shortcut form
-static int bench_conv_pair(int32_t B, int32_t T, int32_t iters, int32_t variant, float* ms_out, double* phase_cycles) {
-  const size_t act = (size_t)B * T * 80 * 32 * 2, wbytes = 32 * 32 * 9 * 2;
-  void *bufs[4] = {nullptr, nullptr, nullptr, nullptr}, *w[3] = {nullptr, nullptr, nullptr}, *zeros = nullptr;
-  float *cst = nullptr, *gate = nullptr, *se = nullptr, *colp = nullptr, *edge = nullptr;
-  const int tiles = cdiv(T, 8);
-  for (auto& p : bufs) SK_HIP(hipMalloc(&p, act));
-  for (auto& p : w) SK_HIP(hipMalloc(&p, wbytes));
-  SK_HIP(hipMalloc(&zeros, 256)); SK_HIP(hipMemset(zeros, 0, 256));
-  SK_HIP(hipMalloc((void**)&cst, 5 * 32 * 4)); SK_HIP(hipMalloc((void**)&gate, (size_t)B * 32 * 4));
-  SK_HIP(hipMalloc((void**)&se, (size_t)B * tiles * 4 * 32 * 4)); SK_HIP(hipMalloc((void**)&colp, (size_t)B * tiles * 2 * 32 * 4)); SK_HIP(hipMalloc((void**)&edge, (size_t)B * 6 * 32 * 4));
-  {
-    uint32_t x = 0x9E3779B9u;
-    auto next = [&]() { x = x * 1664525u + 1013904223u; return (float)((x >> 8) & 0xffff) / 32768.f - 1.f; };
-    std::vector<uint16_t> hb(act / 2);
-    for (int k = 0; k < 2; ++k) {   // O1 (post-ReLU: non-negative) and the block input
-      for (auto& v : hb) { const float f = next(); v = f32_to_bf16(f < 0 ? 0.f : f); }
-      SK_HIP(hipMemcpy(bufs[k], hb.data(), act, hipMemcpyHostToDevice));
-    }
-    std::vector<uint16_t> hw(wbytes / 2);
-    for (auto& p : w) { for (auto& v : hw) v = f32_to_bf16(0.05f * next()); SK_HIP(hipMemcpy(p, hw.data(), wbytes, hipMemcpyHostToDevice)); }
-    std::vector<float> c(5 * 32);
-    for (int i = 0; i < 32; ++i) { c[i] = 1.f; c[32 + i] = 0.f; c[64 + i] = 1.f; c[96 + i] = 0.f; c[128 + i] = 0.f; }
-    SK_HIP(hipMemcpy(cst, c.data(), c.size() * 4, hipMemcpyHostToDevice));
-    std::vector<float> gv((size_t)B * 32, 0.5f);
-    SK_HIP(hipMemcpy(gate, gv.data(), gv.size() * 4, hipMemcpyHostToDevice));
-  }
-  ConvPairArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.C = 32; pa.W = 80; pa.in = bufs[0]; pa.w2pack = w[0]; pa.scale2 = cst; pa.shift2 = cst + 32; pa.gate = gate;
-  if (variant & 1) { pa.sc_in = bufs[1]; pa.sc_wpack = w[2]; pa.sc_shift = cst + 128; } else { pa.shortcut = bufs[1]; }
-  pa.y_out = bufs[2]; pa.w1pack = w[1]; pa.scale1 = cst + 64; pa.shift1 = cst + 96; pa.o_out = bufs[3];
-  pa.se_part = se; pa.col_part = colp; pa.edge = edge; pa.zeros = zeros; pa.lens = Lens{nullptr, T}; pa.B = B; pa.H = T;
-  unsigned long long* stamps = nullptr;
-  const int nblk = 512;   // at most two persistent workgroups per CU
-  if (phase_cycles) { SK_HIP(hipMalloc((void**)&stamps, (size_t)nblk * 128)); SK_HIP(hipMemset(stamps, 0, (size_t)nblk * 128)); pa.stamps = stamps; }
-  hipEvent_t e0, e1;
-  SK_HIP(hipEventCreate(&e0)); SK_HIP(hipEventCreate(&e1));
-  for (int i = 0; i < 3; ++i) SK_TRY(launch_conv_pair(pa, nullptr));
-  SK_HIP(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i) SK_TRY(launch_conv_pair(pa, nullptr));
-  SK_HIP(hipEventRecord(e1, nullptr));
-  SK_HIP(hipEventSynchronize(e1));
-  SK_HIP(hipEventElapsedTime(ms_out, e0, e1));
-  *ms_out /= iters;
-  if (phase_cycles) {   // mean cycles between consecutive stamps (nine phases) of each workgroup's last item; [9] = the item, [10] = its 100-MHz ticks
-    std::vector<unsigned long long> hs((size_t)nblk * 16);
-    SK_HIP(hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 11; ++k) phase_cycles[k] = 0;
-    int n = 0;
-    for (int i = 0; i < nblk; ++i) {
-      if (!hs[(size_t)i * 16 + 9]) continue;
-      for (int k = 0; k < 9; ++k) phase_cycles[k] += (double)(hs[(size_t)i * 16 + k + 1] - hs[(size_t)i * 16 + k]);
-      phase_cycles[9] += (double)(hs[(size_t)i * 16 + 9] - hs[(size_t)i * 16]);
-      phase_cycles[10] += (double)hs[(size_t)i * 16 + 15];
-      ++n;
-    }
-    for (int k = 0; k < 11; ++k) phase_cycles[k] /= (n ? n : 1);
-    (void)hipFree(stamps);
-  }
-  for (auto p : bufs) (void)hipFree(p);
-  for (auto p : w) (void)hipFree(p);
-  (void)hipFree(zeros); (void)hipFree(cst); (void)hipFree(gate); (void)hipFree(se); (void)hipFree(colp); (void)hipFree(edge);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return SK_OK;
-}
-
-#endif
+// convolution shape `iters` times on random operands and returns the mean device time.
 
 int sk_bench_conv(int32_t shape, int32_t dtype, int32_t B, int32_t T, int32_t iters, int32_t variant, float* ms_out, double* phase_cycles) {
   SK_CHECK(ms_out && B > 0 && T > 0 && iters > 0, SK_EARG, "sk_bench_conv: bad arguments");
-#ifdef SK_AB
-  if (shape == 48) {
-    SK_CHECK(dtype == XT_BF16, SK_EARG, "sk_bench_conv: the pair kernel is bf16 only");
-    return bench_conv_pair(B, T, iters, variant, ms_out, phase_cycles);   // phase_cycles: 11 doubles here
-  }
-#endif
   ConvGeom g;
   const int dt = dtype == XT_BF16 ? DT_BF16 : DT_F32;
   SK_TRY(conv_geom(shape, dt, &g));
   const int hin = T, hout = g.stride == 2 ? (T + 1) / 2 : T;
   const size_t in_b = (size_t)B * hin * g.win * g.cin * g.eb, out_b = (size_t)B * hout * (g.win / g.stride) * g.cout * g.eb;
+  BenchAllocs mem;
   void *in = nullptr, *out = nullptr, *w = nullptr, *zeros = nullptr; float *sc = nullptr, *sh = nullptr, *se = nullptr;
-  SK_HIP(hipMalloc(&in, in_b)); SK_HIP(hipMalloc(&out, out_b)); SK_HIP(hipMalloc(&w, conv_pack_bytes(g) + 4096));
-  SK_HIP(hipMalloc(&zeros, 256)); SK_HIP(hipMalloc((void**)&sc, g.cout * 4)); SK_HIP(hipMalloc((void**)&sh, g.cout * 4));
-  SK_HIP(hipMalloc((void**)&se, (size_t)B * (hout / g.th + 2) * (g.wm > 4 ? g.wm : 4) * g.cout * 4));
+  SK_TRY(mem.alloc(&in, in_b)); SK_TRY(mem.alloc(&out, out_b)); SK_TRY(mem.alloc(&w, conv_pack_bytes(g) + 4096));
+  SK_TRY(mem.alloc(&zeros, 256)); SK_TRY(mem.alloc(&sc, g.cout * 4)); SK_TRY(mem.alloc(&sh, g.cout * 4));
+  SK_TRY(mem.alloc(&se, (size_t)B * (hout / g.th + 2) * (g.wm > 4 ? g.wm : 4) * g.cout * 4));
   SK_HIP(hipMemset(zeros, 0, 256));
   {  // random operands (uniform in [-1, 1)): constant fills toggle no bits and let the chip hold a clock real data never sees
     auto fill = [&](void* dst, size_t bytes, float amp) -> int {
@@ -1530,11 +1372,11 @@ int sk_bench_conv(int32_t shape, int32_t dtype, int32_t B, int32_t T, int32_t it
   unsigned long long* stamps = nullptr;
   float *gate = nullptr; void* scut = nullptr; float *colp = nullptr, *edge = nullptr;
   if (variant & 8) {   // statistics-mode epilogue
-    SK_HIP(hipMalloc((void**)&colp, (size_t)nblk * 2 * g.cout * 4)); SK_HIP(hipMalloc((void**)&edge, (size_t)B * 6 * g.cout * 4));
+    SK_TRY(mem.alloc(&colp, (size_t)nblk * 2 * g.cout * 4)); SK_TRY(mem.alloc(&edge, (size_t)B * 6 * g.cout * 4));
     a.se_part = se; a.col_part = colp; a.edge = edge;
   }
   if (variant & 16) {  // residual-mode epilogue
-    SK_HIP(hipMalloc((void**)&gate, (size_t)B * g.cout * 4)); SK_HIP(hipMalloc(&scut, out_b));
+    SK_TRY(mem.alloc(&gate, (size_t)B * g.cout * 4)); SK_TRY(mem.alloc(&scut, out_b));
     {
       std::vector<float> gv((size_t)B * g.cout, 0.5f);
       SK_HIP(hipMemcpy(gate, gv.data(), gv.size() * 4, hipMemcpyHostToDevice));
@@ -1542,9 +1384,9 @@ int sk_bench_conv(int32_t shape, int32_t dtype, int32_t B, int32_t T, int32_t it
     }
     a.gate = gate; a.shortcut = scut;
   }
-  if (phase_cycles) { SK_HIP(hipMalloc((void**)&stamps, (size_t)nblk * 64)); SK_HIP(hipMemset(stamps, 0, (size_t)nblk * 64)); a.stamps = stamps; }
+  if (phase_cycles) { SK_TRY(mem.alloc(&stamps, (size_t)nblk * 64)); SK_HIP(hipMemset(stamps, 0, (size_t)nblk * 64)); a.stamps = stamps; }
   hipEvent_t e0, e1;
-  SK_HIP(hipEventCreate(&e0)); SK_HIP(hipEventCreate(&e1));
+  SK_TRY(mem.event(&e0)); SK_TRY(mem.event(&e1));
   for (int i = 0; i < 3; ++i) SK_TRY(launch_conv(shape, dt, a, nullptr));
   SK_HIP(hipEventRecord(e0, nullptr));
   for (int i = 0; i < iters; ++i) SK_TRY(launch_conv(shape, dt, a, nullptr));
@@ -1565,11 +1407,7 @@ int sk_bench_conv(int32_t shape, int32_t dtype, int32_t B, int32_t T, int32_t it
       ++n;
     }
     for (int k = 0; k < 8; ++k) phase_cycles[k] /= (n ? n : 1);
-    (void)hipFree(stamps);
   }
-  if (colp) (void)hipFree(colp); if (edge) (void)hipFree(edge); if (gate) (void)hipFree(gate); if (scut) (void)hipFree(scut);
-  (void)hipFree(in); (void)hipFree(out); (void)hipFree(w); (void)hipFree(zeros); (void)hipFree(sc); (void)hipFree(sh); (void)hipFree(se);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return SK_OK;
 }
 

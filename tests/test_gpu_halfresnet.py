@@ -238,32 +238,63 @@ def test_bf16_row_tile_boundaries_and_per_utterance(model):
         model.compute_dtype = "fp32"
 
 
-@pytest.mark.ab_variant
-def test_ab_paths_agree(gpu, monkeypatch):
-    """The A/B switches of the -DSK_AB build (shortcut as a stored tensor / mel projection as a GEMM / attention unfused) are the older
-    formulations of the same arithmetic: they must agree with the default path (bf16 bit for bit on the shortcut side)."""
+def _pooling_in_float64(sd, l4, h, lens_rows, dtype):
+    """attention.4 + softmax over time + weighted mean / std (pooling.py:161-168) in float64 on the kernel's own inputs: layer-4 rows
+    [B][T'][10][256] (columns d' = f*256 + c), attention.0 rows h [B*T'][128]; in bf16 the MFMA operands h and attention.4's weights are bf16."""
+    B, T4 = l4.shape[0], l4.shape[1]
+    x = l4.reshape(B, T4, 2560).double()
+    dp = torch.arange(2560)
+    perm = (dp % 256) * 10 + dp // 256                                       # reference channel d = c*10 + f of trunk column d'
+    w2 = sd["stat_pooling.attention.4.weight"].float().cpu().reshape(2560, 128)[perm]
+    b2 = sd["stat_pooling.attention.4.bias"].float().cpu()[perm].double()
+    hh = h.reshape(B, T4, 128)
+    if dtype == "bf16":
+        w2, hh = w2.bfloat16().float(), hh.bfloat16().float()
+    out = torch.zeros(B, 5120, dtype=torch.float64)
+    for b, n in enumerate(lens_rows):
+        e = hh[b, :n].double() @ w2.double().T + b2
+        w = torch.softmax(e, dim=0)
+        mu = (x[b, :n] * w).sum(0)
+        out[b, :2560] = mu
+        out[b, 2560:] = torch.sqrt(torch.clamp((x[b, :n] ** 2 * w).sum(0) - mu * mu, min=1e-9))
+    return out
+
+
+def test_fused_attention_pooling_matches_float64(gpu):
+    """bf16 path: attention.4, the softmax over time and the weighted statistics in one kernel (csrc/pool.hip, att_fused_kernel) against the same
+    arithmetic in float64 on the kernel's inputs (debug taps "layer4" and "att_h"): within 2e-6 relative, on a short ragged batch and on a long one
+    (T' = 157 / 118: several 64-row chunks)."""
+    m = Xtractor(64, model_archi="halfresnet34", loss="aam", seed=5).to(gpu).eval()
+    m.compute_dtype = "bf16"
+    sd = m.state_dict()
     torch.manual_seed(21)
     wav = 0.1 * torch.randn(3, 30000).cuda()
-    lens = [30000, 17000, 22222]
-    base = Xtractor(64, model_archi="halfresnet34", loss="aam", seed=5).to(gpu).eval()
-    long_wav, long_lens = 0.1 * torch.randn(2, 200000).cuda(), [200000, 150001]      # T' = 157 / 118: several 64-row chunks in the fused pooling
-    out, out_long = {}, {}
-    for dtype in ("fp32", "bf16"):
-        base.compute_dtype = dtype
-        out[dtype] = base(wav, is_eval=True, lengths=lens)[1]
-        out_long[dtype] = base(long_wav, is_eval=True, lengths=long_lens)[1]
-    for var in ("SIDEKIT_AMD_SHORTCUT_TENSOR", "SIDEKIT_AMD_MEL_GEMM", "SIDEKIT_AMD_ATT_SEPARATE"):
-        monkeypatch.setenv(var, "1")
-        alt = Xtractor(64, model_archi="halfresnet34", loss="aam", seed=5).to(gpu).eval()
-        for dtype in ("fp32", "bf16"):
-            alt.compute_dtype = dtype
-            e = alt(wav, is_eval=True, lengths=lens)[1]                 # the switch is read when the native handle is made (first forward)
-            assert rel(e, out[dtype]) < (2e-5 if dtype == "fp32" else 2e-2), (var, dtype)
-            if var == "SIDEKIT_AMD_ATT_SEPARATE":   # the fused attention / statistics kernel computes the same scores: only the order of the time sums differs
-                assert rel(e, out[dtype]) < 2e-6, (var, dtype, rel(e, out[dtype]))
-                e_long = alt(long_wav, is_eval=True, lengths=long_lens)[1]
-                assert rel(e_long, out_long[dtype]) < 2e-6, (var, dtype, rel(e_long, out_long[dtype]))
-        monkeypatch.delenv(var)
+    cases = [(wav, [30000, 17000, 22222]), (0.1 * torch.randn(2, 200000).cuda(), [200000, 150001])]
+    m.set_debug(True)
+    try:
+        for x, lens in cases:
+            m(x, is_eval=True, lengths=lens)
+            raw = m.debug_taps(["layer4", "att_h", "pooled"])
+            B = len(lens)
+            l4 = bf16_to_f32(raw["layer4"])
+            T4 = l4.numel() // (B * 2560)
+            l4 = l4.reshape(B, T4, 10, 256)
+            h = torch.from_numpy(raw["att_h"].view(numpy.float32).copy()).reshape(B * T4, 128)
+            pooled = torch.from_numpy(raw["pooled"].view(numpy.float32).copy()).reshape(B, 5120)
+            rows = [_layer4_rows(n) for n in lens]
+            assert max(rows) == T4, (rows, T4)
+            ref = _pooling_in_float64(sd, l4, h, rows, "bf16")
+            assert rel(pooled, ref) < 2e-6, (lens, rel(pooled, ref))
+    finally:
+        m.set_debug(False)
+
+
+def _layer4_rows(n_samples):
+    """layer-4 rows of an utterance of n_samples: 1 + n // 160 feature frames, halved three times (ceil)"""
+    t = 1 + n_samples // 160
+    for _ in range(3):
+        t = (t + 1) // 2
+    return t
 
 
 def test_profile_slots(model):
@@ -304,10 +335,9 @@ SMALL_GRID_CASES = [(1, 64000, False), (1, 45 * 16000, False), (3, 48000, True),
 
 
 def _small_grid_check(gpu, monkeypatch, settings, cases):
-    """models with the same weights under each (SIDEKIT_AMD_SMALL_GRID, SIDEKIT_AMD_GATE_PROLOGUE) setting -> same bits as the first one, every case, both precisions"""
+    """models with the same weights under each SIDEKIT_AMD_SMALL_GRID setting -> same bits as the first one, every case, both precisions"""
     models = {}
-    for key, (grid, gate) in settings.items():
-        monkeypatch.setenv("SIDEKIT_AMD_GATE_PROLOGUE", gate)
+    for key, grid in settings.items():
         monkeypatch.setenv("SIDEKIT_AMD_SMALL_GRID", grid)
         m = Xtractor(64, model_archi="halfresnet34", loss="aam", seed=41).to(gpu).eval()
         m.compute_dtype = "fp32"; m(torch.zeros(1, 4000, device="cuda") + 0.01, is_eval=True)      # the handles are created under this setting
@@ -333,75 +363,7 @@ def test_small_grid_forms_give_the_bits_of_the_batch_forms(gpu, monkeypatch):
     conv2 of layers 3-4 in 3- / 2-row tiles (csrc/conv3x3.hip, "Small-grid forms").  Forced off / on and chosen automatically (SIDEKIT_AMD_SMALL_GRID = 0 /
     2 / 1) on models with the same weights, x-vectors and logits are the same bits at every batch size -- batch 1 at 4 s and 45 s (563 row tiles), ragged
     batches, batches of 12 and 13 (either side of the threshold), a batch of 40 -- in both precisions."""
-    _small_grid_check(gpu, monkeypatch, {"never": ("0", "0"), "always": ("2", "0"), "auto": ("1", "0")}, SMALL_GRID_CASES)
-
-
-@pytest.mark.ab_variant
-def test_in_convolution_gate_forms_give_the_bits_of_the_launch(gpu, monkeypatch):
-    """A/B build only (csrc/se_gate_inl.h; both forms measured slower than the launch in round 5): two ways of computing the SE gate
-    INSIDE conv2 instead of by the launch of ``se_pre_kernel`` between conv1 and conv2 (sidekit/nnet/res_net.py:272-281,316-319) -- a fifth wave of
-    conv2 (layers 1-2) and a prologue in which every workgroup of an utterance walks the 1024 virtual threads of ``se_pre_kernel`` on its 256 real ones
-    (every layer; selected for at most 8 utterances, xt_handle::GATE_AB_MAX_B, or always).  Same bits as the launch at every batch size."""
-    _small_grid_check(gpu, monkeypatch, {"launch": ("0", "0"), "wave always": ("2", "2"), "wave small": ("1", "1"), "prologue always": ("1", "4"), "prologue small": ("1", "3")},
-                      [c for c in SMALL_GRID_CASES if c[0] != 13])
-
-
-@pytest.mark.ab_variant
-def test_layer1_pair_kernel_gives_the_bits_of_the_two_launches(gpu, monkeypatch):
-    """A/B build only (round 6; measured SLOWER than the two launches, profiles/r06_conv_pair_L1.txt, so the product does not carry it): conv2 of
-    block k and conv1 of block k + 1 of layer 1 as ONE kernel (csrc/conv_pair.hip: the block output reaches the next conv1 through LDS;
-    sidekit/nnet/res_net.py:309-320, two consecutive blocks; SIDEKIT_AMD_PAIR=1) against the two stand-alone launches: the stage taps after every
-    layer, the x-vectors and the logits are the same BITS -- the pair kernel's tiles, MFMA order, epilogue arithmetic and SE-sum order are the
-    stand-alone kernels'.  Batches of 1 .. 256; uniform, ragged, clips shorter than one 8-row tile and lengths that leave one valid row in the last
-    tile; a 45-s utterance (563 row tiles); pipelined submits."""
-    def make(env):
-        if env:
-            monkeypatch.setenv("SIDEKIT_AMD_PAIR", "1")
-        m = Xtractor(64, model_archi="halfresnet34", loss="aam", seed=43).to(gpu).eval()
-        m.compute_dtype = "bf16"
-        m(torch.zeros(1, 4000, device="cuda") + 0.01, is_eval=True)
-        if env:
-            monkeypatch.delenv("SIDEKIT_AMD_PAIR")
-        return m
-    plain, paired = make(False), make(True)          # the switch is read per forward: set around every call of `paired`
-    g = torch.Generator(device="cuda").manual_seed(19)
-    names = ["stem", "layer1", "layer2", "layer3", "layer4"]
-
-    def run(m, env, wav, lens):
-        if env:
-            monkeypatch.setenv("SIDEKIT_AMD_PAIR", "1")
-        m.set_debug(True)
-        logits, emb = m(wav, is_eval=True, lengths=lens)
-        taps = m.debug_taps(names)
-        m.set_debug(False)
-        if env:
-            monkeypatch.delenv("SIDEKIT_AMD_PAIR")
-        return logits, emb, taps
-
-    cases = [(1, 64000, None), (3, 48000, [48000, 1290, 31999]), (2, 2400, [2400, 1130]),            # 16 / 8 frames: two tiles / exactly one tile
-             (5, 20000, [20000, 1280 + 159, 1280 * 2, 1280 * 2 + 160, 19999]),                      # 9, 17, 18 rows: one / two valid rows in the last tile
-             (1, 45 * 16000, None), (40, 32000, "ragged"), (256, 16000, None), (130, 24000, "ragged")]
-    for B, L, lens in cases:
-        wav = 0.1 * torch.randn(B, L, device="cuda", generator=g)
-        if lens == "ragged":
-            lens = torch.randint(L // 4, L + 1, (B,), generator=torch.Generator().manual_seed(B * 5 + 3)).tolist()
-        (la, ea, ta), (lb, eb, tb) = run(paired, True, wav, lens), run(plain, False, wav, lens)
-        for n in names:
-            assert numpy.array_equal(ta[n], tb[n]), (B, L, n, int((ta[n] != tb[n]).sum()))
-        same = lambda x, y: torch.equal(x, y) or bool(((x == y) | (torch.isnan(x) & torch.isnan(y))).all())      # T' = 1 clips are NaN in both (the reference's unbiased std)
-        assert same(ea, eb) and same(la, lb), (B, L)
-    # two batches in flight (one workgroup per CU for the persistent grids: persist_cap)
-    w = [0.1 * torch.randn(256, 32000, device="cuda", generator=g) for _ in range(3)]
-    want = [plain(x, is_eval=True)[1].clone() for x in w]
-    monkeypatch.setenv("SIDEKIT_AMD_PAIR", "1")
-    t = [paired.submit(w[0]), paired.submit(w[1])]
-    got = [paired.collect(t[0])[1]]
-    t.append(paired.submit(w[2]))
-    got += [paired.collect(t[1])[1], paired.collect(t[2])[1]]
-    torch.cuda.synchronize()
-    monkeypatch.delenv("SIDEKIT_AMD_PAIR")
-    for a, b in zip(got, want):
-        assert torch.equal(a, b)
+    _small_grid_check(gpu, monkeypatch, {"never": "0", "always": "2", "auto": "1"}, SMALL_GRID_CASES)
 
 
 def test_very_short_clips_as_the_first_call(gpu):

@@ -81,39 +81,40 @@ def test_wav_variable_length_batch(gpu, fx):
             m.compute_dtype = None
 
 
-@pytest.mark.ab_variant
-def test_mfcc_fft_matches_the_dft_contraction(gpu, fx, monkeypatch):
-    """The MFCC spectrum as a 2048-point real FFT (frontend_fft.hip) against the round-1 form, a (frames x 1024) x (1024 x 2050)
-    DFT contraction on the exact-f32 matrix cores (SIDEKIT_AMD_MFCC_DFT_GEMM=1), and both against the oracle: ragged lengths
-    with reflect-padded edges, features after CMVN."""
+def test_mfcc_fft_matches_the_oracle(gpu, fx):
+    """The MFCC spectrum as a 2048-point real FFT (frontend_fft.hip) against the oracle: ragged lengths with reflect-padded edges,
+    features after CMVN, each utterance alone and the same utterances as one ragged batch."""
     lens = [16000 + 17, 40000, 14 * 512 + 5, 64000]       # incl. the shortest utterance the TDNN context admits (15 frames)
     torch.manual_seed(9)
     wav = 0.1 * torch.randn(len(lens), max(lens))
-    m_fft = _model(gpu, fx, "aam")
-    monkeypatch.setenv("SIDEKIT_AMD_MFCC_DFT_GEMM", "1")
-    m_dft = _model(gpu, fx, "aam")
-    monkeypatch.delenv("SIDEKIT_AMD_MFCC_DFT_GEMM")
+    m = _model(gpu, fx, "aam")
     for i, n in enumerate(lens):
         ref = ofe.mfcc_frontend(wav[i:i + 1, :n])
-        a = m_fft.features(wav[i:i + 1, :n].cuda())
-        b = m_dft.features(wav[i:i + 1, :n].cuda())
-        assert a.shape == ref.shape and rel(a, ref) < TOL and rel(b, ref) < TOL and rel(a, b) < TOL, (i, n)
-    fa = m_fft.features(wav.cuda(), lengths=lens)         # the same utterances as one ragged batch
+        a = m.features(wav[i:i + 1, :n].cuda())
+        assert a.shape == ref.shape and rel(a, ref) < TOL, (i, n)
+    fa = m.features(wav.cuda(), lengths=lens)
     for i, n in enumerate(lens):
         t = 1 + n // 512
         assert rel(fa[i, :, :t], ofe.mfcc_frontend(wav[i:i + 1, :n])[0]) < TOL, (i, n)
 
 
-@pytest.mark.ab_variant
-def test_large_gemm_tiling_is_bit_identical(gpu, fx, monkeypatch):
-    """128 x 128 tiles (problems of >= 2048 rows) against the 64 x 64 kernel (SIDEKIT_AMD_GEMM64=1): the same k-ordered FMA
-    chain per output element, so the TDNN forward of a 40-utterance ragged batch (7k rows) must not move by one bit."""
+def test_large_gemm_tiling_is_bit_identical(gpu, fx):
+    """128 x 128 tiles (problems of >= 2048 rows) against the 64 x 64 kernel: the same k-ordered FMA chain per output element.  A 40-utterance
+    ragged batch (7k rows: the TDNN layers take the 128 x 128 tiling) against each utterance alone (< 2048 rows: the 64 x 64 kernel) -- the
+    pooled statistics (per utterance, in an order set by its own row count: pool.hip, mean_std_kernel) and the x-vectors (embedding GEMM
+    summed in K slices for any batch size) must not move by one bit."""
     m = _model(gpu, fx, "aam")
     lens = numpy.random.RandomState(5).randint(32000, 160001, (40,)).tolist()
     g = torch.Generator(device="cuda").manual_seed(11)
     wav = 0.1 * torch.randn(len(lens), max(lens), device="cuda", generator=g)
-    logits_a, emb_a = m(wav, is_eval=True, lengths=lens)
-    monkeypatch.setenv("SIDEKIT_AMD_GEMM64", "1")
-    logits_b, emb_b = m(wav, is_eval=True, lengths=lens)
-    monkeypatch.delenv("SIDEKIT_AMD_GEMM64")
-    assert torch.equal(emb_a, emb_b) and torch.equal(logits_a, logits_b)
+    m.set_debug(True)
+    try:
+        _, emb = m(wav, is_eval=True, lengths=lens)
+        pooled = m.debug_taps(["pooled"])["pooled"].view(numpy.float32).reshape(len(lens), 3072).copy()
+        for i, n in enumerate(lens):
+            _, e1 = m(wav[i:i + 1, :n], is_eval=True)
+            p1 = m.debug_taps(["pooled"])["pooled"].view(numpy.float32)
+            assert numpy.array_equal(p1, pooled[i]), (i, n)
+            assert torch.equal(e1[0], emb[i]), (i, n)
+    finally:
+        m.set_debug(False)
