@@ -69,9 +69,17 @@ struct DevBuf {
 };
 
 
+// A lane's workspace buffers; ws_plan gives every one's size.
+enum Ws { WS_S, WS_FEAT, WS_ACT0, WS_ACT1, WS_ACT2, WS_ACT3, WS_SE, WS_COL, WS_EDGE, WS_SPLITK, WS_GATE, WS_CTX, WS_RB, WS_H, WS_E, WS_POOLED,
+          WS_PRE, WS_INT, WS_COUNT };
+static const char* const WS_NAMES[WS_COUNT] = {"spectrum", "feature", "activation 0", "activation 1", "activation 2", "activation 3",
+                                               "SE statistics", "SE column sums", "SE edge rows", "split-K", "SE gate", "pooling context",
+                                               "attention row bias", "attention hidden", "attention energies", "pooled", "embedding", "integer"};
+struct WsPlan { size_t bytes[WS_COUNT] = {}; };
+
 // One lane of the forward: its own activation / statistics workspace and pinned staging ring for per-utterance integers.
 struct Lane {
-  DevBuf ws_S, ws_feat, ws_act[4], ws_se, ws_col, ws_edge, ws_splitk, ws_gate, ws_ctx, ws_rb, ws_h, ws_e, ws_pooled, ws_pre, ws_int;
+  DevBuf ws[WS_COUNT];
   static constexpr int RING = 4;
   int* ring_host[RING] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ring_ev[RING];
@@ -81,7 +89,8 @@ struct Lane {
   hipStream_t stream = nullptr;        // lanes 1 .. n-1 only: the stream that part of the batch runs on
   hipEvent_t fork = nullptr, join = nullptr;
   int persist_cap = 0;                 // set by xt_forward_begin: persistent convolution grids leave room for the other batch in flight (conv3x3.hip, launch_cfg)
-  std::vector<std::pair<int, int64_t>> reserved;   // side lanes: the (utterances, samples) shapes this lane's workspace has been sized for
+  // the (utterances, samples) shapes this lane's workspace has been sized for: a batch runs in it when one of them covers it in BOTH dimensions
+  std::vector<std::pair<int, int64_t>> reserved;
   bool covers(int B, int64_t L) const {
     for (auto& r : reserved) if (r.first >= B && r.second >= L) return true;
     return false;
@@ -138,23 +147,22 @@ struct xt_handle {
   struct TdnnLayer { float *w, *bias, *scale, *shift; int cin, cout, k, dil; };
   std::vector<TdnnLayer> tdnn;
 
-  // workspace: lanes.  Lane 0 runs on the caller's stream and is sized for the whole batch; lanes 1 .. n-1 (own streams, sized for a
+  // workspace: lanes.  Lane 0 is sized for the whole batch (its record of reserved shapes is the handle's); lanes 1 .. n-1 (sized for a
   // part of a batch) exist only while the split forward is on: a batch of >= 2 LANE_MIN utterances is then forwarded as n parts on n
   // HIP streams, so that one part's latency-bound kernels (SE gates, pooling, front-end: 0.8 ms of a 6.5-ms step) run under another
   // part's convolutions.  Utterances are independent and every kernel is batch-size invariant, so the x-vectors are the same bits.
-  std::vector<std::pair<int, int64_t>> reserved;   // (batch, samples) shapes xt_reserve has sized the workspace for: a batch runs when one of them covers it in BOTH dimensions
   static constexpr int MAX_LANES = 4;
   Lane lane[MAX_LANES];
   int lanes = lanes_from_env();                    // 1: serial (profiling: per-kernel durations mean something), 2 (default) .. 4: that many parts of a batch side by side
   static constexpr int LANE_MIN = 64;              // utterances per lane below which a batch is not split further
   bool norm_embedding = true;
-  // The stream contract, enforced (round 5).  Workspaces are ordered by STREAM order: an unsplit forward runs on the caller's stream in lane
-  // 0's workspace, a split or pipelined one on streams the handle owns behind an event recorded on the caller's stream.  All of that assumes
-  // consecutive calls arrive on ONE stream; round 4's soak test found the first hole in it (a plain forward racing a pipelined batch in slot
-  // 0).  Now every call that touches a workspace ends by recording `tail` on the stream it was given, and a call that arrives on ANOTHER
-  // stream first makes that stream wait for `tail` and for every lane's completion event -- the library orders itself, whatever stream a
-  // call comes from.  Two host threads inside one handle at once are refused (SK_ESTATE): the host-side bookkeeping (pinned rings, lane
-  // state, reserved shapes) has no lock and is not meant to have one (one handle, one driving thread).
+  // The stream contract.  Workspaces are ordered by STREAM order: an unsplit forward runs on the caller's stream in lane 0's workspace, a
+  // split or pipelined one on streams the handle owns behind an event recorded on the caller's stream.  That alone assumes consecutive
+  // calls arrive on ONE stream (a plain forward on another stream raced a pipelined batch in slot 0).  So every call that touches a
+  // workspace ends by recording `tail` on the stream it was given, and a call that arrives on ANOTHER stream first makes that stream wait
+  // for `tail` and for every lane's completion event -- the library orders itself, whatever stream a call comes from (Entry).  Two host
+  // threads inside one handle at once are refused (SK_ESTATE): the host-side bookkeeping (pinned rings, lane state, reserved shapes) has
+  // no lock and is not meant to have one (one handle, one driving thread).
   std::atomic<bool> busy{false};
   hipStream_t last_stream = nullptr;
   bool has_last = false;
@@ -174,37 +182,69 @@ struct xt_handle {
 
 namespace sk {
 
-// One host thread at a time per handle; see xt_handle::busy.
-struct EntryGuard {
-  xt_handle* h; bool ok;
-  explicit EntryGuard(xt_handle* h_) : h(h_), ok(h_ && !h_->busy.exchange(true, std::memory_order_acquire)) {}
-  ~EntryGuard() { if (ok) h->busy.store(false, std::memory_order_release); }
-};
-#define SK_ENTER(h)                                                                                                   \
-  SK_CHECK((h) != nullptr, SK_EARG, "null handle");                                                                   \
-  sk::EntryGuard guard_(h);                                                                                           \
-  SK_CHECK(guard_.ok, SK_ESTATE, "concurrent entry: another host thread is inside this handle (a handle is driven by one thread at a time; use one handle per thread)")
-
-// A call that touches a workspace and arrives on another stream than the previous one: order it behind the previous stream's tail and behind
-// whatever the handle's own streams still run (pipelined batches, xt_forward_begin).
-static int enter_stream(xt_handle* h, hipStream_t st) {
-  if (h->has_last && h->last_stream != st) {
-    SK_HIP(hipStreamWaitEvent(st, h->tail, 0));
-    for (int k = 0; k < xt_handle::MAX_LANES; ++k)
-      if (h->lane[k].stream) SK_HIP(hipStreamWaitEvent(st, h->lane[k].join, 0));
+// One call inside a handle, for the stream contract of xt_handle.
+//   lock():  one host thread at a time (xt_handle::busy).
+//   run():   lock() and the state checks of a forward of B x L samples: finalized, and lane 0 has a reserved shape that covers it.
+//   order(): the call touches a workspace on `st`.  Arriving on another stream than the previous call, it waits for the previous stream's
+//            tail and for whatever the handle's own streams still run (pipelined batches, xt_forward_begin).  `in_lane0`: the call runs on
+//            `st` in lane 0's workspace, where a pipelined batch of slot 0 may still be running on lane 0's own stream -- it waits for that
+//            too (a small plain forward between two submits raced with slot 0 without it).  From then on every exit records `tail` on `st`,
+//            after an error too: whatever was queued before the error is what the next stream must wait for.
+struct Entry {
+  xt_handle* h;
+  hipStream_t st;
+  bool locked = false, ordered = false;
+  explicit Entry(xt_handle* h_, void* st_ = nullptr) : h(h_), st((hipStream_t)st_) {}
+  ~Entry() {
+    if (ordered) {
+      if (!h->tail && hipEventCreateWithFlags(&h->tail, hipEventDisableTiming) != hipSuccess) h->tail = nullptr;
+      else if (hipEventRecord(h->tail, st) == hipSuccess) { h->last_stream = st; h->has_last = true; }
+    }
+    if (locked) h->busy.store(false, std::memory_order_release);
   }
-  return SK_OK;
-}
-// ... and leaves its mark on the stream it ran on (also after an error: whatever was queued before the error is what the next stream must wait for).
-static void leave_stream(xt_handle* h, hipStream_t st) {
-  if (!h->tail && hipEventCreateWithFlags(&h->tail, hipEventDisableTiming) != hipSuccess) { h->tail = nullptr; return; }
-  if (hipEventRecord(h->tail, st) == hipSuccess) { h->last_stream = st; h->has_last = true; }
-}
-struct StreamScope {
-  xt_handle* h; hipStream_t st;
-  StreamScope(xt_handle* h_, hipStream_t st_) : h(h_), st(st_) {}
-  ~StreamScope() { leave_stream(h, st); }
+  int lock() {
+    SK_CHECK(h != nullptr, SK_EARG, "null handle");
+    locked = !h->busy.exchange(true, std::memory_order_acquire);
+    SK_CHECK(locked, SK_ESTATE, "concurrent entry: another host thread is inside this handle (a handle is driven by one thread at a time; use one handle per thread)");
+    return SK_OK;
+  }
+  int run(int B, int64_t L) {
+    SK_TRY(lock());
+    SK_CHECK(h->finalized, SK_ESTATE, "forward before xt_finalize (load_state_dict)");
+    SK_CHECK(B > 0, SK_EARG, "empty batch");
+    SK_CHECK(!h->lane[0].reserved.empty(), SK_ESTATE, "forward before xt_reserve");
+    SK_CHECK(h->lane[0].covers(B, L), SK_EWORKSPACE, "batch of %d x %lld samples exceeds every reserved workspace shape: call xt_reserve(%d, %lld)",
+             B, (long long)L, B, (long long)L);
+    SK_HIP(hipSetDevice(h->device));
+    return SK_OK;
+  }
+  int order(bool in_lane0) {
+    if (h->has_last && h->last_stream != st) {
+      SK_HIP(hipStreamWaitEvent(st, h->tail, 0));
+      for (int k = 0; k < xt_handle::MAX_LANES; ++k)
+        if (h->lane[k].stream) SK_HIP(hipStreamWaitEvent(st, h->lane[k].join, 0));
+    }
+    ordered = true;
+    if (in_lane0 && h->lane[0].stream) SK_HIP(hipStreamWaitEvent(st, h->lane[0].join, 0));
+    return SK_OK;
+  }
 };
+
+// Records the `join` event of lanes [k0, k1) on their streams whatever happened before, so that the next call and xt_forward_end order
+// behind everything that was queued (and, with `wait`, the caller's stream `st` as well): an error in one part must not leave the others
+// running unjoined while the next call reuses their workspaces.  A lane whose join fails is drained on the host.  Returns rc, or the
+// failure to join when rc is SK_OK; nothing here sets an error message otherwise, so the first error's message is the one kept.
+static int join_lanes(xt_handle* h, int k0, int k1, hipStream_t st, bool wait, int rc) {
+  for (int k = k0; k < k1; ++k) {
+    Lane& lk = h->lane[k];
+    const bool joined = hipEventRecord(lk.join, lk.stream) == hipSuccess && (!wait || hipStreamWaitEvent(st, lk.join, 0) == hipSuccess);
+    if (!joined) {
+      (void)hipStreamSynchronize(lk.stream);
+      if (rc == SK_OK) { rc = SK_EHIP; set_error("joining lane %d failed", k); }
+    }
+  }
+  return rc;
+}
 
 // sk_bench_conv's device buffers and events, released on every return (the early ones of SK_HIP / SK_TRY included)
 struct BenchAllocs {
@@ -628,8 +668,8 @@ static int ring_begin(Lane& ln) {
   return SK_OK;
 }
 static int push_ints(Lane& ln, const std::vector<int>& v, size_t slot_off, const int** dptr, hipStream_t st) {
-  int* base = (int*)ln.ws_int.p;
-  SK_CHECK((slot_off + v.size()) * 4 <= ln.ws_int.bytes, SK_EWORKSPACE, "integer workspace too small");
+  int* base = (int*)ln.ws[WS_INT].p;
+  SK_CHECK((slot_off + v.size()) * 4 <= ln.ws[WS_INT].bytes, SK_EWORKSPACE, "integer workspace too small");   // the ring's offsets depend on the call
   int* stage = ln.ring_host[ln.ring_cur] + slot_off;
   memcpy(stage, v.data(), v.size() * 4);
   SK_HIP(hipMemcpyAsync(base + slot_off, stage, v.size() * 4, hipMemcpyHostToDevice, st));
@@ -646,14 +686,13 @@ static int frontend_rows(xt_handle* h, Lane& ln, const void* d_wav, int pcm16, i
   const FrontCfg& f = h->fc;
   const int M = m.R ? m.R : m.B * m.T;
   const bool mfcc = h->cfg.arch == XT_ARCH_TDNN;
-  float* logmel = mfcc ? (float*)ln.ws_act[3].p : d_feat_rows;   // MFCC: the DCT follows
+  float* logmel = mfcc ? (float*)ln.ws[WS_ACT3].p : d_feat_rows;   // MFCC: the DCT follows
   // 1) |rFFT(window * preemph(frame))|^2, one wavefront per frame (frontend_fft.hip)
   FftArgs fa;
   fa.n_fft = f.n_fft;
   fa.wav = d_wav; fa.pcm16 = pcm16; fa.wav_ld = wav_ld; fa.nsamples = m.d_nsamples; fa.nsamples_uniform = m.nsamples_uniform; fa.window = h->d_window;
-  fa.tw512 = h->d_tw512; fa.tw1024 = h->d_tw1024; fa.P = (float*)ln.ws_S.p; fa.ldp = h->nbp; fa.M = M; fa.t_max = m.T; fa.hop = f.hop;
+  fa.tw512 = h->d_tw512; fa.tw1024 = h->d_tw1024; fa.P = (float*)ln.ws[WS_S].p; fa.ldp = h->nbp; fa.M = M; fa.t_max = m.T; fa.hop = f.hop;
   fa.row_b = m.d_row_b; fa.row_t = m.d_row_t; fa.preemph = 0.97f;
-  SK_CHECK((size_t)M * h->nbp * 4 <= ln.ws_S.bytes, SK_EWORKSPACE, "spectrum workspace too small (xt_reserve)");
   fa.mel_cw = nullptr; fa.mel_ck0 = nullptr; fa.mel_fmeta = nullptr; fa.mel_chunks = 0; fa.n_mels = 0; fa.logmel = nullptr; fa.ldl = 0;
   if (h->mel_fused) {  // power spectrum stays in LDS, the kernel writes log-mel rows
     fa.mel_cw = h->d_mel_cw; fa.mel_ck0 = h->d_mel_ck0; fa.mel_fmeta = h->d_mel_fmeta; fa.mel_chunks = h->mel_chunks; fa.n_mels = f.n_mels;
@@ -662,7 +701,7 @@ static int frontend_rows(xt_handle* h, Lane& ln, const void* d_wav, int pcm16, i
   { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_stft_power_fft(fa, st)); }
   if (!h->mel_fused) {  // 2) power x mel filterbank, log(. + 1e-6)
     GemmArgs p = gemm_args();
-    p.A = ln.ws_S.p; p.lda = h->nbp; p.a_rows = M;
+    p.A = ln.ws[WS_S].p; p.lda = h->nbp; p.a_rows = M;
     p.W = h->d_fbT; p.ldw = h->nbp; p.M = M; p.N = f.n_mels; p.K = h->nbp; p.act = ACT_LOG_EPS;
     p.C = logmel; p.ldc = f.n_mels;
     { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_gemm(p, st)); }
@@ -681,12 +720,12 @@ static int frontend_rows(xt_handle* h, Lane& ln, const void* d_wav, int pcm16, i
 
 static int tail(xt_handle* h, Lane& ln, int B, float* d_emb, float* d_logits, hipStream_t st, bool normalised = false) {
   const int E = h->cfg.emb_dim;
-  SK_TRY(tap(h, "pre_norm", ln.ws_pre.p, (size_t)B * E * 4, st));
+  SK_TRY(tap(h, "pre_norm", ln.ws[WS_PRE].p, (size_t)B * E * 4, st));
   if (!h->norm_embedding && h->cfg.loss == XT_LOSS_CCE) {  // xvector.py:893-898: cce + is_eval returns x as is
-    SK_HIP(hipMemcpyAsync(d_emb, ln.ws_pre.p, (size_t)B * E * 4, hipMemcpyDeviceToDevice, st));
+    SK_HIP(hipMemcpyAsync(d_emb, ln.ws[WS_PRE].p, (size_t)B * E * 4, hipMemcpyDeviceToDevice, st));
     return SK_OK;
   }
-  if (!normalised) SK_TRY(launch_l2norm((const float*)ln.ws_pre.p, d_emb, E, B, st));   // else: done by the embedding GEMM's slice-adding kernel
+  if (!normalised) SK_TRY(launch_l2norm((const float*)ln.ws[WS_PRE].p, d_emb, E, B, st));   // else: done by the embedding GEMM's slice-adding kernel
   if (d_logits) {
     SK_CHECK(h->head_wn != nullptr, SK_ESTATE, "logits requested but the model has no cosine head (loss='cce' returns embeddings only)");
     GemmArgs g = gemm_args();
@@ -706,8 +745,7 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
   int Hl[4];
   for (int l = 0; l < 4; ++l) Hl[l] = halve(T, l);
   const size_t act_bytes = (size_t)B * T * 80 * 32 * EB;
-  for (int i = 0; i < 4; ++i) SK_CHECK(act_bytes <= ln.ws_act[i].bytes, SK_EWORKSPACE, "activation workspace too small: call xt_reserve(%d, >= %d frames)", B, T);
-  void *X = ln.ws_act[0].p, *O1 = ln.ws_act[1].p, *O2 = ln.ws_act[2].p;
+  void *X = ln.ws[WS_ACT0].p, *O1 = ln.ws[WS_ACT1].p, *O2 = ln.ws[WS_ACT2].p;
   { ProfScope ps(h, XT_PROF_STEM, st); SK_TRY(launch_stem(feats, sb, sf, stt, h->stem_w, h->stem_shift, X, dt, m.lens, B, T, st)); }
   SK_TRY(tap(h, "stem", X, act_bytes, st));
   for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
@@ -721,14 +759,8 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
     a.lens = m.lens; a.B = B; a.zeros = h->d_zeros; a.persist_cap = ln.persist_cap;
     // conv1 + bn1 + relu -> O1, leaving the sums the block's SE gate is derived from
     a.in = X; a.wpack = b.c1.wpack; a.scale = b.c1.scale; a.shift = b.c1.shift; a.out = O1;
-    a.se_part = (float*)ln.ws_se.p; a.col_part = (float*)ln.ws_col.p; a.edge = (float*)ln.ws_edge.p;
+    a.se_part = (float*)ln.ws[WS_SE].p; a.col_part = (float*)ln.ws[WS_COL].p; a.edge = (float*)ln.ws[WS_EDGE].p;
     a.halvings_in = lin; a.Hin = Hl[lin]; a.Hout = Hl[li]; a.relu = 1;
-    {
-      const size_t tiles1 = (size_t)cdiv(Hl[li], b.c1.g.th);
-      SK_CHECK((size_t)B * tiles1 * b.c1.g.wm * b.C * 4 <= ln.ws_se.bytes && (size_t)B * tiles1 * 2 * b.C * 4 <= ln.ws_col.bytes &&
-               (size_t)B * 6 * b.C * 4 <= ln.ws_edge.bytes && (size_t)B * b.C * 4 <= ln.ws_gate.bytes, SK_EWORKSPACE,
-               "SE statistics workspace too small for %d x %d frames (xt_reserve)", B, T);
-    }
     // SE gate, known before conv2 runs (linearity of the plane mean in O1): its own launch, one workgroup per utterance.  (Round 4 built
     // the alternative the round-3 verdict asked to have measured -- conv1's last workgroup of an utterance computes the gate in its
     // tail, an agent-scope release + ticket per workgroup -- and dropped it: at batch 256 every workgroup's release made the step
@@ -736,9 +768,9 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
     // (layer 3: 161 -> 242 registers + 348 B of scratch, 6.68 ms per step); and at batch 1 the single-workgroup tail was slower than the
     // launch it replaced (0.93 vs 0.75 ms per utterance).  DESIGN.md section 5.)
     SeArgs se;
-    se.se_part = (const float*)ln.ws_se.p; se.col_part = (const float*)ln.ws_col.p; se.edge = (const float*)ln.ws_edge.p;
+    se.se_part = (const float*)ln.ws[WS_SE].p; se.col_part = (const float*)ln.ws[WS_COL].p; se.edge = (const float*)ln.ws[WS_EDGE].p;
     se.tiles = cdiv(Hl[li], b.c1.g.th); se.wm = b.c1.g.wm; se.th = b.c1.g.th; se.w2t = b.w2t; se.w2t_bf16 = h->cfg.dtype == XT_BF16; se.scale2 = b.c2.scale; se.shift2 = b.c2.shift;
-    se.fc1 = b.se_w1; se.fc2 = b.se_w2; se.gate = (float*)ln.ws_gate.p; se.lens = m.lens; se.halvings = li; se.wout = wout; se.C = b.C; se.B = B;
+    se.fc1 = b.se_w1; se.fc2 = b.se_w2; se.gate = (float*)ln.ws[WS_GATE].p; se.lens = m.lens; se.halvings = li; se.wout = wout; se.C = b.C; se.B = B;
     { ProfScope ps(h, b.c1.shape, st); SK_TRY(launch_conv(b.c1.shape, dt, a, st)); }
     { ProfScope ps(h, XT_PROF_SE_RES, st); SK_TRY(launch_se_pre(se, st)); }
     // small grids (at most SMALL_GRID_MAX_B utterances; 1 is the reference driver's call shape, sidekit/bin/extract_xvectors.py:146): a forward is a
@@ -748,7 +780,7 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
     const int c2shape = !small ? b.c2.shape : (li == 2 ? (int)CONV_L3T : (li == 3 ? (int)CONV_L4T : b.c2.shape));
     // conv2 + bn2, * gate, + shortcut, relu -> O2 (the block output)
     a.in = O1; a.wpack = b.c2.wpack; a.scale = b.c2.scale; a.shift = b.c2.shift; a.out = O2;
-    a.se_part = nullptr; a.col_part = nullptr; a.edge = nullptr; a.gate = (const float*)ln.ws_gate.p; a.shortcut = X;
+    a.se_part = nullptr; a.col_part = nullptr; a.edge = nullptr; a.gate = (const float*)ln.ws[WS_GATE].p; a.shortcut = X;
     a.halvings_in = li; a.Hin = Hl[li]; a.Hout = Hl[li]; a.relu = 0;
     if (first) {   // first block of a layer: conv2's epilogue evaluates the 1x1 shortcut conv itself from the block input (no shortcut tensor)
       a.shortcut = nullptr; a.sc_in = X; a.sc_hin = Hl[lin];
@@ -767,32 +799,32 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
   const int xbf = dt == DT_BF16;
   RowSpan rs{nullptr, H4, m.lens, 3, 0};
   ProfScope ps_pool(h, XT_PROF_POOL_TAIL, st);
-  SK_TRY(launch_mean_std(X, xbf, D, D, rs, (float*)ln.ws_ctx.p, B, st));
+  SK_TRY(launch_mean_std(X, xbf, D, D, rs, (float*)ln.ws[WS_CTX].p, B, st));
   GemmArgs c = gemm_args();  // context term of attention.0: W1[:, 2560:] . [mean | std] + bias, once per utterance
-  c.A = ln.ws_ctx.p; c.lda = 2 * D; c.a_rows = B; c.W = h->att_w1c; c.ldw = 2 * D; c.C = (float*)ln.ws_rb.p; c.ldc = 128;
-  c.M = B; c.N = 128; c.K = 2 * D; c.bias = h->att_b1; c.splitk_ws = (float*)ln.ws_splitk.p;
+  c.A = ln.ws[WS_CTX].p; c.lda = 2 * D; c.a_rows = B; c.W = h->att_w1c; c.ldw = 2 * D; c.C = (float*)ln.ws[WS_RB].p; c.ldc = 128;
+  c.M = B; c.N = 128; c.K = 2 * D; c.bias = h->att_b1; c.splitk_ws = (float*)ln.ws[WS_SPLITK].p;
   SK_TRY(launch_gemm(c, st));
   GemmArgs g1 = gemm_args();  // attention.0 on x + ReLU + BatchNorm1d + tanh
-  g1.A = X; g1.a_bf16 = xbf; g1.lda = D; g1.a_rows = R; g1.W = h->att_w1x; g1.ldw = D; g1.C = (float*)ln.ws_h.p; g1.ldc = 128;
-  g1.M = R; g1.N = 128; g1.K = D; g1.rowbias = (const float*)ln.ws_rb.p; g1.rows_per_group = H4;
+  g1.A = X; g1.a_bf16 = xbf; g1.lda = D; g1.a_rows = R; g1.W = h->att_w1x; g1.ldw = D; g1.C = (float*)ln.ws[WS_H].p; g1.ldc = 128;
+  g1.M = R; g1.N = 128; g1.K = D; g1.rowbias = (const float*)ln.ws[WS_RB].p; g1.rows_per_group = H4;
   g1.act = ACT_RELU_BN_TANH; g1.scale = h->att_bn_scale; g1.shift = h->att_bn_shift; g1.W_bf16 = h->att_w1x_bf16;
-  if (xbf && (size_t)8 * 512 * 128 * 4 <= ln.ws_splitk.bytes) g1.splitk_ws = (float*)ln.ws_splitk.p;   // bf16 path, at most 512 rows (a few utterances): K in eight slices side by side (gemm.hip)
+  if (xbf) g1.splitk_ws = (float*)ln.ws[WS_SPLITK].p;   // bf16 path, at most 512 rows (a few utterances): K in eight slices side by side (gemm.hip)
   SK_TRY(launch_gemm(g1, st));
-  SK_TRY(tap(h, "att_h", ln.ws_h.p, (size_t)R * 128 * 4, st));
+  SK_TRY(tap(h, "att_h", ln.ws[WS_H].p, (size_t)R * 128 * 4, st));
   if (xbf) {   // bf16 path: attention.4 + softmax + statistics fused, e never leaves the accumulators
-    SK_TRY(launch_att_fused(X, (const float*)ln.ws_h.p, h->att_w2_bf16, h->att_b2, D, D, rs, (float*)ln.ws_pooled.p, B, st));
+    SK_TRY(launch_att_fused(X, (const float*)ln.ws[WS_H].p, h->att_w2_bf16, h->att_b2, D, D, rs, (float*)ln.ws[WS_POOLED].p, B, st));
   } else {   // fp32 path: attention.4 as a GEMM, then softmax + statistics
     GemmArgs g2 = gemm_args();
-    g2.A = ln.ws_h.p; g2.lda = 128; g2.a_rows = R; g2.W = h->att_w2; g2.ldw = 128; g2.C = (float*)ln.ws_e.p; g2.ldc = D;
+    g2.A = ln.ws[WS_H].p; g2.lda = 128; g2.a_rows = R; g2.W = h->att_w2; g2.ldw = 128; g2.C = (float*)ln.ws[WS_E].p; g2.ldc = D;
     g2.M = R; g2.N = D; g2.K = 128; g2.bias = h->att_b2;
     SK_TRY(launch_gemm(g2, st));
-    SK_TRY(launch_att_stats((const float*)X, (const float*)ln.ws_e.p, D, D, rs, (float*)ln.ws_pooled.p, B, st));
+    SK_TRY(launch_att_stats((const float*)X, (const float*)ln.ws[WS_E].p, D, D, rs, (float*)ln.ws[WS_POOLED].p, B, st));
   }
-  SK_TRY(tap(h, "pooled", ln.ws_pooled.p, (size_t)B * 2 * D * 4, st));
+  SK_TRY(tap(h, "pooled", ln.ws[WS_POOLED].p, (size_t)B * 2 * D * 4, st));
   GemmArgs e = gemm_args();  // lin_be + bn_be (xvector.py:578-581)
-  e.A = ln.ws_pooled.p; e.lda = 2 * D; e.a_rows = B; e.W = h->emb_w; e.ldw = 2 * D; e.C = (float*)ln.ws_pre.p;
+  e.A = ln.ws[WS_POOLED].p; e.lda = 2 * D; e.a_rows = B; e.W = h->emb_w; e.ldw = 2 * D; e.C = (float*)ln.ws[WS_PRE].p;
   e.ldc = h->cfg.emb_dim; e.M = B; e.N = h->cfg.emb_dim; e.K = 2 * D; e.scale = h->emb_scale; e.shift = h->emb_shift;
-  if (h->cfg.emb_dim <= 256) e.splitk_ws = (float*)ln.ws_splitk.p;
+  if (h->cfg.emb_dim <= 256) e.splitk_ws = (float*)ln.ws[WS_SPLITK].p;
   int l2_done = 0;
   e.l2_out = d_emb; e.l2_done = &l2_done;     // the aam head always normalises (xvector.py:903)
   SK_TRY(launch_gemm(e, st));
@@ -804,11 +836,10 @@ static int tdnn_from_rows(xt_handle* h, Lane& ln, const float* rows, const Batch
   const int R = m.R;
   const float* in = rows;
   int lda = 80;
-  float* bufs[2] = {(float*)ln.ws_act[0].p, (float*)ln.ws_act[1].p};
+  float* bufs[2] = {(float*)ln.ws[WS_ACT0].p, (float*)ln.ws[WS_ACT1].p};
   for (int i = 0; i < 5; ++i) {
     const auto& L = h->tdnn[i];
     float* out = bufs[i & 1];
-    SK_CHECK((size_t)R * L.cout * 4 <= ln.ws_act[i & 1].bytes, SK_EWORKSPACE, "TDNN activation workspace too small (xt_reserve)");
     GemmArgs g = gemm_args();
     g.A = in; g.lda = lda; g.a_rows = R; g.kc = L.k > 1 ? L.cin : 0; g.dil = L.dil;
     g.W = L.w; g.ldw = (long)L.cin * L.k; g.C = out; g.ldc = L.cout; g.M = R; g.N = L.cout; g.K = L.cin * L.k;
@@ -820,12 +851,12 @@ static int tdnn_from_rows(xt_handle* h, Lane& ln, const float* rows, const Batch
   }
   ProfScope ps_pool(h, XT_PROF_POOL_TAIL, st);
   RowSpan rs{m.d_offsets, 0, m.lens, 0, 14};  // context_size()-1 = 4 + 4 + 6 frames consumed by the valid convs
-  SK_TRY(launch_mean_std(in, 0, 1536, 1536, rs, (float*)ln.ws_pooled.p, m.B, st));
-  SK_TRY(tap(h, "pooled", ln.ws_pooled.p, (size_t)m.B * 3072 * 4, st));
+  SK_TRY(launch_mean_std(in, 0, 1536, 1536, rs, (float*)ln.ws[WS_POOLED].p, m.B, st));
+  SK_TRY(tap(h, "pooled", ln.ws[WS_POOLED].p, (size_t)m.B * 3072 * 4, st));
   GemmArgs e = gemm_args();  // linear6 (xvector.py:489-491)
-  e.A = ln.ws_pooled.p; e.lda = 3072; e.a_rows = m.B; e.W = h->emb_w; e.ldw = 3072; e.C = (float*)ln.ws_pre.p; e.ldc = h->cfg.emb_dim;
+  e.A = ln.ws[WS_POOLED].p; e.lda = 3072; e.a_rows = m.B; e.W = h->emb_w; e.ldw = 3072; e.C = (float*)ln.ws[WS_PRE].p; e.ldc = h->cfg.emb_dim;
   e.M = m.B; e.N = h->cfg.emb_dim; e.K = 3072; e.bias = h->emb_bias;
-  if (h->cfg.emb_dim <= 256) e.splitk_ws = (float*)ln.ws_splitk.p;
+  if (h->cfg.emb_dim <= 256) e.splitk_ws = (float*)ln.ws[WS_SPLITK].p;
   int l2_done = 0;
   if (h->norm_embedding || h->cfg.loss != XT_LOSS_CCE) { e.l2_out = d_emb; e.l2_done = &l2_done; }
   SK_TRY(launch_gemm(e, st));
@@ -916,9 +947,7 @@ int xt_destroy(xt_handle* h) {
   if (!h) return SK_OK;
   for (void* p : h->dev_allocs) (void)hipFree(p);
   for (Lane& ln : h->lane) {
-    DevBuf* bufs[] = {&ln.ws_S, &ln.ws_feat, &ln.ws_act[0], &ln.ws_act[1], &ln.ws_act[2], &ln.ws_act[3], &ln.ws_se, &ln.ws_col, &ln.ws_edge, &ln.ws_splitk, &ln.ws_gate,
-                      &ln.ws_ctx, &ln.ws_rb, &ln.ws_h, &ln.ws_e, &ln.ws_pooled, &ln.ws_pre, &ln.ws_int};
-    for (DevBuf* b : bufs) b->release();
+    for (DevBuf& b : ln.ws) b.release();
     for (int i = 0; i < Lane::RING; ++i)
       if (ln.ring_host[i]) { (void)hipHostFree(ln.ring_host[i]); (void)hipEventDestroy(ln.ring_ev[i]); }
     if (ln.stream) (void)hipStreamDestroy(ln.stream);
@@ -982,16 +1011,67 @@ static int create_lane_stream(Lane& lk) {
   return SK_OK;
 }
 
-static int reserve_lane(xt_handle* h, Lane& ln, int32_t max_batch, int64_t max_samples) {
+// Every workspace buffer's bytes for a batch of B utterances of at most T frames.  Each grows with B and T, so a lane sized for a shape
+// holds every batch that shape covers.
+static WsPlan ws_plan(const xt_handle* h, size_t B, size_t T) {
   const FrontCfg& f = h->fc;
-  const size_t B = (size_t)max_batch;
-  const size_t T = 1 + (size_t)(max_samples / f.hop);
   const size_t nbp = (size_t)((f.n_fft / 2 + 1 + 3) / 4 * 4);
-  const size_t R = B * T;
-  SK_TRY(ln.ws_S.ensure(R * nbp * 4));
-  SK_TRY(ln.ws_feat.ensure(R * f.n_out * 4));
-  const size_t int_bytes = (4 * B + 2 * R + 16) * 4;
-  SK_TRY(ln.ws_int.ensure(int_bytes));
+  const size_t R = B * T, E = (size_t)h->cfg.emb_dim;
+  WsPlan p;
+  size_t* n = p.bytes;
+  n[WS_S] = R * nbp * 4;
+  n[WS_FEAT] = R * f.n_out * 4;
+  n[WS_INT] = (4 * B + 2 * R + 16) * 4;
+  n[WS_PRE] = B * E * 4;
+  {  // split-K partials of the skinny GEMMs (N <= 256), [slices][rows <= 512][N]: the embedding / context GEMMs; attention.0 below 512 rows
+    const size_t skinny = (size_t)32 * (B < 512 ? B : 512) * 256 * 4, att0 = (size_t)8 * 512 * 128 * 4;
+    n[WS_SPLITK] = skinny > att0 ? skinny : att0;
+  }
+  if (h->cfg.arch == XT_ARCH_HALFRESNET34) {
+    const size_t EB = h->cfg.dtype == XT_BF16 ? 2 : 4;
+    for (int i = 0; i < 4; ++i) n[WS_ACT0 + i] = R * 80 * 32 * EB;
+    // SE statistics of the statistics-form convolutions: [B][row tiles][wave rows][C] totals and [B][row tiles][2][C] column
+    // sums, sized from the largest first convolution of a block (short utterances: one 2-KB tile of layer 4 per utterance
+    // outgrows a per-frame estimate)
+    for (const Block& b : h->blocks) {
+      const size_t tiles = (size_t)cdiv(halve((int)T, b.li), b.c1.g.th);
+      const size_t s1 = B * tiles * b.c1.g.wm * b.C * 4, s2 = B * tiles * 2 * b.C * 4;
+      n[WS_SE] = s1 > n[WS_SE] ? s1 : n[WS_SE];
+      n[WS_COL] = s2 > n[WS_COL] ? s2 : n[WS_COL];
+    }
+    n[WS_EDGE] = B * 6 * 256 * 4;
+    n[WS_GATE] = B * 256 * 4;
+    const size_t H4 = (size_t)halve((int)T, 3);
+    n[WS_CTX] = B * 5120 * 4;
+    n[WS_RB] = B * 128 * 4;
+    n[WS_H] = B * H4 * 128 * 4;
+    n[WS_E] = B * H4 * 2560 * 4;
+    n[WS_POOLED] = B * 5120 * 4;
+  } else {
+    n[WS_ACT0] = R * 1536 * 4;
+    n[WS_ACT1] = R * 512 * 4;
+    n[WS_ACT3] = R * f.n_mels * 4;
+    n[WS_POOLED] = B * 3072 * 4;
+  }
+  return p;
+}
+
+static int64_t frames_of(const xt_handle* h, int64_t samples) { return 1 + samples / h->fc.hop; }
+
+// A lane call's one workspace check, before anything is enqueued: every buffer against the plan of the batch it is about to run.
+static int check_workspace(const xt_handle* h, const Lane& ln, int B, int64_t T) {
+  const WsPlan p = ws_plan(h, (size_t)B, (size_t)T);
+  for (int i = 0; i < WS_COUNT; ++i)
+    SK_CHECK(p.bytes[i] <= ln.ws[i].bytes, SK_EWORKSPACE, "%s workspace too small for %d x %lld frames (xt_reserve)", WS_NAMES[i], B,
+             (long long)T);
+  return SK_OK;
+}
+
+// Sizes a lane for a (batch, samples) shape and records the shape.
+static int reserve_lane(xt_handle* h, Lane& ln, int32_t max_batch, int64_t max_samples) {
+  const WsPlan p = ws_plan(h, (size_t)max_batch, (size_t)frames_of(h, max_samples));
+  for (int i = 0; i < WS_COUNT; ++i) SK_TRY(ln.ws[i].ensure(p.bytes[i]));
+  const size_t int_bytes = p.bytes[WS_INT];
   if (int_bytes > ln.ring_bytes) {
     for (int i = 0; i < Lane::RING; ++i) {
       if (ln.ring_host[i]) { if (ln.ring_used[i]) SK_HIP(hipEventSynchronize(ln.ring_ev[i])); SK_HIP(hipHostFree(ln.ring_host[i])); }
@@ -1001,48 +1081,14 @@ static int reserve_lane(xt_handle* h, Lane& ln, int32_t max_batch, int64_t max_s
     }
     ln.ring_bytes = int_bytes;
   }
-  const size_t E = (size_t)h->cfg.emb_dim;
-  SK_TRY(ln.ws_pre.ensure(B * E * 4));
-  {
-    const size_t skinny = (size_t)32 * (B < 512 ? B : 512) * 256 * 4, att0 = (size_t)8 * 512 * 128 * 4;   // [slices][rows <= 512][N]: the embedding / context GEMMs; attention.0 below 512 rows
-    SK_TRY(ln.ws_splitk.ensure(skinny > att0 ? skinny : att0));
-  }  // split-K partials of the skinny GEMMs (N <= 256)
-  if (h->cfg.arch == XT_ARCH_HALFRESNET34) {
-    const size_t EB = h->cfg.dtype == XT_BF16 ? 2 : 4;
-    for (int i = 0; i < 4; ++i) SK_TRY(ln.ws_act[i].ensure(R * 80 * 32 * EB));
-    // SE statistics of the statistics-form convolutions: [B][row tiles][wave rows][C] totals and [B][row tiles][2][C] column
-    // sums, sized from the largest first convolution of a block (short utterances: one 2-KB tile of layer 4 per utterance
-    // outgrows a per-frame estimate)
-    size_t se_b = 0, col_b = 0;
-    for (const Block& b : h->blocks) {
-      const size_t tiles = (size_t)cdiv(halve((int)T, b.li), b.c1.g.th);
-      const size_t s1 = B * tiles * b.c1.g.wm * b.C * 4, s2 = B * tiles * 2 * b.C * 4;
-      se_b = s1 > se_b ? s1 : se_b;
-      col_b = s2 > col_b ? s2 : col_b;
-    }
-    SK_TRY(ln.ws_se.ensure(se_b));
-    SK_TRY(ln.ws_col.ensure(col_b));
-    SK_TRY(ln.ws_edge.ensure(B * 6 * 256 * 4));
-    SK_TRY(ln.ws_gate.ensure(B * 256 * 4));
-    const size_t H4 = (size_t)halve((int)T, 3);
-    SK_TRY(ln.ws_ctx.ensure(B * 5120 * 4));
-    SK_TRY(ln.ws_rb.ensure(B * 128 * 4));
-    SK_TRY(ln.ws_h.ensure(B * H4 * 128 * 4));
-    SK_TRY(ln.ws_e.ensure(B * H4 * 2560 * 4));
-    SK_TRY(ln.ws_pooled.ensure(B * 5120 * 4));
-  } else {
-    SK_TRY(ln.ws_act[0].ensure(R * 1536 * 4));
-    SK_TRY(ln.ws_act[1].ensure(R * 512 * 4));
-    SK_TRY(ln.ws_act[3].ensure(R * f.n_mels * 4));
-    SK_TRY(ln.ws_pooled.ensure(B * 3072 * 4));
-  }
+  if (!ln.covers(max_batch, max_samples)) ln.reserved.push_back({max_batch, max_samples});
   return SK_OK;
 }
 
 // lanes 1 .. n-1 take the later parts of a split batch (part k of n': rows [k B / n', (k + 1) B / n')).  A batch SMALLER than the
 // reserved one is split into FEWER, larger parts (lanes = 4, reserve 256: B = 255 gives three parts of 85), so lane k is sized for the
 // largest part it can ever be handed by a batch this shape covers: it runs only when n' >= k + 1, i.e. at most ceil(max_batch / (k + 1))
-// utterances (sizing it for ceil(max_batch / n) let the STFT kernel write past ws_feat on a final partial batch).
+// utterances (sizing it for ceil(max_batch / n) let the STFT kernel write past the feature buffer on a final partial batch).
 static int reserve_side_lanes(xt_handle* h, int32_t max_batch, int64_t max_samples) {
   if (h->cfg.arch != XT_ARCH_HALFRESNET34) return SK_OK;
   const int n = lane_parts(h->lanes, max_batch, xt_handle::LANE_MIN);
@@ -1054,16 +1100,13 @@ static int reserve_side_lanes(xt_handle* h, int32_t max_batch, int64_t max_sampl
       // GPU_MAX_HW_QUEUES (4) hardware queues, least-referenced first, and two streams on one queue run one after the other.  In a
       // plain process the second stream created gets its own queue; in a process that has initialised RCCL (torch's pool of 32
       // normal-priority streams exists) a normal-priority lane stream landed on the caller's queue and the two-lane forward was
-      // SLOWER than the serial one (round 4, one rank under torch.distributed.run: 6.41-6.60 vs 5.93-6.08 ms,
-      // scripts/rccl_step_probe.py).  Queues are pooled per priority, so lanes of another priority get queues of their own; and
-      // they must all have the SAME priority: one high-priority lane beside the caller's normal stream ran ahead of it instead of
-      // beside it and the overlap was gone (5.92 vs 5.73 ms).  So: the lowest priority (create_lane_stream).
+      // SLOWER than the serial one (one rank under torch.distributed.run: 6.41-6.60 vs 5.93-6.08 ms, scripts/rccl_step_probe.py).
+      // Queues are pooled per priority, so lanes of another priority get queues of their own; and they must all have the SAME
+      // priority: one high-priority lane beside the caller's normal stream ran ahead of it instead of beside it and the overlap was
+      // gone (5.92 vs 5.73 ms).  So: the lowest priority (create_lane_stream).
       SK_TRY(create_lane_stream(lk));
     }
-    if (k == 0) continue;   // lane 0's workspace is the handle's full-size one
-    const int part = (max_batch + k) / (k + 1);
-    SK_TRY(reserve_lane(h, lk, part, max_samples));
-    if (!lk.covers(part, max_samples)) lk.reserved.push_back({part, max_samples});
+    if (k > 0) SK_TRY(reserve_lane(h, lk, (max_batch + k) / (k + 1), max_samples));   // lane 0's workspace is the handle's full-size one
   }
   return SK_OK;
 }
@@ -1072,110 +1115,73 @@ static int reserve_impl(xt_handle* h, int32_t max_batch, int64_t max_samples) {
   SK_CHECK(h && max_batch > 0 && max_samples > 0, SK_EARG, "xt_reserve: bad arguments");
   SK_HIP(hipSetDevice(h->device));
   SK_TRY(reserve_lane(h, h->lane[0], max_batch, max_samples));
-  SK_TRY(reserve_side_lanes(h, max_batch, max_samples));
-  bool covered = false;
-  for (auto& r : h->reserved) covered = covered || (r.first >= max_batch && r.second >= max_samples);
-  if (!covered) h->reserved.push_back({max_batch, max_samples});
-  return SK_OK;
+  return reserve_side_lanes(h, max_batch, max_samples);
 }
 
 int xt_reserve(xt_handle* h, int32_t max_batch, int64_t max_samples) {
-  SK_ENTER(h);
+  Entry e(h);
+  SK_TRY(e.lock());
   return reserve_impl(h, max_batch, max_samples);
-}
-
-static int check_run(xt_handle* h, int B, int64_t L_samples) {
-  SK_CHECK(h, SK_EARG, "null handle");
-  SK_CHECK(h->finalized, SK_ESTATE, "forward before xt_finalize (load_state_dict)");
-  SK_CHECK(B > 0, SK_EARG, "empty batch");
-  SK_CHECK(!h->reserved.empty(), SK_ESTATE, "forward before xt_reserve");
-  bool covered = false;
-  for (auto& r : h->reserved) covered = covered || (r.first >= B && r.second >= L_samples);
-  SK_CHECK(covered, SK_EWORKSPACE, "batch of %d x %lld samples exceeds every reserved workspace shape: call xt_reserve(%d, %lld)", B,
-           (long long)L_samples, B, (long long)L_samples);
-  SK_HIP(hipSetDevice(h->device));
-  return SK_OK;
 }
 
 // One lane's forward in two halves: front-end (wav -> CMVN'ed features in the lane's workspace) and trunk + pooling + tail.
 static int lane_frontend(xt_handle* h, Lane& ln, const void* d_wav, int pcm16, int64_t wav_ld, const int32_t* h_nsamples, int32_t B, int64_t L,
                          BatchMeta& m, hipStream_t st) {
   SK_TRY(make_meta(h, ln, h_nsamples, B, L, true, m, st));
-  float* feat = (float*)ln.ws_feat.p;
-  const int M = m.R ? m.R : m.B * m.T;
-  SK_CHECK((size_t)M * h->fc.n_out * 4 <= ln.ws_feat.bytes, SK_EWORKSPACE, "feature workspace too small for %d x %d frames (xt_reserve)", m.B, m.T);
+  float* feat = (float*)ln.ws[WS_FEAT].p;
   SK_TRY(frontend_rows(h, ln, d_wav, pcm16, wav_ld, m, feat, st));
-  return tap(h, "feats", feat, (size_t)M * h->fc.n_out * 4, st);
+  return tap(h, "feats", feat, (size_t)(m.R ? m.R : m.B * m.T) * h->fc.n_out * 4, st);
 }
 
 static int lane_trunk(xt_handle* h, Lane& ln, const BatchMeta& m, float* d_emb, float* d_logits, hipStream_t st) {
-  float* feat = (float*)ln.ws_feat.p;
+  float* feat = (float*)ln.ws[WS_FEAT].p;
   if (h->cfg.arch == XT_ARCH_HALFRESNET34) return half_from_feats(h, ln, feat, (long)m.T * 80, 1, 80, m, d_emb, d_logits, st);
   return tdnn_from_rows(h, ln, feat, m, d_emb, d_logits, st);
 }
 
 static int forward_wav(xt_handle* h, const void* d_wav, int pcm16, int64_t wav_ld, const int32_t* h_nsamples, int32_t B, int64_t L,
                        float* d_emb, float* d_logits, void* stream) {
-  SK_ENTER(h);
-  SK_TRY(check_run(h, B, L));
+  Entry e(h, stream);
+  SK_TRY(e.run(B, L));
   SK_CHECK(d_wav && d_emb && wav_ld >= L, SK_EARG, "xt_forward: bad buffers");
-  hipStream_t st = (hipStream_t)stream;
-  SK_TRY(enter_stream(h, st));
-  StreamScope scope_(h, st);
-  Lane& l0 = h->lane[0];
-  int n = (h->debug || h->cfg.arch != XT_ARCH_HALFRESNET34) ? 1 : lane_parts(h->lanes, B, xt_handle::LANE_MIN);
-  // fewer parts until every side lane exists (a handle switched after its last reserve) and its workspace covers its part: nothing
-  // is enqueued before every part is known to fit
-  auto parts_fit = [&](int np) {
-    if (!h->lane[0].stream) return false;
-    for (int k = 1; k < np; ++k) {
-      const int r0 = (int)((long)k * B / np), r1 = (int)((long)(k + 1) * B / np);
-      if (!h->lane[k].stream || !h->lane[k].covers(r1 - r0, L)) return false;
-    }
+  // n parts: part k = rows [k B / n, (k + 1) B / n) in lane k.  Fewer parts until every lane exists (a handle switched after its last
+  // reserve) and its workspace covers its part: nothing is enqueued before every part is known to fit
+  auto r0 = [&](int k, int n) { return (int)((long)k * B / n); };
+  auto parts_fit = [&](int n) {
+    for (int k = 0; k < n; ++k)
+      if (!h->lane[k].stream || !h->lane[k].covers(r0(k + 1, n) - r0(k, n), L)) return false;
     return true;
   };
+  int n = (h->debug || h->cfg.arch != XT_ARCH_HALFRESNET34) ? 1 : lane_parts(h->lanes, B, xt_handle::LANE_MIN);
   while (n > 1 && !parts_fit(n)) --n;
-  BatchMeta m0;
+  for (int k = 0; k < n; ++k) SK_TRY(check_workspace(h, h->lane[k], r0(k + 1, n) - r0(k, n), frames_of(h, L)));
+  // an unsplit forward runs on the CALLER's stream in lane 0's workspace, behind what lane 0's own stream still runs (Entry::order)
+  SK_TRY(e.order(n == 1));
   for (int k = 0; k < xt_handle::MAX_LANES; ++k) h->lane[k].persist_cap = 0;
   if (n == 1) {
-    // an unsplit forward runs on the CALLER's stream in lane 0's workspace: a pipelined batch (xt_forward_begin, slot 0) may still be running there on
-    // lane 0's own stream -- order behind it (found by scripts/soak_pipelined.py: a small plain forward between two submits raced with slot 0)
-    if (l0.stream) SK_HIP(hipStreamWaitEvent(st, l0.join, 0));
-    SK_TRY(lane_frontend(h, l0, d_wav, pcm16, wav_ld, h_nsamples, B, L, m0, st));
-    return lane_trunk(h, l0, m0, d_emb, d_logits, st);
+    BatchMeta m0;
+    SK_TRY(lane_frontend(h, h->lane[0], d_wav, pcm16, wav_ld, h_nsamples, B, L, m0, e.st));
+    return lane_trunk(h, h->lane[0], m0, d_emb, d_logits, e.st);
   }
-  // n lanes: part k = rows [k B / n, (k + 1) B / n), every part on a stream the handle owns (reserve_side_lanes says why part 0 too).
-  // A lane starts behind everything queued on the caller's stream so far (its input may still be in flight) and the caller's stream
-  // continues only once every part is done.  Round 3 found the first version of this giving a few wrong spectrum bins per batch in
-  // the second lane: the STFT kernel's SLP-formed packed-f32 instructions (v_pk_add_f32 / v_pk_mul_f32 with op_sel / neg modifiers)
-  // misbehave on MI355X beside another stream's dense bf16 MFMAs.  The library is built without them now (csrc/Makefile; DESIGN 6;
-  // tests/test_isa_guard.py keeps them out) and tests/test_gpu_fullsize.py repeats the split forward against the serial one.
+  // every part on a stream the handle owns (reserve_side_lanes says why part 0 too).  A lane starts behind everything queued on the
+  // caller's stream so far (its input may still be in flight) and the caller's stream continues only once every part is done.  The
+  // first version of this gave a few wrong spectrum bins per batch in the second lane: the STFT kernel's SLP-formed packed-f32
+  // instructions (v_pk_add_f32 / v_pk_mul_f32 with op_sel / neg modifiers) misbehave on MI355X beside another stream's dense bf16
+  // MFMAs.  The library is built without them (csrc/Makefile; tests/test_isa_guard.py keeps them out) and
+  // tests/test_gpu_fullsize.py repeats the split forward against the serial one.
   const size_t eb = pcm16 ? 2 : 4;
-  SK_HIP(hipEventRecord(h->lane[0].fork, st));
+  SK_HIP(hipEventRecord(h->lane[0].fork, e.st));
   for (int k = 0; k < n; ++k) SK_HIP(hipStreamWaitEvent(h->lane[k].stream, h->lane[0].fork, 0));
-  // An error in one part must not leave the others running unjoined: the caller's stream would no longer order behind the side
-  // streams (which keep writing d_emb / d_logits) and the next call would reuse their workspaces.  So every lane that was forked
-  // is joined whatever happened, and the first error is what the call returns.
   int rc = SK_OK;
-  char first_err[sizeof(g_err)] = "";
   for (int k = 0; k < n && rc == SK_OK; ++k) {
     Lane& lk = h->lane[k];
-    const int r0 = (int)((long)k * B / n), r1 = (int)((long)(k + 1) * B / n);
-    hipStream_t sk_ = lk.stream;
+    const int a = r0(k, n);
     BatchMeta mk;
-    rc = lane_frontend(h, lk, (const unsigned char*)d_wav + (size_t)r0 * wav_ld * eb, pcm16, wav_ld, h_nsamples ? h_nsamples + r0 : nullptr, r1 - r0, L, mk, sk_);
-    if (rc == SK_OK) rc = lane_trunk(h, lk, mk, d_emb + (size_t)r0 * h->cfg.emb_dim, d_logits ? d_logits + (size_t)r0 * h->cfg.n_spk : nullptr, sk_);
-    if (rc != SK_OK) snprintf(first_err, sizeof(first_err), "%s", g_err);
+    rc = lane_frontend(h, lk, (const unsigned char*)d_wav + (size_t)a * wav_ld * eb, pcm16, wav_ld, h_nsamples ? h_nsamples + a : nullptr,
+                       r0(k + 1, n) - a, L, mk, lk.stream);
+    if (rc == SK_OK) rc = lane_trunk(h, lk, mk, d_emb + (size_t)a * h->cfg.emb_dim, d_logits ? d_logits + (size_t)a * h->cfg.n_spk : nullptr, lk.stream);
   }
-  for (int k = 0; k < n; ++k) {
-    const bool joined = hipEventRecord(h->lane[k].join, h->lane[k].stream) == hipSuccess && hipStreamWaitEvent(st, h->lane[k].join, 0) == hipSuccess;
-    if (!joined) {   // last resort: drain the side stream on the host
-      (void)hipStreamSynchronize(h->lane[k].stream);
-      if (rc == SK_OK) { rc = SK_EHIP; snprintf(first_err, sizeof(first_err), "xt_forward: joining lane %d failed", k); }
-    }
-  }
-  if (rc != SK_OK) set_error("%s", first_err);
-  return rc;
+  return join_lanes(h, 0, n, e.st, true, rc);
 }
 
 int xt_forward(xt_handle* h, const float* d_wav, int64_t wav_ld, const int32_t* h_nsamples, int32_t B, int64_t L, float* d_emb,
@@ -1188,102 +1194,90 @@ int xt_forward_pcm16(xt_handle* h, const int16_t* d_pcm, int64_t pcm_ld, const i
   return forward_wav(h, d_pcm, 1, pcm_ld, h_nsamples, B, L, d_emb, d_logits, stream);
 }
 
-// ---- pipelined forwards (round 4) -----------------------------------------------------------------------------------------------
-// Two WHOLE batches in flight on two streams the handle owns beat two half batches side by side (5.67 vs 5.87 ms per batch of 256 in one bench.py run, profiles/r05_bench_line.json; first measured by
-// scripts/alt_streams.py): consecutive forwards run half a step apart, so one batch's HBM-bound layer 1 overlaps the other's
-// MFMA-bound layers 3-4 -- and nothing joins at the end of a call.  A slot is a full-size workspace + a stream; xt_forward_begin queues
-// the whole (serial) forward of a batch on its slot's stream behind everything queued on the caller's stream so far and returns;
-// xt_forward_end makes a stream wait for that forward.  A caller keeps `slots` batches in flight: begin(k), end(k - slots + 1), ...
-static int reserve_slot(xt_handle* h, int slot, int32_t max_batch, int64_t max_samples) {
-  Lane& lk = h->lane[slot];
-  if (!lk.stream) SK_TRY(create_lane_stream(lk));
-  SK_TRY(reserve_lane(h, lk, max_batch, max_samples));
-  if (slot > 0 && !lk.covers(max_batch, max_samples)) lk.reserved.push_back({max_batch, max_samples});
-  return SK_OK;
-}
-
+// ---- pipelined forwards ---------------------------------------------------------------------------------------------------------
+// Two WHOLE batches in flight on two streams the handle owns beat two half batches side by side (5.67 vs 5.87 ms per batch of 256 in one
+// bench.py run, profiles/r05_bench_line.json): consecutive forwards run half a step apart, so one batch's HBM-bound layer 1 overlaps the
+// other's MFMA-bound layers 3-4 -- and nothing joins at the end of a call.  A slot is a full-size lane: workspace + stream.
+// xt_forward_begin queues the whole (serial) forward of a batch on its slot's stream behind everything queued on the caller's stream so
+// far and returns; xt_forward_end makes a stream wait for that forward.  A caller keeps `slots` batches in flight: begin(k),
+// end(k - slots + 1), ...
 int xt_reserve_slots(xt_handle* h, int32_t slots, int32_t max_batch, int64_t max_samples) {
   SK_CHECK(h && slots >= 1 && slots <= xt_handle::MAX_LANES && max_batch > 0 && max_samples > 0, SK_EARG, "xt_reserve_slots: 1 .. %d slots", xt_handle::MAX_LANES);
-  SK_ENTER(h);
-  SK_HIP(hipSetDevice(h->device));
-  SK_TRY(reserve_impl(h, max_batch, max_samples));          // slot 0 = the handle's full-size workspace; records the shape
-  for (int k = 0; k < slots; ++k) SK_TRY(reserve_slot(h, k, max_batch, max_samples));
+  Entry e(h);
+  SK_TRY(e.lock());
+  SK_TRY(reserve_impl(h, max_batch, max_samples));          // slot 0 is lane 0
+  for (int k = 0; k < slots; ++k) {
+    if (!h->lane[k].stream) SK_TRY(create_lane_stream(h->lane[k]));
+    SK_TRY(reserve_lane(h, h->lane[k], max_batch, max_samples));
+  }
   return SK_OK;
 }
 
 int xt_forward_begin(xt_handle* h, int32_t slot, const void* d_wav, int32_t in_dtype, int64_t wav_ld, const int32_t* h_nsamples, int32_t B, int64_t L,
                      float* d_emb, float* d_logits, void* stream) {
-  SK_ENTER(h);
-  SK_TRY(check_run(h, B, L));
-  SK_CHECK(slot >= 0 && slot < xt_handle::MAX_LANES && h->lane[slot].stream && (slot == 0 || h->lane[slot].covers(B, L)), SK_EWORKSPACE,
+  Entry e(h, stream);
+  SK_TRY(e.run(B, L));
+  SK_CHECK(slot >= 0 && slot < xt_handle::MAX_LANES && h->lane[slot].stream && h->lane[slot].covers(B, L), SK_EWORKSPACE,
            "xt_forward_begin: slot %d has no workspace for %d x %lld samples (xt_reserve_slots)", slot, B, (long long)L);
   SK_CHECK(d_wav && d_emb && wav_ld >= L && (in_dtype == XT_F32 || in_dtype == XT_I16), SK_EARG, "xt_forward_begin: bad buffers");
   SK_CHECK(!h->debug, SK_ESTATE, "xt_forward_begin: debug taps belong to the plain forward");
   Lane& lk = h->lane[slot];
-  SK_TRY(enter_stream(h, (hipStream_t)stream));
-  StreamScope scope_(h, (hipStream_t)stream);
-  SK_HIP(hipEventRecord(lk.fork, (hipStream_t)stream));
+  SK_TRY(check_workspace(h, lk, B, frames_of(h, L)));
+  SK_TRY(e.order(false));
+  SK_HIP(hipEventRecord(lk.fork, e.st));
   SK_HIP(hipStreamWaitEvent(lk.stream, lk.fork, 0));
   lk.persist_cap = 1;   // one persistent workgroup per CU: room for the other batch in flight (launch_cfg)
   BatchMeta m;
   int rc = lane_frontend(h, lk, d_wav, in_dtype == XT_I16 ? 1 : 0, wav_ld, h_nsamples, B, L, m, lk.stream);
   if (rc == SK_OK) rc = lane_trunk(h, lk, m, d_emb, d_logits, lk.stream);
-  char err[sizeof(g_err)];
-  snprintf(err, sizeof(err), "%s", g_err);
-  const bool recorded = hipEventRecord(lk.join, lk.stream) == hipSuccess;   // also after an error: xt_forward_end then orders behind whatever was queued
-  if (!recorded) (void)hipStreamSynchronize(lk.stream);
-  if (rc != SK_OK) set_error("%s", err);
-  return rc;
+  return join_lanes(h, slot, slot + 1, e.st, false, rc);   // xt_forward_end waits for the join
 }
 
 int xt_forward_end(xt_handle* h, int32_t slot, void* stream) {
-  SK_ENTER(h);
-  SK_CHECK(h && slot >= 0 && slot < xt_handle::MAX_LANES && h->lane[slot].stream, SK_EARG, "xt_forward_end: slot %d was never reserved", slot);
+  Entry e(h);
+  SK_TRY(e.lock());
+  SK_CHECK(slot >= 0 && slot < xt_handle::MAX_LANES && h->lane[slot].stream, SK_EARG, "xt_forward_end: slot %d was never reserved", slot);
   SK_HIP(hipStreamWaitEvent((hipStream_t)stream, h->lane[slot].join, 0));
   return SK_OK;
 }
 
 int xt_forward_features(xt_handle* h, const float* d_feats, const int32_t* h_frames, int32_t B, int32_t T, float* d_emb,
                         float* d_logits, void* stream) {
-  SK_ENTER(h);
-  SK_TRY(check_run(h, B, (int64_t)(T > 0 ? T - 1 : 0) * (h ? h->fc.hop : 1)));
+  Entry e(h, stream);
+  SK_TRY(e.run(B, (int64_t)(T > 0 ? T - 1 : 0) * (h ? h->fc.hop : 1)));
   SK_CHECK(d_feats && d_emb && T > 0, SK_EARG, "xt_forward_features: bad buffers");
-  hipStream_t st = (hipStream_t)stream;
-  SK_TRY(enter_stream(h, st));
-  StreamScope scope_(h, st);
-  BatchMeta m;
   Lane& ln = h->lane[0];
+  SK_TRY(check_workspace(h, ln, B, T));
+  SK_TRY(e.order(true));
   ln.persist_cap = 0;
-  if (ln.stream) SK_HIP(hipStreamWaitEvent(st, ln.join, 0));   // lane 0's workspace: behind whatever its own stream still runs (forward_wav)
-  SK_TRY(make_meta(h, ln, h_frames, B, T, false, m, st));
+  BatchMeta m;
+  SK_TRY(make_meta(h, ln, h_frames, B, T, false, m, e.st));
   if (h->cfg.arch == XT_ARCH_HALFRESNET34) {
     m.T = T;  // rows are addressed through the caller's (B, 80, T) strides
-    return half_from_feats(h, ln, d_feats, (long)80 * T, T, 1, m, d_emb, d_logits, st);
+    return half_from_feats(h, ln, d_feats, (long)80 * T, T, 1, m, d_emb, d_logits, e.st);
   }
-  float* rows = (float*)ln.ws_feat.p;
+  float* rows = (float*)ln.ws[WS_FEAT].p;
   RowSpan rs{m.d_offsets, 0, m.lens, 0, 0};
-  hipLaunchKernelGGL(bft_to_rows_kernel, dim3(B), dim3(256), 0, st, d_feats, rows, 80, T, rs);
+  hipLaunchKernelGGL(bft_to_rows_kernel, dim3(B), dim3(256), 0, e.st, d_feats, rows, 80, T, rs);
   SK_HIP(hipGetLastError());
-  return tdnn_from_rows(h, ln, rows, m, d_emb, d_logits, st);
+  return tdnn_from_rows(h, ln, rows, m, d_emb, d_logits, e.st);
 }
 
 int xt_features(xt_handle* h, const float* d_wav, int64_t wav_ld, const int32_t* h_nsamples, int32_t B, int64_t L,
                 float* d_feats_out, void* stream) {
-  SK_ENTER(h);
-  SK_TRY(check_run(h, B, L));
+  Entry e(h, stream);
+  SK_TRY(e.run(B, L));
   SK_CHECK(d_wav && d_feats_out && wav_ld >= L, SK_EARG, "xt_features: bad buffers");
-  hipStream_t st = (hipStream_t)stream;
-  SK_TRY(enter_stream(h, st));
-  StreamScope scope_(h, st);
-  BatchMeta m;
   Lane& ln = h->lane[0];
-  if (ln.stream) SK_HIP(hipStreamWaitEvent(st, ln.join, 0));   // lane 0's workspace: behind whatever its own stream still runs (forward_wav)
-  SK_TRY(make_meta(h, ln, h_nsamples, B, L, true, m, st));
-  float* feat = (float*)ln.ws_feat.p;
-  SK_TRY(frontend_rows(h, ln, d_wav, 0, wav_ld, m, feat, st));
-  const int T = 1 + (int)(L / h->fc.hop);
+  const int T = (int)frames_of(h, L);
+  SK_TRY(check_workspace(h, ln, B, T));
+  SK_TRY(e.order(true));
+  BatchMeta m;
+  SK_TRY(make_meta(h, ln, h_nsamples, B, L, true, m, e.st));
+  float* feat = (float*)ln.ws[WS_FEAT].p;
+  SK_TRY(frontend_rows(h, ln, d_wav, 0, wav_ld, m, feat, e.st));
   RowSpan rs{m.d_offsets, m.T, m.lens, 0, 0};
-  hipLaunchKernelGGL(rows_to_bft_kernel, dim3(B), dim3(256), 0, st, feat, d_feats_out, h->fc.n_out, T, rs);
+  hipLaunchKernelGGL(rows_to_bft_kernel, dim3(B), dim3(256), 0, e.st, feat, d_feats_out, h->fc.n_out, T, rs);
   SK_HIP(hipGetLastError());
   return SK_OK;
 }
@@ -1296,11 +1290,13 @@ int xt_set_norm_embedding(xt_handle* h, int32_t on) {
 
 int xt_set_lanes(xt_handle* h, int32_t lanes) {
   SK_CHECK(h && lanes >= 1 && lanes <= xt_handle::MAX_LANES, SK_EARG, "xt_set_lanes: 1 (serial) .. %d", xt_handle::MAX_LANES);
-  SK_ENTER(h);
+  Entry e(h);
+  SK_TRY(e.lock());
   h->lanes = lanes;
-  if (lanes > 1) {   // size the second lane for every shape reserved while the handle was serial
+  if (lanes > 1) {   // size the side lanes for every shape lane 0 was reserved for while the handle was serial
     SK_HIP(hipSetDevice(h->device));
-    for (auto& r : h->reserved) SK_TRY(reserve_side_lanes(h, r.first, r.second));
+    const auto shapes = h->lane[0].reserved;
+    for (auto& r : shapes) SK_TRY(reserve_side_lanes(h, r.first, r.second));
   }
   return SK_OK;
 }

@@ -25,6 +25,10 @@ def _ptr(arr):
     return None if arr is None else arr.ctypes.data
 
 
+def _dptr(t):
+    return None if t is None else t.data_ptr()
+
+
 class _Params(SimpleNamespace):
     """Attribute view on a group of checkpoint tensors (e.g. ``model.after_speaker_embedding.weight``)."""
 
@@ -65,9 +69,8 @@ class Xtractor:
         self.device = torch.device("cpu")
         self.training = True
         self.compute_dtype = None  # None: follow torch autocast (reduced precision -> bf16 trunk), 'fp32' or 'bf16'
-        self._handles = {}
-        self._reserved = {}
-        self._slot_shapes, self._tickets, self._next_slot = {}, [], 0     # pipelined forwards (submit / collect)
+        self._handles, self._reserved = {}, {}     # per dtype key: the library handle / {reserved (batch, samples): slots sized for it} (_reserve)
+        self._tickets, self._next_slot = [], 0     # pipelined forwards (submit / collect)
         self._refresh_views()
 
     # ---- torch.nn.Module look-alikes -------------------------------------------------------------
@@ -143,16 +146,12 @@ class Xtractor:
             raise NotImplementedError("sidekit_amd.Xtractor runs extraction only: call with is_eval=True and no target")
         x = self._check_input(x, pcm16_ok=True)
         B, L = x.shape
-        h = self._handle()
-        self._reserve(h, B, L)
-        lib = _lib.lib()
-        _lib.check(lib.xt_set_norm_embedding(h, 1 if norm_embedding else 0))
-        emb = torch.empty((B, self.embedding_size), dtype=torch.float32, device=x.device)
-        logits = torch.empty((B, int(self.speaker_number)), dtype=torch.float32, device=x.device) if self.loss == "aam" else None
+        h = self._reserve(B, L)
+        logits, emb = self._outputs(h, B, x.device, norm_embedding)
         lens = self._lengths(lengths, B, L)
+        lib = _lib.lib()
         entry = lib.xt_forward_pcm16 if x.dtype == torch.int16 else lib.xt_forward
-        _lib.check(entry(h, x.data_ptr(), x.stride(0) if B > 1 else L, _ptr(lens), B, L, emb.data_ptr(),
-                         logits.data_ptr() if logits is not None else None, self._stream(x)))
+        _lib.check(entry(h, x.data_ptr(), x.stride(0) if B > 1 else L, _ptr(lens), B, L, emb.data_ptr(), _dptr(logits), self._stream(x)))
         return (logits, emb) if self.loss == "aam" else emb
 
     # ---- pipelined forwards: two whole batches in flight (xt_forward_begin / xt_forward_end) ---------------------------------------
@@ -163,11 +162,23 @@ class Xtractor:
         except ValueError:
             return 2
 
-    # batches in flight.  Two is where the gain is (5.80 -> 5.56 ms per batch of 256, round 4).  A third adds 0.3-1.1 % on resident inputs (round 6, alternating
+    # batches in flight.  Two is where the gain is (5.80 -> 5.56 ms per batch of 256).  A third adds 0.3-1.1 % on resident inputs (alternating
     # runs on two boxes: 46.12 / 46.14 -> 46.49 / 46.63 k and 45.24 / 45.39 -> 45.74 / 45.52 k x-vectors/s) and COSTS the streaming extractor 13 % (38.5 / 39.6 ->
     # 34.4 / 33.6 k files/s: its copy stream and read-backs then share the device with three forwards); four in flight lose 8 % in bench.py itself (42.4-42.5 k);
     # GPU_MAX_HW_QUEUES=8 changes none of it.  profiles/r06_pipeline_depth.txt
-    pipeline_depth = _depth_from_env.__func__()
+    _pipeline_depth = _depth_from_env.__func__()
+
+    @property
+    def pipeline_depth(self):
+        return self._pipeline_depth
+
+    @pipeline_depth.setter
+    def pipeline_depth(self, depth):
+        if int(depth) != self._pipeline_depth:     # a new depth restarts the slot rotation, which the outstanding tickets belong to
+            if self._tickets:
+                raise RuntimeError(f"pipeline_depth: collect() the {len(self._tickets)} batch(es) in flight before changing the depth")
+            self._pipeline_depth, self._next_slot = int(depth), 0
+
     # Workspaces are sized for a batch's longest utterance rounded UP to a whole second of samples: a corpus streams batches whose maxima creep up by a few
     # samples at a time, and every new record otherwise costs a device synchronisation + the reallocation of every buffer of every slot in the middle of the
     # run (round 6: 16 384 files of 3-5 s: 37-39 k -> see profiles/r06_pipeline_bench.json).  At most one second of activations per utterance more memory.
@@ -186,34 +197,23 @@ class Xtractor:
         ``pipeline_depth`` may be outstanding.  The x-vectors are the bits ``forward`` returns."""
         x = self._check_input(x, pcm16_ok=True)
         B, L = x.shape
-        h = self._handle()
-        key = next(k for k, v in self._handles.items() if v is h)
-        lib = _lib.lib()
-        shapes = self._slot_shapes.setdefault(key, [])
-        if not any(b >= B and l >= L for b, l in shapes):
-            Lr = self._round_up(L)
-            with torch.cuda.device(self.device):
-                torch.cuda.synchronize(self.device)
-                _lib.check(lib.xt_reserve_slots(h, self.pipeline_depth, B, Lr))
-            shapes[:] = [(b, l) for b, l in shapes if not (b <= B and l <= Lr)] + [(B, Lr)]
-            self._reserved[key] = [(b, l) for b, l in self._reserved[key] if not (b <= B and l <= Lr)] + [(B, Lr)]
-        if len(self._tickets) >= self.pipeline_depth:
-            raise RuntimeError(f"submit: {self.pipeline_depth} batches are already in flight -- collect() the oldest first")
-        _lib.check(lib.xt_set_norm_embedding(h, 1 if norm_embedding else 0))
-        emb = torch.empty((B, self.embedding_size), dtype=torch.float32, device=x.device)
-        logits = torch.empty((B, int(self.speaker_number)), dtype=torch.float32, device=x.device) if self.loss == "aam" else None
+        depth = self.pipeline_depth
+        h = self._reserve(B, L, slots=depth)
+        if len(self._tickets) >= depth:
+            raise RuntimeError(f"submit: {depth} batches are already in flight -- collect() the oldest first")
+        logits, emb = self._outputs(h, B, x.device, norm_embedding)
         lens = self._lengths(lengths, B, L)
+        lib = _lib.lib()
         slot = self._next_slot
         rc = lib.xt_forward_begin(h, slot, x.data_ptr(), _lib.XT_I16 if x.dtype == torch.int16 else _lib.XT_F32,
-                                  x.stride(0) if B > 1 else L, _ptr(lens), B, L, emb.data_ptr(),
-                                  logits.data_ptr() if logits is not None else None, self._stream(x))
+                                  x.stride(0) if B > 1 else L, _ptr(lens), B, L, emb.data_ptr(), _dptr(logits), self._stream(x))
         if rc != _lib.SK_OK:
             # part of the forward may already be queued on the slot's stream (the library records the slot's completion event on its error
             # paths too): order the caller's stream behind it BEFORE emb / logits / x go back to the caching allocator with this frame
             msg = _lib.last_error()
             lib.xt_forward_end(h, slot, self._stream(x))
             raise (ValueError if rc == _lib.SK_EARG else RuntimeError)(msg)
-        self._next_slot = (slot + 1) % self.pipeline_depth
+        self._next_slot = (slot + 1) % depth
         # x is kept alive until the forward that reads it has been waited for; the submitting stream is kept because emb / logits were taken from ITS pool
         ticket = (h, slot, x, logits, emb, torch.cuda.current_stream(x.device))
         self._tickets.append(ticket)
@@ -250,23 +250,17 @@ class Xtractor:
         B, F, T = feats.shape
         if F != 80:
             raise RuntimeError(f"expected (B, 80, T) features, got {tuple(feats.shape)}")
-        h = self._handle()
-        self._reserve(h, B, (T - 1) * self.preprocessor.hop_length + self.preprocessor.n_fft)
-        lib = _lib.lib()
-        _lib.check(lib.xt_set_norm_embedding(h, 1 if norm_embedding else 0))
-        emb = torch.empty((B, self.embedding_size), dtype=torch.float32, device=feats.device)
-        logits = torch.empty((B, int(self.speaker_number)), dtype=torch.float32, device=feats.device) if self.loss == "aam" else None
+        h = self._reserve(B, (T - 1) * self.preprocessor.hop_length + self.preprocessor.n_fft)
+        logits, emb = self._outputs(h, B, feats.device, norm_embedding)
         lens = self._lengths(frames, B, T)
-        _lib.check(lib.xt_forward_features(h, feats.data_ptr(), _ptr(lens), B, T, emb.data_ptr(),
-                                           logits.data_ptr() if logits is not None else None, self._stream(feats)))
+        _lib.check(_lib.lib().xt_forward_features(h, feats.data_ptr(), _ptr(lens), B, T, emb.data_ptr(), _dptr(logits), self._stream(feats)))
         return (logits, emb) if self.loss == "aam" else emb
 
     def features(self, x, lengths=None):
         """Front-end only (``MelSpecFrontEnd.forward(is_eval=True)`` / ``MfccFrontEnd.forward``): ``(B, 80, T)``."""
         x = self._check_input(x)
         B, L = x.shape
-        h = self._handle("fp32")
-        self._reserve(h, B, L)
+        h = self._reserve(B, L, dtype="fp32")
         T = 1 + L // self.preprocessor.hop_length
         out = torch.empty((B, 80, T), dtype=torch.float32, device=x.device)
         lens = self._lengths(lengths, B, L)
@@ -348,6 +342,13 @@ class Xtractor:
             raise ValueError(f"lengths must have shape ({B},)")
         return arr
 
+    def _outputs(self, h, B, device, norm_embedding):
+        """``(logits, emb)`` buffers of a forward of B utterances (no logits for 'cce'), with the handle's norm-embedding switch set for it."""
+        _lib.check(_lib.lib().xt_set_norm_embedding(h, 1 if norm_embedding else 0))
+        emb = torch.empty((B, self.embedding_size), dtype=torch.float32, device=device)
+        logits = torch.empty((B, int(self.speaker_number)), dtype=torch.float32, device=device) if self.loss == "aam" else None
+        return logits, emb
+
     @staticmethod
     def _stream(t):
         return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
@@ -388,21 +389,26 @@ class Xtractor:
                 lib.xt_destroy(h)
                 raise
         self._handles[key] = h
-        self._reserved[key] = []
+        self._reserved[key] = {}
         return h
 
-    def _reserve(self, h, B, L):
-        """Size the workspace for a (B, L) batch unless a shape reserved earlier covers it in both dimensions: buffers grow to
-        the largest B x L product actually requested, never to max(B) x max(L) of unrelated calls."""
-        key = next(k for k, v in self._handles.items() if v is h)
+    def _reserve(self, B, L, slots=0, dtype=None):
+        """The handle for ``dtype``, its workspace sized for a (B, L) batch -- with ``slots`` > 0 for that many pipelined slots as well --
+        unless a shape reserved earlier covers it in both dimensions and in slots (``_reserved``: {(batch, samples): slots}): buffers
+        grow to the largest B x L product actually requested, never to max(B) x max(L) of unrelated calls."""
+        key = self._dtype_key(dtype)
+        h = self._handle(key)
         shapes = self._reserved[key]
-        if any(b >= B and l >= L for b, l in shapes):
-            return
+        if any(b >= B and l >= L and s >= slots for (b, l), s in shapes.items()):
+            return h
         L = self._round_up(L)
+        lib = _lib.lib()
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)
-            _lib.check(_lib.lib().xt_reserve(h, B, L))
-        self._reserved[key] = [(b, l) for b, l in shapes if not (b <= B and l <= L)] + [(B, L)]
+            _lib.check(lib.xt_reserve_slots(h, slots, B, L) if slots else lib.xt_reserve(h, B, L))
+        kept = {(b, l): s for (b, l), s in shapes.items() if not (b <= B and l <= L and s <= slots)}
+        self._reserved[key] = {**kept, (B, L): slots}
+        return h
 
     def _drop_handles(self):
         if self._handles:
@@ -412,7 +418,7 @@ class Xtractor:
             for h in self._handles.values():
                 lib.xt_destroy(h)
         self._handles, self._reserved = {}, {}
-        self._slot_shapes, self._tickets, self._next_slot = {}, [], 0
+        self._tickets, self._next_slot = [], 0
 
     def __del__(self):
         try:
@@ -468,14 +474,7 @@ def extract_embeddings(idmap_name, model_filename, data_root_name, device, batch
     from ..statserver import StatServer
     if transform_pipeline:
         raise NotImplementedError("augmentation pipelines are training-time (out of scope)")
-    if isinstance(model_filename, str):
-        checkpoint = torch.load(model_filename, map_location="cpu", weights_only=False)
-        model_opts = checkpoint["model_archi"]
-        model = Xtractor(checkpoint["speaker_number"], model_archi=model_opts["model_type"], loss=model_opts["loss"]["type"],
-                         embedding_size=256)
-        model.load_state_dict(checkpoint["model_state_dict"])
-    else:
-        model = model_filename
+    model = _load_model(model_filename)
     idmap = idmap_name if isinstance(idmap_name, IdMap) else IdMap(idmap_name)
     model.eval()
     model.to(device)

@@ -296,6 +296,35 @@ def test_pipelined_forwards_are_bit_identical(gpu, dtype):
     assert torch.equal(m.collect(m.submit(batches[0][0]))[1], refs[0][1])
 
 
+def test_pipeline_depth_changes_between_submits(gpu):
+    """raising Xtractor.pipeline_depth after a first submit reserves the extra slot (the third batch in flight once failed with
+    SK_EWORKSPACE); changing the depth while tickets are outstanding is refused before anything is queued; with none outstanding the slot
+    rotation restarts at 0.  Every result is the plain forward's, bit for bit."""
+    m = Xtractor(64, model_archi="halfresnet34", loss="aam", seed=14).to(gpu).eval()
+    m.compute_dtype = "bf16"
+    g = torch.Generator(device="cuda").manual_seed(23)
+    batches = [0.1 * torch.randn(B, 32000, device="cuda", generator=g) for B in (128, 96, 128)]
+    refs = [tuple(t.clone() for t in m(w, is_eval=True)) for w in batches]
+
+    def same(out, ref):
+        return torch.equal(out[0], ref[0]) and torch.equal(out[1], ref[1])
+
+    m.pipeline_depth = 2
+    assert same(m.collect(m.submit(batches[0])), refs[0])
+    m.pipeline_depth = 3
+    tickets = [m.submit(w) for w in batches]                     # three batches in flight
+    with pytest.raises(RuntimeError):
+        m.pipeline_depth = 2
+    assert m.pipeline_depth == 3
+    outs = [m.collect(t) for t in tickets]
+    torch.cuda.synchronize()
+    assert all(same(o, r) for o, r in zip(outs, refs))
+    m.pipeline_depth = 2                                         # nothing outstanding: allowed
+    t1, t2 = m.submit(batches[1]), m.submit(batches[2])
+    assert same(m.collect(t1), refs[1]) and same(m.collect(t2), refs[2])
+    assert same(m(batches[0], is_eval=True), refs[0])
+
+
 def test_pipelined_forwards_tdnn(gpu):
     """The same for the TDNN x-vector (ragged rows, fp32): submit / collect against the plain forward."""
     m = Xtractor(64, model_archi="xvector", loss="aam", seed=13).to(gpu).eval()

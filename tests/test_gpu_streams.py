@@ -1,5 +1,5 @@
 """The handle's stream / thread contract is a property of the LIBRARY (include/sidekit_amd.h, "Conventions"; csrc/xt_api.hip
-enter_stream / leave_stream / EntryGuard), not of the caller's discipline.
+Entry: lock / run / order), not of the caller's discipline.
 
 The reference drives a model from one Python thread on torch's current stream (sidekit/bin/extract_xvectors.py:130-150,
 sidekit/nnet/xvector.py:1890-1896) and torch orders everything; this library reuses one set of workspaces from call to call, so two
