@@ -136,8 +136,9 @@ int xt_debug_tap(xt_handle* h, const char* name, void* h_dst, size_t capacity, s
 
 /* Measurement: when on, every kernel launch of the forward is bracketed by HIP events recorded on
  * the launch stream.  xt_get_profile synchronises and returns, per slot, the summed device time (ms)
- * and the number of launches since the last reset.  Slots 0..10 are the 3x3 / 1x1 trunk convolution
- * shapes in the order L1, L1-shortcut, L2a, L2-shortcut, L2, L3a, L3-shortcut, L3, L4a, L4-shortcut, L4.
+ * and the number of launches since the last reset.  Slots 0, 2, 4, 5, 7, 8, 10 are the 3x3 trunk convolution
+ * shapes L1, L2a, L2, L3a, L3, L4a, L4; slots 1, 3, 6, 9 (once the layers' stand-alone 1x1 shortcut convolutions) are
+ * unused and stay zero since the shortcut runs in the epilogue of the block's second convolution.
  * `on`: 0 = off, 1 = every slot, otherwise a mask with bit (slot + 1) set for each slot to bracket -- an event pair
  * costs about 2 us of stream time, so a timed run brackets only the class it reports (bench.py: the dominant one). */
 #define XT_PROF_FRONTEND 11
@@ -150,9 +151,10 @@ int xt_set_profile(xt_handle* h, int32_t on);
 int xt_get_profile(xt_handle* h, double* ms /*[XT_PROF_SLOTS]*/, int64_t* launches /*[XT_PROF_SLOTS]*/, int32_t reset);
 
 /* Tuning harness (diagnostic): mean device ms of `iters` launches of trunk convolution `shape` (slot order of
- * xt_get_profile) on a B x T batch; variant bit0 = no stores, bit1 = no MFMA loop, bit2 = no staging, bit3 = statistics epilogue, bit4 = residual epilogue,
- * bit5 = one workgroup per tile even for the persistent shapes, bit6 = print the runtime's occupancy for the shape; shapes 0..10 are the
- * trunk's eleven, 42 / 43 the small-grid tilings of layers 3 / 4 (csrc/conv3x3.hip). */
+ * xt_get_profile) on a B x T batch; variant bit0 = no stores, bit1 = no MFMA loop, bit2 = no staging, bit4 = residual epilogue (conv2 of a block), otherwise
+ * the statistics epilogue runs (conv1 of a block; bit3, which once selected it, is accepted and implied), bit5 = one workgroup per tile even for the persistent
+ * shapes, bit6 = print the runtime's occupancy for the kernel; shapes 0, 2, 4, 5, 7, 8, 10 are the trunk's seven (2, 5, 8, the stride-2 first convolutions,
+ * have no residual form), 42 / 43 the small-grid tilings of layers 3 / 4, which have the residual form only (csrc/conv3x3.hip). */
 int sk_bench_conv(int32_t shape, int32_t dtype, int32_t B, int32_t T, int32_t iters, int32_t variant, float* ms_out,
                   double* phase_cycles /* [8] mean shader cycles per kernel phase, or NULL */);
 

@@ -1,4 +1,4 @@
-// 3x3 (and strided 1x1) convolution + folded BatchNorm (+ReLU) (+SE plane sums) for the
+// 3x3 convolution + folded BatchNorm (+ReLU) (+SE plane sums) (+residual, + the first block's 1x1 shortcut) for the
 // HalfResNet34 trunk: reference BasicBlock.forward, sidekit/nnet/res_net.py:309-320 (K5/K6 of
 // SURVEY 2.3), built MI355X-first:
 //
@@ -16,7 +16,7 @@
 //    consumed LDS buffer and writes it as contiguous 16-B-per-lane NHWC rows;
 //  * per-utterance lengths: rows >= the utterance's own row count are read as zero
 //    padding and never written, so a padded batch reproduces each utterance run alone;
-//  * one template, four compile-time epilogue forms (plain / statistics for the SE gate / residual / residual with the
+//  * one template, three compile-time epilogue forms (statistics for the SE gate / residual / residual with the
 //    first block's 1x1 shortcut convolution evaluated in place), two LDS images (padded, or pad-free and swizzled),
 //    per-shape occupancy: persistent weight-resident workgroups for the 32-channel inputs, three workgroups per
 //    CU at 168 registers for layers 2-3, small tiles for the stride-2 shapes (DESIGN.md section 4 has the measurements
@@ -38,19 +38,11 @@ template <> __device__ inline void mma_step<float>(f32x16& acc, const uint4& w, 
 }
 
 enum { LANES_LINEAR = 0, LANES_GRID = 1, LANES_DENSE = 2 };
-template <typename T_, int CIN_, int COUT_, int S_, int WIN_, int TH_, int WM_, int WN_, int MW_, int NW_, int CK_, int TAPS_, int OCC_ = 0, int PD_ = 0, bool SWZ_ = false, int BLK_ = LANES_LINEAR, bool M16_ = false, bool DIRECT_ = false, bool S2G_ = false, int LEANF_ = -1>
+template <typename T_, int CIN_, int COUT_, int S_, int WIN_, int TH_, int WM_, int WN_, int MW_, int NW_, int CK_, int OCC_ = 0, int PD_ = 0, bool SWZ_ = false, int BLK_ = LANES_LINEAR, bool M16_ = false, bool S2G_ = false>
 struct ConvCfg {
-  // DIRECT: the epilogue stores straight from the accumulators (32x32 MFMA layouts).  A lane holds, for its position, four groups of 4
-  // consecutive output channels (8 B of bf16); v_permlane32_swap pairs the groups of lanes r and r + 32 into 16-B pieces of 8
-  // consecutive channels, so a wave's store instruction writes 32 B of each of its 32 positions and two of them complete the lines
-  // (cdna_hip_programming.md T21) -- no transposition through LDS, no barriers, no copy-out pass.  The statistics form then leaves
-  // the border sums of the SE gate to se_pre_kernel, which reads the stored border rows / columns back.
-  static constexpr bool DIRECT = DIRECT_;
-  static_assert(!DIRECT_ || (!M16_), "DIRECT: 32x32 MFMA accumulator layout");
   using T = T_;
   static constexpr int EB = elem<T_>::bytes;
   static constexpr int CIN = CIN_, COUT = COUT_, S = S_, WIN = WIN_, TH = TH_, WM = WM_, WN = WN_, MW = MW_, NW = NW_, CK = CK_;
-  static constexpr int TAPS = TAPS_;             // 9 (3x3, pad 1) or 1 (1x1: centre tap only)
   static constexpr int WOUT = WIN / S;
   static constexpr int MT = TH * WOUT;           // positions per workgroup
   static constexpr int NT = WN * NW * 32;        // output channels per workgroup
@@ -84,7 +76,7 @@ struct ConvCfg {
   // one register per tap (or per dw), XORed with the k-step -- one VALU instruction per k-step instead of one per M-tile.
   static constexpr int BLK = BLK_;
   static constexpr int GC = BLK == LANES_GRID ? (WIN_ / S_) / MW_ : 16, GR = 16 / GC;   // read-group block (GRID)
-  static_assert(BLK == LANES_LINEAR || (SWZ_ && S_ == 1 && TAPS_ == 9), "block lane orders: swizzled image, stride 1, 3x3");
+  static_assert(BLK == LANES_LINEAR || (SWZ_ && S_ == 1), "block lane orders: swizzled image, stride 1");
   static_assert(BLK != LANES_GRID || (GC * MW_ == WIN_ / S_ && GR * GC == 16 && TH_ == 2 * WM_ * GR), "GRID: W = MW * GC, TH = 2 * WM * GR");
   static_assert(BLK != LANES_DENSE || (WM_ == 1 && CK_ * elem<T_>::bytes == 256 && TH_ * (WIN_ + 1) <= MW_ * 32), "DENSE: 256-B positions, one wave row");
   // a leading zero position in front of the image makes column -1 of a row the physically preceding position (no address
@@ -113,25 +105,22 @@ struct ConvCfg {
   // swizzle key of the staged position (staged row, column): XORed into the 16-B chunk index of the position
   static constexpr int KCMASK = (GC >> SWSH) - 1;                   // GRID: column bits of the key, (col >> SWSH) & KCMASK
   static constexpr int KRSH = SWSH == 0 ? (GC == 4 ? 2 : (GC == 8 ? 3 : 4)) : (SWSH == 1 ? (GC == 8 ? 2 : 3) : 2);   // log2(GC) - SWSH
-  // S2G (round 3; A/B shapes X17-X19 only -- measured, not faster, see the shape list): the stride-2 first convolution of a layer on a
-  // PLANAR image with a block lane order.  A tap of a stride-2 convolution
+  // S2G: the stride-2 first convolution of a layer on a PLANAR image, with the 16x16x32 MFMA.  A tap of a stride-2 convolution
   // reads every other staged column, so on the row-major image its lanes only ever touch half of the 16-B slots of a bank row (rocprofv3:
   // 48 / 58 / 70 % of the LDS cycles of layers 2 / 3 / 4 were conflict cycles; scripts/lds_conflicts.py: 7.8 / 10 / 14 cycles per read).
   // Staged row = [even columns | odd columns | zero position] (a DMA lane may fetch any global address, so the permutation is free): a
-  // tap's lanes then read CONSECUTIVE positions of one plane, and the 16 lanes of read group g of M-tile i own the S2GR x S2GC block at
-  // block row wm, block column 2 i + g of the output tile (2 x 8 at W_out 40, 4 x 4 at 20, 8 x 2 at 10).  Key = (output-row bits, the
-  // position bits above the bank row): 16 different slots under every tap, 4.2 cycles per read in the model (the zero position is the rest).
+  // tap's lanes then read CONSECUTIVE positions of one plane, in S2GR x S2GC blocks of 16 output positions (2 x 8 at W_out 40, 4 x 4 at 20,
+  // 8 x 2 at 10).  Key = (output-row bits, the position bits above the bank row).
   static constexpr bool S2G = S2G_;
+  static_assert(!S2G_ || M16_, "S2G: the planar image is read by the 16x16x32 MFMA lane order only");
   static constexpr int S2GR = S2G_ ? TH_ / WM_ : 1, S2GC = 16 / S2GR, S2NBC = (WIN_ / S_) / S2GC;
   static constexpr int S2PPB = 256 / (CK_ * elem<T_>::bytes) > 0 ? 256 / (CK_ * elem<T_>::bytes) : 1;   // positions per 256-B bank row
   static constexpr int S2PB = S2GC / S2PPB > 0 ? S2GC / S2PPB : 1;                                         // key values taken from the position
-  static_assert(!S2G_ || (BLK_ == LANES_LINEAR && SWZ_ && S_ == 2 && TAPS_ == 9 && TH_ % WM_ == 0 && S2GR * S2GC == 16 &&
+  static_assert(!S2G_ || (BLK_ == LANES_LINEAR && SWZ_ && S_ == 2 && TH_ % WM_ == 0 && S2GR * S2GC == 16 &&
                           (WIN_ / 2) % S2GC == 0 && 2 * MW_ >= S2NBC && S2GC >= S2PPB && S2GR * S2PB == CK_ * elem<T_>::bytes / 16),
                 "S2G: stride 2, swizzled image, 16-position blocks that tile the output rows, one key value per slot of a position");
-  __host__ __device__ static constexpr int planar(int col) { return (col < 0 || col >= WIN) ? WIN : (col & 1) * (WIN / 2) + (col >> 1); }
   __host__ __device__ static constexpr int unplanar(int P) { return P < WIN / 2 ? 2 * P : 2 * (P - WIN / 2) + 1; }   // P < WIN
-  // S2G with the 16x16x32 MFMA (round 4: the stride-2 product shapes).  A lane is ONE position (l & 15) of a 16-position tile = one
-  // S2GR x S2GC block (block row = wave row, block column = tile index: W_out / S2GC = 5 tiles per wave for all three shapes, no idle
+  // A lane is ONE position (l & 15) of a 16-position tile = one S2GR x S2GC block (block row = wave row, block column = tile index: W_out / S2GC = 5 tiles per wave for all three shapes, no idle
   // MFMA rows -- the 32-row tiles wasted a sixth) and the 16-B chunk 4 s + (l >> 4) of a 32-channel k-step.  A read group of a
   // ds_read_b128 then carries chunk q for tile positions {0-3, 12-15} and chunk q + 1 for {4-11}, so besides 16 different (bank-row
   // part, key) pairs no position of the first half may have a key that differs from one of the second half in bit 0 alone:
@@ -142,7 +131,7 @@ struct ConvCfg {
   // scripts/lds_conflicts.py (s2_m16_report): 4.27 LDS cycles per read for all three (the tile-0 reads of the zero position are the .27).
   __host__ __device__ static constexpr int s2_rowkey(int row) {
     const int hp = (row >> 1) & (S2GR - 1);
-    return ((M16_ && S2GR == 8) ? (((hp << 1) & 7) | (hp >> 2)) : hp) * S2PB;
+    return (S2GR == 8 ? (((hp << 1) & 7) | (hp >> 2)) : hp) * S2PB;
   }
   __host__ __device__ static constexpr int s2p_half(int p) { return (p >= 4 && p < 12) ? 1 : 0; }
   __host__ __device__ static constexpr int s2p_j(int p) { return p < 4 ? p : (p < 12 ? p - 4 : p - 8); }
@@ -173,19 +162,20 @@ struct ConvCfg {
   static_assert(!SWZ || (SPP == 4 || SPP == 8 || SPP == 16 || SPP == 32), "swizzled image: 64..512 B per position");
   static constexpr int KS = CB / 32;             // MFMA k-steps (32 B of k) per tap per chunk
   static constexpr int NCH = CIN / CK;           // channel chunks
-  static constexpr int KTOT = NCH * TAPS * KS;   // k-steps per output-channel tile
+  static constexpr int KTOT = NCH * 9 * KS;   // k-steps per output-channel tile
   // waves per SIMD the kernel is compiled for (caps the register budget at 512 / OCC): by default two workgroups per
   // CU whenever two halo tiles fit the LDS and the accumulators are small enough
   static constexpr int OCC = OCC_ ? OCC_ : ((MW * NW <= 5 && 160 * 1024 / LDS * WM * WN >= 8) ? 2 : 1);
-  static constexpr int NK = TAPS * KS;           // k-steps per channel chunk
-  static constexpr int KS32 = CB / 64, NK32 = TAPS * KS32, KTOT32 = NCH * NK32;   // M16: 32-channel k-steps
+  static constexpr int NK = 9 * KS;              // k-steps per channel chunk (nine taps)
+  static constexpr int KS32 = CB / 64, NK32 = 9 * KS32, KTOT32 = NCH * NK32;   // M16: 32-channel k-steps
   static constexpr int MT16 = 2 * MW, NT16 = 2 * NW;                              // M16: position / output-channel tiles of 16 per wave
-  static constexpr int PD = PD_ ? PD_ : ((NK * NW <= 24) ? NK : (NW == 1 ? 8 : 4));   // weight prefetch depth in k-steps
-  static constexpr int PD16 = NK32 * NT16 <= 18 ? NK32 : (PD_ >= 16 ? PD_ - 16 : 2);   // M16: depth in 32-channel steps (two 1-KB fragments each per NW); PD_ = 16 + d selects depth d (A/B shapes)
-  static constexpr bool RESIDENT = TAPS == 9 && NCH == 1 && (M16 ? PD16 == NK32 : PD == NK) && NT == COUT;   // a wave keeps all its weight fragments in registers
+  // weight prefetch depth; PD_ names it where the default does not serve, in the k-steps of the shape's MFMA
+  static constexpr int PD = PD_ ? PD_ : ((NK * NW <= 24) ? NK : (NW == 1 ? 8 : 4));   // 32x32: k-steps
+  static constexpr int PD16 = NK32 * NT16 <= 18 ? NK32 : (PD_ ? PD_ : 2);             // M16: 32-channel steps (two 1-KB fragments each per NW)
+  static constexpr bool RESIDENT = NCH == 1 && (M16 ? PD16 == NK32 : PD == NK) && NT == COUT;   // a wave keeps all its weight fragments in registers
   // register-lean epilogue (constants per channel group, shortcut prefetch in two halves).  The two epilogue walks add the statistics form's plane sums in
-  // different orders (group-major / tile-major), so a shape that must reproduce another shape's sums bit for bit names that shape's choice (LEANF_)
-  static constexpr bool LEAN = LEANF_ < 0 ? (RESIDENT || OCC >= 3) : (LEANF_ != 0);
+  // different orders (group-major / tile-major)
+  static constexpr bool LEAN = RESIDENT || OCC >= 3;
   static_assert(MT <= WM * MW * 32, "positions must be covered by the waves' 32-row MFMA tiles (trailing tiles may be partial or idle)");
   static constexpr bool PARTIAL_M = MT < WM * MW * 32;   // lanes past the tile compute on a duplicate of the last position and store nothing
   // M16: tile-linear output position of lane position p (0..15) of 16-position tile t of wave row wm; >= MT: none
@@ -208,11 +198,6 @@ struct ConvCfg {
     } else if constexpr (BLK == LANES_DENSE) {
       const int L = i * 32 + r, row = L / (WIN + 1), col = L % (WIN + 1);
       return (col < WIN && row < TH) ? row * WOUT + col : MT;
-    } else if constexpr (S2G) {
-      const int g = ((r >= 4 && r < 12) || (r >= 16 && r < 20) || r >= 28) ? 1 : 0;
-      const int j = r - (r < 4 ? 0 : (r < 12 ? 4 : (r < 20 ? 8 : (r < 28 ? 12 : 16))));
-      const int bc = 2 * i + g;
-      return bc < S2NBC ? (wm * S2GR + j / S2GC) * WOUT + bc * S2GC + j % S2GC : MT;
     } else {
       return (wm * MW + i) * 32 + r;
     }
@@ -224,15 +209,16 @@ struct ConvCfg {
 // second launch-bound = waves per SIMD: two workgroups per CU whenever two halo tiles fit the LDS, which caps the
 // kernel at 256 registers (VGPR + AGPR) per lane
 // FORM selects the epilogue at compile time (the statistics form carries no shortcut registers, the residual form no
-// plane sums): 0 plain, 1 statistics (conv1 of a block), 2 residual (conv2 of a block), 3 residual with the layer's
+// plane sums): 1 statistics (conv1 of a block), 2 residual (conv2 of a block), 3 residual with the layer's
 // first-block 1x1 shortcut convolution evaluated in the epilogue
-enum { FORM_PLAIN = 0, FORM_STATS = 1, FORM_RESID = 2, FORM_RESID_SC = 3 };   // 3: residual form, 1x1 shortcut conv computed in place
+enum { FORM_STATS = 1, FORM_RESID = 2, FORM_RESID_SC = 3 };
 template <int F> struct FormTag { static constexpr int value = F; };
 
 template <class C, int FORM>
 __global__ __launch_bounds__(C::WM * C::WN * 64, C::OCC)
 void conv3x3_kernel(ConvArgs a) {
   using T = typename C::T;
+  constexpr bool STATS = FORM == FORM_STATS, RESID = FORM == FORM_RESID, RSC = FORM == FORM_RESID_SC;
   constexpr int NWAVES = C::WM * C::WN, NTHREADS = NWAVES * 64;
   // NT < COUT (layer 4: 128 of 256 output channels per workgroup): the NY workgroups of a work item read the SAME halo tile, so
   // they sit NY x 8 apart in a 1-D grid -- block ids b and b + 8 share an XCD (round-robin dispatch) and start together, which
@@ -291,10 +277,10 @@ void conv3x3_kernel(ConvArgs a) {
     if constexpr (!C::LEAD) fixreg = col0 == 0 ? C::RS - C::CB : -C::CB;
   }
   int s2x = 0;   // S2G: taps of the third kernel row read the next output row's staged pair -> another row key: one XOR on the address
-  // S2G + M16: per-lane byte offset of (tile 0, horizontal tap dw) at k-step 0; tile t adds the immediate t * S2GC * CB (the column part of
+  // S2G: per-lane byte offset of (tile 0, horizontal tap dw) at k-step 0; tile t adds the immediate t * S2GC * CB (the column part of
   // the key has period S2GC), except that column -1 of tile 0 is the row's zero position (s2bz)
   int s2b[3] = {0, 0, 0}, s2bz = 0;
-  if constexpr (C::S2G && C::M16) {
+  if constexpr (C::S2G) {
     const int p = lane & 15, q = lane >> 4;
     const int ho = wm * C::S2GR + C::s2p_row(p), pcol = C::s2p_col(p);
     s2x = (C::s2_rowkey(2 * ho) ^ C::s2_rowkey(2 * ho + 2)) << 4;
@@ -305,22 +291,6 @@ void conv3x3_kernel(ConvArgs a) {
     }
     const int Pz = pcol == 0 ? C::WIN : C::WIN / 2 + pcol - 1;
     s2bz = (2 * ho) * C::RS + Pz * C::CB + ((q ^ C::swz_key(2 * ho, Pz)) << 4);
-  }
-  if constexpr (C::S2G && !C::M16) {
-    const int g = ((r >= 4 && r < 12) || (r >= 16 && r < 20) || r >= 28) ? 1 : 0;
-    const int j = r - (r < 4 ? 0 : (r < 12 ? 4 : (r < 20 ? 8 : (r < 28 ? 12 : 16))));
-    const int ho = wm * C::S2GR + j / C::S2GC;
-    s2x = (C::s2_rowkey(2 * ho) ^ C::s2_rowkey(2 * ho + 2)) << 4;
-#pragma unroll
-    for (int i = 0; i < C::MW; ++i) {
-      const int bc = 2 * i + g < C::S2NBC ? 2 * i + g : C::S2NBC - 1;   // lanes past the last block re-read it (and store nothing)
-      const int wo = bc * C::S2GC + j % C::S2GC;
-#pragma unroll
-      for (int dw = 0; dw < 3; ++dw) {
-        const int P = C::planar(2 * wo + dw - 1);
-        base[i][dw] = (2 * ho) * C::RS + P * C::CB + ((h ^ C::swz_key(2 * ho, P)) << 4);
-      }
-    }
   }
 #pragma unroll
   for (int i = 0; i < ((C::BLK || C::S2G) ? 0 : C::MW); ++i) {
@@ -357,7 +327,7 @@ void conv3x3_kernel(ConvArgs a) {
   constexpr bool RESIDENT = C::RESIDENT;
   // packed-weight index (tap * KS + ks) of the kk-th k-step of a chunk (see the k-step order below)
   auto kord = [](int kk) {
-    return (C::SWZ && C::TAPS == 9 && !C::BLK) ? ((kk % 3) * 3 + kk / (3 * C::KS)) * C::KS + (kk / 3) % C::KS : kk;
+    return (C::SWZ && !C::BLK) ? ((kk % 3) * 3 + kk / (3 * C::KS)) * C::KS + (kk / 3) % C::KS : kk;
   };
   uint4 wq[C::M16 ? 1 : PD][C::NW];
   // M16: fragments of 16 output channels x 32 input channels; a wave's 32-channel tile j is the pair of 16-channel tiles 2j, 2j + 1
@@ -449,13 +419,12 @@ void conv3x3_kernel(ConvArgs a) {
     __builtin_amdgcn_s_setprio(0);
     // k-step order inside a chunk: (tap, ks) for the padded image; the swizzled image walks (dw, ks, dh) so that one
     // swizzled address serves three consecutive steps (the row offset is an instruction immediate) and then dies
-    auto step_tap = [](int kk) { return (C::SWZ && C::TAPS == 9 && !C::BLK) ? (kk % 3) * 3 + kk / (3 * C::KS) : kk / C::KS; };
-    auto step_ks = [](int kk) { return (C::SWZ && C::TAPS == 9 && !C::BLK) ? (kk / 3) % C::KS : kk % C::KS; };
+    auto step_tap = [](int kk) { return (C::SWZ && !C::BLK) ? (kk % 3) * 3 + kk / (3 * C::KS) : kk / C::KS; };
+    auto step_ks = [](int kk) { return (C::SWZ && !C::BLK) ? (kk / 3) % C::KS : kk % C::KS; };
     int rl = r;
     if constexpr (C::BLK == LANES_DENSE) asm volatile("" : "+v"(rl));
     auto xaddr = [&](int i, int kk) {
-      const int t = step_tap(kk), ks = step_ks(kk);
-      const int tap = (C::TAPS == 9) ? t : 4;
+      const int tap = step_tap(kk), ks = step_ks(kk);
       if constexpr (C::BLK != LANES_LINEAR) {
         const int dh = tap / 3, dw = tap % 3;
         if constexpr (C::BLK == LANES_DENSE) {
@@ -469,8 +438,7 @@ void conv3x3_kernel(ConvArgs a) {
           if (!C::LEAD && dw == 0 && i == 0) return smem + (v + fixreg) + dh * C::RS;
           return smem + v + (C::IMG0 + (i * C::GC + dw - 1) * C::CB + dh * C::RS);
         }
-      } else if constexpr (C::S2G) return smem + (base[i][tap % 3] ^ ((ks << 5) ^ (tap / 3 == 2 ? s2x : 0))) + (tap / 3) * C::RS;
-      else if constexpr (C::SWZ) return smem + (base[i][tap % 3] ^ (ks << 5)) + (tap / 3) * C::RS;
+      } else if constexpr (C::SWZ) return smem + (base[i][tap % 3] ^ (ks << 5)) + (tap / 3) * C::RS;
       else return smem + base[i][0] + (tap / 3) * C::RS + (tap % 3) * C::PSTRIDE + ks * 32;
     };
     if constexpr (C::M16) {
@@ -567,8 +535,7 @@ void conv3x3_kernel(ConvArgs a) {
     }
   }
 
-  // ---- epilogue: BN scale/shift, then one of three forms:
-  //   plain      (+ReLU)                       -> store
+  // ---- epilogue: BN scale/shift, then the kernel's form:
   //   statistics (+ReLU, conv1 of a block)     -> store + the sums the SE gate of the block is derived from
   //   residual   (conv2 of a block)            -> * gate[b][c] + shortcut -> ReLU -> store
   // The tile is transposed through the (now consumed) LDS halo buffer and leaves as whole 1-KiB, 16-B-per-lane NHWC
@@ -576,7 +543,9 @@ void conv3x3_kernel(ConvArgs a) {
   constexpr int NC = C::WN * 32;                // channels of one out sub-tile
   constexpr int OPS = NC * C::EB + 16;          // out-tile position stride in LDS (padded against bank conflicts)
   static_assert(C::MT * OPS <= C::LDS, "out tile must fit the consumed input buffer");
-  if (!(a.dbg & 128)) __builtin_amdgcn_s_setprio(3);   // memory phases (epilogue, stores, next tile's DMA) ahead of other workgroups' MFMAs
+  // memory phases (epilogue, stores, next tile's DMA) ahead of other workgroups' MFMAs.  The test is always true (nothing sets bit 7 of dbg);
+  // it stays because the branch ends a scheduling region: without it seven kernels change registers and layer 1's in-place-shortcut form spills
+  if (!(a.dbg & 128)) __builtin_amdgcn_s_setprio(3);
   const int mvalid = (hout_b - ho0) * C::WOUT < C::MT ? (hout_b - ho0) * C::WOUT : C::MT;
   const size_t gpos0 = ((size_t)b * a.Hout + ho0) * C::WOUT;
   auto lds_elem = [&](int m, int c) {
@@ -584,107 +553,12 @@ void conv3x3_kernel(ConvArgs a) {
     else return *reinterpret_cast<const float*>(smem + m * OPS + c * 4);
   };
   stamp(3);
-  // one output stream: (accumulators, BN scale/shift, destination, epilogue form)
-  auto emit = [&](auto form, auto& accv, const float* scale, const float* shift, unsigned char* out, bool relu) {
-  constexpr bool STATS = decltype(form)::value == FORM_STATS, RESID = decltype(form)::value == FORM_RESID;
-  constexpr bool RSC = decltype(form)::value == FORM_RESID_SC;
+  // The epilogue is a lambda called once, below, and its body is written at the level of do_item.  It is kept as one on purpose: written
+  // inline (with or without these four values as locals) the same statements compile to another schedule and register allocation in
+  // every kernel of the file ("what the trunk convolution no longer carries").
+  auto emit = [&](auto& accv, const float* scale, const float* shift, unsigned char* out) {
   const float* gate = (RESID || RSC) ? a.gate : nullptr;
   float* se_part = STATS ? a.se_part : nullptr;
-  if constexpr (C::DIRECT && decltype(form)::value != FORM_RESID_SC) {
-    unsigned char* scut_d = (unsigned char*)a.shortcut;
-#pragma unroll
-    for (int j = 0; j < C::NW; ++j) {
-      const int nbase = (nt0 + j * C::WN + wn) * 32;
-      const float* gate_b = RESID ? gate + (size_t)b * C::COUT : scale;
-      f32x4 sc[4], sh[4], gt[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        sc[g] = *reinterpret_cast<const f32x4*>(scale + nbase + 8 * g + 4 * h);
-        sh[g] = *reinterpret_cast<const f32x4*>(shift + nbase + 8 * g + 4 * h);
-        gt[g] = RESID ? *reinterpret_cast<const f32x4*>(gate_b + nbase + 8 * g + 4 * h) : sc[g];
-      }
-      float ssum[STATS ? 16 : 1];
-      if constexpr (STATS) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) ssum[q] = 0.f;
-      }
-      // this lane's two 16-B pieces of position m sit at channel offsets 16 k + 8 h of the wave's 32-channel tile (bf16),
-      // its four 16-B pieces at 8 g + 4 h (f32)
-      constexpr int NP = C::EB == 2 ? 2 : 4;
-      uint4 sreg[RESID ? C::MW : 1][RESID ? NP : 1];
-      auto paddr = [&](int m, int k) { return ((gpos0 + m) * C::COUT + nbase) * C::EB + (C::EB == 2 ? 32 * k + 16 * h : (8 * k + 4 * h) * 4); };
-      if constexpr (RESID) {
-#pragma unroll
-        for (int i = 0; i < C::MW; ++i) {
-          const int m = C::lane_pos(wm, i, r);
-#pragma unroll
-          for (int k = 0; k < NP; ++k) sreg[i][k] = (m < mvalid) ? *reinterpret_cast<const uint4*>(scut_d + paddr(m, k)) : make_uint4(0, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < C::MW; ++i) {
-        const int m = C::lane_pos(wm, i, r);
-        const bool valid = m < mvalid;
-        float v[4][4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float x = accv[i][j][4 * g + q] * sc[g][q] + sh[g][q];
-            if constexpr (RESID) x *= gt[g][q];
-            else if (relu) x = relu_nan(x);
-            if constexpr (C::EB == 2) x = round_bf16(x);
-            v[g][q] = x;
-            if constexpr (STATS) ssum[4 * g + q] += valid ? x : 0.f;
-          }
-        if constexpr (C::EB == 2) {
-          uint32_t P[4][2];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) { P[g][0] = pack_bf16x2(v[g][0], v[g][1]); P[g][1] = pack_bf16x2(v[g][2], v[g][3]); }
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            // lanes r and r + 32: (group 2k of the upper lane) <-> (group 2k + 1 of the lower lane)
-            const auto s0 = __builtin_amdgcn_permlane32_swap(P[2 * k][0], P[2 * k + 1][0], false, false);
-            const auto s1 = __builtin_amdgcn_permlane32_swap(P[2 * k][1], P[2 * k + 1][1], false, false);
-            uint4 piece = make_uint4(s0[0], s1[0], s0[1], s1[1]);
-            if constexpr (RESID) {
-              const uint4 sv = sreg[i][k];
-              const uint32_t vv[4] = {piece.x, piece.y, piece.z, piece.w}, ss[4] = {sv.x, sv.y, sv.z, sv.w};
-              uint32_t rr[4];
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                rr[e] = pack_bf16x2(relu_nan(bf16_to_f32(vv[e] & 0xffff) + bf16_to_f32(ss[e] & 0xffff)),
-                                    relu_nan(bf16_to_f32(vv[e] >> 16) + bf16_to_f32(ss[e] >> 16)));
-              piece = make_uint4(rr[0], rr[1], rr[2], rr[3]);
-            }
-            if (valid && !(a.dbg & 1)) *reinterpret_cast<uint4*>(out + paddr(m, k)) = piece;
-          }
-        } else {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            float4 piece = make_float4(v[g][0], v[g][1], v[g][2], v[g][3]);
-            if constexpr (RESID) {
-              const float4 sf = __builtin_bit_cast(float4, sreg[i][g]);
-              piece = make_float4(relu_nan(piece.x + sf.x), relu_nan(piece.y + sf.y), relu_nan(piece.z + sf.z), relu_nan(piece.w + sf.w));
-            }
-            if (valid && !(a.dbg & 1)) *reinterpret_cast<float4*>(out + paddr(m, g)) = piece;
-          }
-        }
-      }
-      if constexpr (STATS) {
-        float* sp = se_part + (((size_t)b * tiles + tile) * C::WM + wm) * C::COUT + nbase;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) ssum[q] = half_sum_upper_row(ssum[q]);
-        if (r == 16) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(sp + 4 * h + 8 * g) = make_float4(ssum[4 * g], ssum[4 * g + 1], ssum[4 * g + 2], ssum[4 * g + 3]);
-        }
-      }
-    }
-    if (true) { stamp(4); stamp(5); }
-    return;
-  }
 #pragma unroll
   for (int j = 0; j < C::NW; ++j) {
     const int nbase = (nt0 + j * C::WN + wn) * 32;
@@ -739,8 +613,7 @@ void conv3x3_kernel(ConvArgs a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float x = fmaf(accv[i][j][4 * g + q], sc[q], sh[q]);   // one rounding (the file is built with -ffp-contract=off); residual form: sc, sh carry the gate
-        if constexpr (STATS) x = relu_nan(x);   // the statistics form is conv1 + bn1 + ReLU of a block (launch_cfg checks a.relu): no run-time select per value
-        else if constexpr (!RESID) { if (relu) x = relu_nan(x); }
+        if constexpr (STATS) x = relu_nan(x);   // conv1 + bn1 + ReLU of a block; the residual form applies its ReLU after the shortcut, at the copy-out
         v[q] = x;
       }
       if constexpr (C::EB == 2) {
@@ -1000,7 +873,7 @@ void conv3x3_kernel(ConvArgs a) {
     }
   }
   };
-  emit(FormTag<FORM>{}, acc, a.scale, a.shift, reinterpret_cast<unsigned char*>(a.out), a.relu != 0);
+  emit(acc, a.scale, a.shift, reinterpret_cast<unsigned char*>(a.out));
   stamp(6);
   return true;
   };
@@ -1023,8 +896,24 @@ static int cu_count() {
   return n;
 }
 
-template <class C>
+// the forms a shape is launched in (HAS_RESID: with a stored shortcut and with the in-place one)
+enum { HAS_STATS = 1, HAS_RESID = 2 };
+
+template <class C, int FORM>
+static int launch_form(const ConvArgs& a, dim3 grid, dim3 block, hipStream_t st) {
+  if (a.dbg & 16) {  // tuning aid: what the runtime says about residency of the kernel
+    int nb = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv3x3_kernel<C, FORM>, block.x, 0);
+    fprintf(stderr, "[conv occupancy] LDS %d B, compiled for %d waves/SIMD: %d workgroups per CU\n", C::LDS, C::OCC, nb);
+  }
+  hipLaunchKernelGGL((conv3x3_kernel<C, FORM>), grid, block, 0, st, a);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
+template <class C, int FORMS>
 static int launch_cfg(const ConvArgs& a, hipStream_t st) {
+  static_assert(!(FORMS & HAS_RESID) || (C::S == 1 && C::CIN == C::COUT), "residual forms: conv2 of a block");
   const int tiles = cdiv(a.Hout, C::TH), nwork = a.B * tiles;
   // weight-resident shapes: just the workgroups the chip holds at once (LDS and the compiled-for occupancy), persistent
   constexpr int NWV = C::WM * C::WN;
@@ -1038,55 +927,31 @@ static int launch_cfg(const ConvArgs& a, hipStream_t st) {
   static_assert(NY == 1 || !C::RESIDENT, "persistent shapes cover all output channels");
   dim3 grid((unsigned)(NY > 1 ? cdiv(nwork, 8) * 8 * NY : ((C::RESIDENT && !(a.dbg & 8) && nwork > resident_wgs) ? resident_wgs : nwork)), 1);
   const dim3 block(NWV * 64);
-  if (a.dbg & 16) {  // tuning aid: what the runtime says about residency of the statistics-form kernel
-    int nb = -1;
-    if constexpr (C::TAPS == 9) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv3x3_kernel<C, FORM_STATS>, NWV * 64, 0);
-    fprintf(stderr, "[conv occupancy] LDS %d B, compiled for %d waves/SIMD: %d workgroups per CU\n", C::LDS, C::OCC, nb);
-  }
-  SK_CHECK(!(a.gate && a.se_part), SK_EARG, "a convolution is either the statistics or the residual form");
-  SK_CHECK(!a.se_part || a.relu, SK_EARG, "the statistics form is conv1 + bn1 + ReLU of a block: relu must be set");
+  SK_CHECK(!a.gate != !a.se_part, SK_EARG, "a convolution is either the statistics form (se_part) or a residual form (gate)");
   SK_CHECK(!a.sc_wpack || a.sc_in, SK_EARG, "the 1x1 shortcut weights belong to the in-place shortcut form (sc_in)");
-  if constexpr (C::TAPS == 9) {
-    if (a.se_part) {
-      hipLaunchKernelGGL((conv3x3_kernel<C, FORM_STATS>), grid, block, 0, st, a);
-      SK_HIP(hipGetLastError());
-      return SK_OK;
+  if (a.se_part) {
+    if constexpr (FORMS & HAS_STATS) return launch_form<C, FORM_STATS>(a, grid, block, st);
+  } else if (a.sc_in) {  // first block of a layer: the 1x1 shortcut conv of the block input evaluated in this epilogue
+    if constexpr (FORMS & HAS_RESID) {
+      SK_CHECK(a.sc_wpack && a.sc_shift && !a.shortcut, SK_EARG, "in-place shortcut form: bad arguments");
+      return launch_form<C, FORM_RESID_SC>(a, grid, block, st);
     }
-    if constexpr (C::S == 1 && C::CIN == C::COUT) {
-      if (a.gate && a.sc_in) {  // first block of a layer: the 1x1 shortcut conv of the block input evaluated in this epilogue
-        SK_CHECK(a.sc_wpack && a.sc_scale && a.sc_shift && !a.shortcut, SK_EARG, "in-place shortcut form: bad arguments");
-        hipLaunchKernelGGL((conv3x3_kernel<C, FORM_RESID_SC>), grid, block, 0, st, a);
-        SK_HIP(hipGetLastError());
-        return SK_OK;
-      }
-    }
-    if constexpr (C::S == 1) {
-      if (a.gate) {
-        hipLaunchKernelGGL((conv3x3_kernel<C, FORM_RESID>), grid, block, 0, st, a);
-        SK_HIP(hipGetLastError());
-        return SK_OK;
-      }
-    }
+  } else {
+    if constexpr (FORMS & HAS_RESID) return launch_form<C, FORM_RESID>(a, grid, block, st);
   }
-  SK_CHECK(!a.gate && !a.se_part, SK_EARG, "this convolution shape has no statistics / residual form");
-  hipLaunchKernelGGL((conv3x3_kernel<C, FORM_PLAIN>), grid, block, 0, st, a);
-  SK_HIP(hipGetLastError());
-  return SK_OK;
+  set_error("this convolution shape has no %s form", a.se_part ? "statistics" : "residual");
+  return SK_EARG;
 }
 
 // ---- the trunk's convolution shapes ---------------------------------------------------------
-//                      T      CIN COUT S WIN TH WM WN MW NW  CK TAPS
-using B_L1   = ConvCfg<bf16_t,  32,  32, 1, 80,  8, 4, 1, 5, 1, 32, 9, 0, 0, true>;     // two persistent weight-resident workgroups per CU; linear lanes + 32x32x16 MFMA kept: HBM-bound, 1 x 16 blocks / 16x16x32 measured no gain in the forward and the A,B,B,A read-group pattern of the 16-lane shape cannot be made conflict-free at 4 slots per position
-using B_L1S  = ConvCfg<bf16_t,  32,  32, 1, 80,  8, 4, 1, 5, 1, 32, 1, 0, 0, true>;
-using B_L2A  = ConvCfg<bf16_t,  32,  64, 2, 80,  4, 2, 2, 3, 1, 32, 9, 3, 0, true, LANES_LINEAR, true, false, true>;     // round 4: planar image (even | odd columns), 2 x 8 blocks, 16x16x32 MFMA, weights resident; 4-row tiles (47 KB), THREE persistent workgroups per CU (166 registers).  Alone 161 / 174 us (plain / statistics form) against 198 / 214 us for the round-3 row-major 32x32x16 shape (X25) and 170 / 184 us at two workgroups per CU (X29)
-using B_L2S  = ConvCfg<bf16_t,  32,  64, 2, 80,  8, 2, 2, 5, 1, 32, 1, 0, 0, true>;
-using B_L2   = ConvCfg<bf16_t,  64,  64, 1, 40,  8, 2, 2, 5, 1, 64, 9, 3, 4, true, LANES_GRID, true>;     // three workgroups per CU; 2 x 8 read-group blocks
-using B_L3A  = ConvCfg<bf16_t,  64, 128, 2, 40,  4, 1, 4, 3, 1, 64, 9, 2, 0, true, LANES_LINEAR, true, false, true>;     // round 4: planar image, 4 x 4 blocks, 16x16x32 MFMA (five 16-position tiles per wave, no idle MFMA rows): 117 / 132 us against 129 / 142 us (X26)
-using B_L3S  = ConvCfg<bf16_t,  64, 128, 2, 40,  8, 1, 4, 5, 1, 64, 1>;
-using B_L3   = ConvCfg<bf16_t, 128, 128, 1, 20,  8, 1, 4, 5, 1, 128, 9, 3, 4, true, LANES_GRID, true>;    // three workgroups per CU: 53760 B = 42 LDS granules; 4 x 4 read-group blocks
-using B_L4A  = ConvCfg<bf16_t, 128, 256, 2, 20,  8, 1, 4, 3, 1, 64, 9, 2, 0, true, LANES_LINEAR, true, false, true>;     // round 4: planar image, 8 x 2 blocks with the rotated row key, 16x16x32 MFMA: 91 us against 135 us (X27; planar 32x32x16, X19: 125 us); NT = 128: two workgroups per tile on one XCD
-using B_L4S  = ConvCfg<bf16_t, 128, 256, 2, 20, 16, 1, 4, 5, 1, 64, 1>;
-using B_L4   = ConvCfg<bf16_t, 256, 256, 1, 10, 17, 1, 4, 6, 1, 128, 9, 2, 0, true, LANES_DENSE, true>;   // 187 of 192 lane slots enumerate the 17 x 11 padded tile; NT = 128: two workgroups per CU
+//                      T      CIN COUT S WIN TH WM WN MW NW  CK  OCC PD SWZ BLK M16 S2G
+using B_L1  = ConvCfg<bf16_t,  32,  32, 1, 80,  8, 4, 1, 5, 1,  32, 0, 0, true>;     // two persistent weight-resident workgroups per CU; linear lanes + 32x32x16 MFMA kept: HBM-bound, 1 x 16 blocks / 16x16x32 measured no gain in the forward and the A,B,B,A read-group pattern of the 16-lane shape cannot be made conflict-free at 4 slots per position
+using B_L2A = ConvCfg<bf16_t,  32,  64, 2, 80,  4, 2, 2, 3, 1,  32, 3, 0, true, LANES_LINEAR, true, true>;     // planar image (even | odd columns), 2 x 8 blocks, 16x16x32 MFMA, weights resident; 4-row tiles (47 KB), THREE persistent workgroups per CU (166 registers).  Statistics form alone: 174 us against 214 us for the row-major 32x32x16 shape and 184 us at two workgroups per CU
+using B_L2  = ConvCfg<bf16_t,  64,  64, 1, 40,  8, 2, 2, 5, 1,  64, 3, 0, true, LANES_GRID, true>;     // three workgroups per CU; 2 x 8 read-group blocks
+using B_L3A = ConvCfg<bf16_t,  64, 128, 2, 40,  4, 1, 4, 3, 1,  64, 2, 0, true, LANES_LINEAR, true, true>;     // planar image, 4 x 4 blocks, 16x16x32 MFMA (five 16-position tiles per wave, no idle MFMA rows): statistics form 132 us against 142 us row-major
+using B_L3  = ConvCfg<bf16_t, 128, 128, 1, 20,  8, 1, 4, 5, 1, 128, 3, 0, true, LANES_GRID, true>;    // three workgroups per CU: 53760 B = 42 LDS granules; 4 x 4 read-group blocks
+using B_L4A = ConvCfg<bf16_t, 128, 256, 2, 20,  8, 1, 4, 3, 1,  64, 2, 0, true, LANES_LINEAR, true, true>;     // planar image, 8 x 2 blocks with the rotated row key, 16x16x32 MFMA: 91 us against 135 us row-major (and 125 us for the planar image on the 32x32x16 MFMA); NT = 128: two workgroups per tile on one XCD
+using B_L4  = ConvCfg<bf16_t, 256, 256, 1, 10, 17, 1, 4, 6, 1, 128, 2, 0, true, LANES_DENSE, true>;   // 187 of 192 lane slots enumerate the 17 x 11 padded tile; NT = 128: two workgroups per CU
 
 // Small-grid forms (round 5; batches of at most xt_handle::SMALL_GRID_MAX_B = 12 utterances -- 1 is the reference driver's call shape -- xt_api.hip), residual forms only (conv2 of a
 // block: no statistics whose order a tiling would change).  At batch 1 a launch is a handful of workgroups on an empty chip and its duration is ONE
@@ -1099,36 +964,34 @@ using B_L4   = ConvCfg<bf16_t, 256, 256, 1, 10, 17, 1, 4, 6, 1, 128, 9, 2, 0, tr
 // With tiles this short the weight ring matters as well (the product shapes fetch two k-steps ahead -- 168 registers at three workgroups per CU
 // leave no more; here the register file is free): twelve k-steps ahead 0.625 vs 0.645 ms per utterance; layer 4 in 2-row tiles (52 workgroups
 // x 288 MFMAs) 0.631 vs 0.645 (profiles/r05_latency_matrix.txt).
-using B_L3T  = ConvCfg<bf16_t, 128, 128, 1, 20,  3, 1, 4, 2, 1, 128, 9, 1, 16 + 12, true, LANES_DENSE, true>;
-using B_L4T  = ConvCfg<bf16_t, 256, 256, 1, 10,  2, 1, 4, 1, 1, 128, 9, 1, 16 + 12, true, LANES_DENSE, true>;
+using B_L3T = ConvCfg<bf16_t, 128, 128, 1, 20,  3, 1, 4, 2, 1, 128, 1, 12, true, LANES_DENSE, true>;
+using B_L4T = ConvCfg<bf16_t, 256, 256, 1, 10,  2, 1, 4, 1, 1, 128, 1, 12, true, LANES_DENSE, true>;
 
-using F_L1   = ConvCfg<float,  32,  32, 1, 80,  8, 4, 1, 5, 1, 32, 9, 0, 0, true>;
-using F_L1S  = ConvCfg<float,  32,  32, 1, 80,  8, 4, 1, 5, 1, 32, 1, 0, 0, true>;
-using F_L2A  = ConvCfg<float,  32,  64, 2, 80,  8, 2, 2, 5, 1, 16, 9, 0, 0, true>;
-using F_L2S  = ConvCfg<float,  32,  64, 2, 80,  8, 2, 2, 5, 1, 16, 1, 0, 0, true>;
-using F_L2   = ConvCfg<float,  64,  64, 1, 40,  8, 2, 2, 5, 1, 64, 9, 0, 0, true>;
-using F_L3A  = ConvCfg<float,  64, 128, 2, 40,  8, 1, 4, 5, 1, 32, 9>;
-using F_L3S  = ConvCfg<float,  64, 128, 2, 40,  8, 1, 4, 5, 1, 32, 1>;
-using F_L3   = ConvCfg<float, 128, 128, 1, 20,  8, 1, 4, 5, 1, 128, 9>;
-using F_L4A  = ConvCfg<float, 128, 256, 2, 20, 16, 1, 4, 5, 2, 32, 9>;
-using F_L4S  = ConvCfg<float, 128, 256, 2, 20, 16, 1, 4, 5, 2, 32, 1>;
-using F_L4   = ConvCfg<float, 256, 256, 1, 10, 16, 1, 4, 5, 2, 128, 9>;
+using F_L1  = ConvCfg<float,   32,  32, 1, 80,  8, 4, 1, 5, 1,  32, 0, 0, true>;
+using F_L2A = ConvCfg<float,   32,  64, 2, 80,  8, 2, 2, 5, 1,  16, 0, 0, true>;
+using F_L2  = ConvCfg<float,   64,  64, 1, 40,  8, 2, 2, 5, 1,  64, 0, 0, true>;
+using F_L3A = ConvCfg<float,   64, 128, 2, 40,  8, 1, 4, 5, 1,  32>;
+using F_L3  = ConvCfg<float,  128, 128, 1, 20,  8, 1, 4, 5, 1, 128>;
+using F_L4A = ConvCfg<float,  128, 256, 2, 20, 16, 1, 4, 5, 2,  32>;
+using F_L4  = ConvCfg<float,  256, 256, 1, 10, 16, 1, 4, 5, 2, 128>;
 using F_L3T = F_L3; using F_L4T = F_L4;   // the f32 parity path keeps its shapes at every batch size
 
 template <class C>
 static void fill_geom(ConvGeom& g) {
   g.cin = C::CIN; g.cout = C::COUT; g.stride = C::S; g.win = C::WIN; g.th = C::TH; g.wm = C::WM;
-  g.ck = C::CK; g.taps = C::TAPS; g.ks = C::KS; g.eb = C::EB; g.nw = C::NW; g.m16 = C::M16 ? 1 : 0;
+  g.ck = C::CK; g.taps = 9; g.ks = C::KS; g.eb = C::EB; g.nw = C::NW; g.m16 = C::M16 ? 1 : 0;
 }
 
-// the product's shapes: the trunk's eleven + the two small-grid tilings
+// the product's shapes (the trunk's seven + the two small-grid tilings) and the forms the forward launches each in: a layer's stride-2
+// first convolution is a conv1 (statistics), the small-grid tilings are conv2 only (residual)
 #define SK_CONV_CASES(X) \
-  X(CONV_L1, L1) X(CONV_L1S, L1S) X(CONV_L2A, L2A) X(CONV_L2S, L2S) X(CONV_L2, L2) X(CONV_L3A, L3A) \
-  X(CONV_L3S, L3S) X(CONV_L3, L3) X(CONV_L4A, L4A) X(CONV_L4S, L4S) X(CONV_L4, L4) X(CONV_L3T, L3T) X(CONV_L4T, L4T)
+  X(CONV_L1, L1, HAS_STATS | HAS_RESID) X(CONV_L2A, L2A, HAS_STATS) X(CONV_L2, L2, HAS_STATS | HAS_RESID) X(CONV_L3A, L3A, HAS_STATS) \
+  X(CONV_L3, L3, HAS_STATS | HAS_RESID) X(CONV_L4A, L4A, HAS_STATS) X(CONV_L4, L4, HAS_STATS | HAS_RESID)                           \
+  X(CONV_L3T, L3T, HAS_RESID) X(CONV_L4T, L4T, HAS_RESID)
 
 int conv_geom(int shape, int dtype, ConvGeom* g) {
   switch (shape) {
-#define X(id, name)                                              \
+#define X(id, name, forms)                                       \
   case id:                                                       \
     if (dtype == DT_BF16) fill_geom<B_##name>(*g); else fill_geom<F_##name>(*g); \
     return SK_OK;
@@ -1141,8 +1004,8 @@ int conv_geom(int shape, int dtype, ConvGeom* g) {
 
 int launch_conv(int shape, int dtype, const ConvArgs& a, hipStream_t st) {
   switch (shape) {
-#define X(id, name) \
-  case id: return dtype == DT_BF16 ? launch_cfg<B_##name>(a, st) : launch_cfg<F_##name>(a, st);
+#define X(id, name, forms) \
+  case id: return dtype == DT_BF16 ? launch_cfg<B_##name, forms>(a, st) : launch_cfg<F_##name, forms>(a, st);
     SK_CONV_CASES(X)
 #undef X
   }

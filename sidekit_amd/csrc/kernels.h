@@ -7,8 +7,10 @@ namespace sk {
 enum { DT_F32 = 0, DT_BF16 = 1, DT_F64 = 2, DT_I64 = 3 };
 
 // ---- conv3x3.hip ------------------------------------------------------------------------
+// The values are the xt_get_profile slot numbers and the sk_bench_conv shape numbers.  1, 3, 6, 9 were the layers' stand-alone 1x1 shortcut
+// convolutions; the shortcut runs in conv2's epilogue, so those slots stay unused (and zero).
 enum ConvShape {
-  CONV_L1 = 0, CONV_L1S, CONV_L2A, CONV_L2S, CONV_L2, CONV_L3A, CONV_L3S, CONV_L3, CONV_L4A, CONV_L4S, CONV_L4,
+  CONV_L1 = 0, CONV_L2A = 2, CONV_L2 = 4, CONV_L3A = 5, CONV_L3 = 7, CONV_L4A = 8, CONV_L4 = 10,
   CONV_NSHAPES,
   // small-grid forms of CONV_L3 / CONV_L4 (conv3x3.hip: 3- / 2-row tiles)
   CONV_L3T = 42, CONV_L4T = 43
@@ -41,14 +43,13 @@ struct ConvArgs {
   const void* shortcut;  // NHWC, same shape and type as out
   // -- residual mode of the FIRST block of a layer (gate != nullptr && sc_in != nullptr): the shortcut is not a stored
   //    tensor but bn(conv1x1_stride(x)) of the block input x (res_net.py:301-307), computed in this epilogue from x's
-  //    own rows: sc_in = x [B][sc_hin][WOUT*s][cin_x], weights sc_wpack / sc_scale / sc_shift
+  //    own rows: sc_in = x [B][sc_hin][WOUT*s][cin_x], weights sc_wpack (the shortcut BatchNorm's scale folded in), its shift sc_shift
   const void* sc_in; int sc_hin;
-  const void* sc_wpack; const float* sc_scale; const float* sc_shift;
+  const void* sc_wpack; const float* sc_shift;
   const void* zeros;   // >= 16 zero bytes in device memory (source of the conv zero padding)
   Lens lens;           // feature frames per utterance
   int halvings_in;     // stride-2 stages between the features and this conv's input
   int B, Hin, Hout;    // allocated rows of in / out
-  int relu;
   int persist_cap;     // > 0: at most this many workgroups per CU for the persistent (weight-resident) shapes, see launch_cfg
   unsigned long long* stamps;  // diagnostics only: per-workgroup s_memtime stamps at the phase boundaries (8 per block), or nullptr
   int dbg;             // diagnostics only (sk_bench_conv): bit0 skip stores, bit1 skip MFMA loop, bit2 skip staging

@@ -44,12 +44,13 @@ struct ConvLayer {
   ConvGeom g;
 };
 struct Block {
-  ConvLayer c1, c2, sc;
-  bool has_sc = false;
+  ConvLayer c1, c2;
+  bool has_sc = false;   // first block of a layer: 1x1 shortcut convolution + BatchNorm, evaluated in conv2's epilogue
   float* se_w1 = nullptr;
   float* se_w2 = nullptr;
   void* w2t = nullptr;   // conv2 weights as the MFMA consumes them, [tap][ci][co] bf16 / f32 (SE gate pre-computation)
   void* sc_wfold = nullptr;   // shortcut 1x1 weights with the shortcut BN scale folded in (row co times scale[co]), fragment order
+  float* sc_shift = nullptr;  // the shortcut BN shift
   int C, li;
 };
 
@@ -477,7 +478,6 @@ static int finalize_half(xt_handle* h) {
   SK_TRY(upload_f(h, sh, &h->stem_shift));
   static const int first_shape[4] = {CONV_L1, CONV_L2A, CONV_L3A, CONV_L4A};
   static const int rest_shape[4] = {CONV_L1, CONV_L2, CONV_L3, CONV_L4};
-  static const int sc_shape[4] = {CONV_L1S, CONV_L2S, CONV_L3S, CONV_L4S};
   for (int li = 0; li < 4; ++li)
     for (int bi = 0; bi < HALF_BLOCKS[li]; ++bi) {
       const std::string p = sn + ".layer" + std::to_string(li + 1) + "." + std::to_string(bi);
@@ -487,20 +487,22 @@ static int finalize_half(xt_handle* h) {
       SK_TRY(make_conv(h, b.c2, rest_shape[li], p + ".conv2.weight", p + ".bn2"));
       b.has_sc = bi == 0;
       if (b.has_sc) {
-        SK_TRY(make_conv(h, b.sc, sc_shape[li], p + ".shortcut.0.weight", p + ".shortcut.1"));
         // in-place shortcut (conv2's epilogue): bn_s(conv1x1(x)) = (scale_s * W) x + shift_s accumulates straight into
         // conv2's (already gate- and BN-scaled) accumulators, so the BN scale of the shortcut goes into its weights
-        const HostTensor& w = h->tensors[p + ".shortcut.0.weight"];
+        const std::string wkey = p + ".shortcut.0.weight";
+        const HostTensor& w = h->tensors[wkey];
+        const int cin_x = li == 0 ? b.C : b.C / 2;   // the block input's channels
+        SK_CHECK(w.shape[0] == b.C && w.shape[1] == cin_x && w.shape[2] * w.shape[3] == 1, SK_ESHAPE, "conv %s: weight/shape table mismatch", wkey.c_str());
         std::vector<float> scs, shs;
         fold_bn(h, p + ".shortcut.1", scs, shs);
         std::vector<float> wf(w.data.size());
-        const size_t per = wf.size() / b.sc.g.cout;
-        for (size_t i = 0; i < wf.size(); ++i) wf[i] = w.data[i] * scs[i / per];
-        ConvGeom gs = b.sc.g;           // the fragments conv2's epilogue multiplies with: conv2's MFMA shape, not the stand-alone 1x1 kernel's
-        gs.m16 = b.c2.g.m16;
+        for (size_t i = 0; i < wf.size(); ++i) wf[i] = w.data[i] * scs[i / cin_x];
+        ConvGeom gs = b.c2.g;           // the fragments conv2's epilogue multiplies with: conv2's element type and MFMA shape, one tap, one channel chunk
+        gs.cin = cin_x; gs.cout = b.C; gs.taps = 1; gs.ck = cin_x; gs.ks = cin_x * gs.eb / 32;
         std::vector<unsigned char> packed(conv_pack_bytes(gs));
-        conv_pack_weights(gs, wf.data(), (int)(w.shape[2] * w.shape[3]), packed.data());
+        conv_pack_weights(gs, wf.data(), 1, packed.data());
         SK_TRY(upload(h, packed.data(), packed.size(), &b.sc_wfold));
+        SK_TRY(upload_f(h, shs, &b.sc_shift));
       }
       {
         const auto& w2 = T(h, p + ".conv2.weight");  // [co][ci][3][3]
@@ -760,7 +762,7 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
     // conv1 + bn1 + relu -> O1, leaving the sums the block's SE gate is derived from
     a.in = X; a.wpack = b.c1.wpack; a.scale = b.c1.scale; a.shift = b.c1.shift; a.out = O1;
     a.se_part = (float*)ln.ws[WS_SE].p; a.col_part = (float*)ln.ws[WS_COL].p; a.edge = (float*)ln.ws[WS_EDGE].p;
-    a.halvings_in = lin; a.Hin = Hl[lin]; a.Hout = Hl[li]; a.relu = 1;
+    a.halvings_in = lin; a.Hin = Hl[lin]; a.Hout = Hl[li];
     // SE gate, known before conv2 runs (linearity of the plane mean in O1): its own launch, one workgroup per utterance.  (Round 4 built
     // the alternative the round-3 verdict asked to have measured -- conv1's last workgroup of an utterance computes the gate in its
     // tail, an agent-scope release + ticket per workgroup -- and dropped it: at batch 256 every workgroup's release made the step
@@ -781,10 +783,10 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
     // conv2 + bn2, * gate, + shortcut, relu -> O2 (the block output)
     a.in = O1; a.wpack = b.c2.wpack; a.scale = b.c2.scale; a.shift = b.c2.shift; a.out = O2;
     a.se_part = nullptr; a.col_part = nullptr; a.edge = nullptr; a.gate = (const float*)ln.ws[WS_GATE].p; a.shortcut = X;
-    a.halvings_in = li; a.Hin = Hl[li]; a.Hout = Hl[li]; a.relu = 0;
+    a.halvings_in = li; a.Hin = Hl[li]; a.Hout = Hl[li];
     if (first) {   // first block of a layer: conv2's epilogue evaluates the 1x1 shortcut conv itself from the block input (no shortcut tensor)
       a.shortcut = nullptr; a.sc_in = X; a.sc_hin = Hl[lin];
-      a.sc_wpack = b.sc_wfold; a.sc_scale = b.sc.scale; a.sc_shift = b.sc.shift;
+      a.sc_wpack = b.sc_wfold; a.sc_shift = b.sc_shift;
     }
     { ProfScope ps(h, b.c2.shape, st); SK_TRY(launch_conv(c2shape, dt, a, st)); }
     std::swap(X, O2);
@@ -1363,15 +1365,14 @@ int sk_bench_conv(int32_t shape, int32_t dtype, int32_t B, int32_t T, int32_t it
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   a.in = in; a.wpack = w; a.scale = sc; a.shift = sh; a.out = out; a.se_part = nullptr; a.zeros = zeros;
-  a.lens = Lens{nullptr, T}; a.halvings_in = 0; a.B = B; a.Hin = hin; a.Hout = hout; a.relu = 1; a.dbg = (variant & 7) | ((variant & 32) ? 8 : 0) | ((variant & 64) ? 16 : 0);
+  a.lens = Lens{nullptr, T}; a.halvings_in = 0; a.B = B; a.Hin = hin; a.Hout = hout; a.dbg = (variant & 7) | ((variant & 32) ? 8 : 0) | ((variant & 64) ? 16 : 0);
   const int nblk = B * cdiv(hout, g.th);
   unsigned long long* stamps = nullptr;
   float *gate = nullptr; void* scut = nullptr; float *colp = nullptr, *edge = nullptr;
-  if (variant & 8) {   // statistics-mode epilogue
+  if (!(variant & 16)) {   // statistics-mode epilogue (bit 3 is implied: a convolution runs in the statistics or the residual form)
     SK_TRY(mem.alloc(&colp, (size_t)nblk * 2 * g.cout * 4)); SK_TRY(mem.alloc(&edge, (size_t)B * 6 * g.cout * 4));
     a.se_part = se; a.col_part = colp; a.edge = edge;
-  }
-  if (variant & 16) {  // residual-mode epilogue
+  } else {  // residual-mode epilogue
     SK_TRY(mem.alloc(&gate, (size_t)B * g.cout * 4)); SK_TRY(mem.alloc(&scut, out_b));
     {
       std::vector<float> gv((size_t)B * g.cout, 0.5f);
