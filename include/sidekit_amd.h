@@ -214,6 +214,33 @@ int sc_topk_stats(const float* d_scores, int32_t n_rows, int32_t n_cols, int32_t
 int sc_snorm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t,
                    const float* d_std_t, void* stream);
 
+/* ---- PLDA training: sidekit.factor_analyser.FactorAnalyser.plda (sidekit/factor_analyser.py:830-932) ----------------------------
+ * The device half of the EM: everything with an utterance (N) or class (C) dimension, in float64 on the f64 matrix cores; the D x D and
+ * rank x rank algebra stays on the host (sidekit_amd/factor_analyser.py).  X is XT_F32 or XT_F64 and is widened in the load.  No
+ * floating-point atomics: partial sums go through the sc_* workspace (sc_release_workspace) and are added in a fixed order, so the
+ * result's bits are a function of the arguments alone. */
+
+/* StatServer.sum_stat_per_model (sidekit/statserver.py:1335-1355): S[c][:] = sum of the rows of X (N x D) that belong to class c.
+ * The class index arrives as a CSR built by the host: d_rows (N row numbers, grouped by class, ascending inside a class) is cut into
+ * n_slices slices d_rows[d_slice_off[s] .. d_slice_off[s + 1]) that never straddle a class, and class c owns the slices
+ * [d_class_slice_off[c], d_class_slice_off[c + 1]).  d_S: C x D; d_colsum (D column sums of X, i.e. N * mean) may be NULL. */
+int sc_class_sums(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const int32_t* d_rows, const int32_t* d_slice_off,
+                  int32_t n_slices, const int32_t* d_class_slice_off, int32_t C, double* d_S, double* d_colsum, void* stream);
+
+/* G[m][n] = sum_k w[k] (A[k][m] - ca[m]) (B[k][n] - cb[n]),  A: K x M, B: K x Nn row-major, both `dtype` (XT_F32 / XT_F64), G: M x Nn
+ * float64; d_w, d_ca, d_cb may each be NULL (weight 1, centre 0).  K is the long dimension: it is cut into row slabs whose partial
+ * tiles are added in slab order.  With A = B = X and ca = cb = mean this is the total scatter of the x-vectors. */
+int sc_gemm_tn(const void* d_A, const void* d_B, int32_t dtype, int64_t K, int32_t M, int32_t Nn, const double* d_w, const double* d_ca,
+               const double* d_cb, double* d_G, void* stream);
+
+/* C = epilogue(alpha * A . B),  A: M x K, B: K x N, C: M x N, float64 row-major; d_rowv (M) and d_colv (N) come together or not at all.
+ *   SC_EPI_RANK1:     C[m][n] = alpha * (A B)[m][n] - rowv[m] * colv[n]        (whitened, centred class sums: (S - n mu') W)
+ *   SC_EPI_POSTERIOR: C[m][n] = alpha * (A B)[m][n] / (1 + rowv[m] * colv[n])  (the E-step's posterior scale in the eigenbasis of F'F) */
+#define SC_EPI_RANK1 0
+#define SC_EPI_POSTERIOR 1
+int sc_dgemm_nn(const double* d_A, const double* d_B, int32_t M, int32_t N, int32_t K, double alpha, const double* d_rowv,
+                const double* d_colv, int32_t epilogue, double* d_C, void* stream);
+
 /* ---- EER support (host code, no GPU needed) --------------------------------------------------- */
 
 /* sidekit.bosaris.detplot.pavx (sidekit/bosaris/detplot.py:289-351): isotonic (non-decreasing) fit of y.

@@ -1,7 +1,7 @@
 """sidekit_amd -- MI355X-native x-vector extraction and trial scoring behind SIDEKIT's Python surface.
 
 Sub-modules mirror the reference package layout for the hot path only:
-``sidekit_amd.nnet.xvector.Xtractor``, ``sidekit_amd.iv_scoring``, ``sidekit_amd.statserver``,
+``sidekit_amd.nnet.xvector.Xtractor``, ``sidekit_amd.iv_scoring``, ``sidekit_amd.factor_analyser``, ``sidekit_amd.statserver``,
 ``sidekit_amd.bosaris``, ``sidekit_amd.score_normalization``, ``sidekit_amd.sidekit_io``.
 ``install_as_sidekit()`` registers them under the ``sidekit`` names so that reference-style drivers
 (``extract_xvectors.py``, scoring scripts) import them unchanged.
@@ -25,12 +25,13 @@ _LAZY = {
     "StatServer": "statserver",
     "cosine_scoring": "iv_scoring", "PLDA_scoring": "iv_scoring", "fast_PLDA_scoring": "iv_scoring", "full_PLDA_scoring": "iv_scoring",
     "mahalanobis_scoring": "iv_scoring", "two_covariance_scoring": "iv_scoring",
+    "FactorAnalyser": "factor_analyser",
     "asnorm": "score_normalization",
     "write_matrix_hdf5": "sidekit_io", "read_plda_hdf5": "sidekit_io", "write_plda_hdf5": "sidekit_io",
 }
 
 # every module of the mirror, by its reference name
-SUBMODULES = ("bosaris", "bosaris.idmap", "bosaris.ndx", "bosaris.key", "bosaris.scores", "bosaris.detplot", "statserver", "iv_scoring",
+SUBMODULES = ("bosaris", "bosaris.idmap", "bosaris.ndx", "bosaris.key", "bosaris.scores", "bosaris.detplot", "statserver", "iv_scoring", "factor_analyser",
               "score_normalization", "sidekit_io", "nnet", "nnet.xvector", "nnet.preprocessor")
 
 

@@ -24,6 +24,7 @@ SK_OK, SK_EARG, SK_ESHAPE, SK_EHIP, SK_EWORKSPACE, SK_ESTATE = 0, -1, -2, -3, -4
 XT_ARCH_HALFRESNET34, XT_ARCH_TDNN = 0, 1
 XT_F32, XT_BF16, XT_F64, XT_I64, XT_I16 = 0, 1, 2, 3, 4
 XT_LOSS_AAM, XT_LOSS_CCE = 0, 1
+SC_EPI_RANK1, SC_EPI_POSTERIOR = 0, 1
 XT_PROF_SLOTS = 16
 PROF_NAMES = ("conv_L1", "conv_L1S", "conv_L2A", "conv_L2S", "conv_L2", "conv_L3A", "conv_L3S", "conv_L3", "conv_L4A", "conv_L4S",
               "conv_L4", "frontend", "stem", "se_residual", "pool_tail", "tdnn")
@@ -70,6 +71,9 @@ SIGNATURES = {
     "sc_cosine_trials": (ctypes.c_int, [_P, _P, _I32, _P, _P, _I64, _P, _P]),
     "sc_topk_stats": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
     "sc_snorm_apply": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "sc_class_sums": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P]),
+    "sc_gemm_tn": (ctypes.c_int, [_P, _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    "sc_dgemm_nn": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _F64, _P, _P, _I32, _P, _P]),
     "sk_bench_conv": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_F64)]),
     "sk_pavx": (ctypes.c_int, [_P, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
     "sk_rocch_vertices": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _P]),

@@ -17,8 +17,9 @@ jitter and white noise (a batch is generated on the device with seed ``1000 + in
 structure for the randomly initialised extractor to separate speakers with a non-trivial EER.  The PLDA parameters are inputs
 to the scoring path: ``--plda FILE`` reads ``(mu, F, Sigma)`` from a SIDEKIT PLDA HDF5 file (``sidekit_io.read_plda_hdf5``) or from
 an ``.npz`` with those three arrays (``tests/golden/config5.npz`` holds the ones the reference's ``FactorAnalyser.plda`` trained);
-without it a moment estimate (between / within speaker covariance of the training x-vectors) stands in, since PLDA *training*
-proper (``sidekit/factor_analyser.py:830-932``) is out of scope.
+without it they are estimated from the training x-vectors: ``--plda-train moments`` (the default) takes a moment estimate (between /
+within speaker covariance, on the host), ``--plda-train em`` runs PLDA training proper (``sidekit/factor_analyser.py:830-932``) with
+``factor_analyser.plda_device`` on the gathered device tensor -- the x-vectors make no host round trip.  ``--plda FILE`` wins over both.
 
 ``main(argv, model=None, scoring=None, keep=None)``: ``keep`` (a dict) receives the gathered x-vectors (``"xv"``, device tensor), the labels and
 rank 0's two score matrices -- for tests that compare two runs; the model and the module that scores (``cosine_matrix_device``, ``plda_matrix_device``,
@@ -111,6 +112,8 @@ def main(argv=None, model=None, scoring=None, keep=None):
     ap.add_argument("--hist-bins", type=int, default=None, help="bins of the all-pairs histograms: 8192 (default, one pass) or a multiple of 8190 (that many passes / 8190)")
     ap.add_argument("--seed", type=int, default=0, help="corpus seed: another draw of speaker labels, phases, amplitude jitter and noise for the same speaker table")
     ap.add_argument("--plda", default=None, help="PLDA (mu, F, Sigma): SIDEKIT HDF5 or .npz; default: moment estimate from the corpus")
+    ap.add_argument("--plda-train", default="moments", choices=["moments", "em"],
+                    help="without --plda: moment estimate on the host (default) or EM training on the device (factor_analyser.plda_device, 10 iterations)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL over xGMI; gloo for CPU rehearsals")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu only with an injected model / scoring module")
     args = ap.parse_args(argv)
@@ -179,6 +182,9 @@ def main(argv=None, model=None, scoring=None, keep=None):
     if args.plda:
         mu, F, Sigma = load_plda(args.plda)
         assert mu.shape[0] == xv.shape[1], "PLDA dimension differs from the x-vectors'"
+    elif args.plda_train == "em":
+        from ..factor_analyser import plda_device
+        mu, F, Sigma = plda_device(train, labels[2 * n:], args.plda_rank)                 # identical on every rank: same data, fixed summation order
     else:
         mu, F, Sigma = plda_moments(train.cpu().numpy(), labels[2 * n:], args.plda_rank)  # identical on every rank (same gathered data)
     Phi, Psi, cst = iv_scoring.plda_parameters(mu, F, Sigma)
@@ -190,7 +196,7 @@ def main(argv=None, model=None, scoring=None, keep=None):
     t_plda = time.perf_counter() - t0
     out = {"ranks": world, "utterances": N, "x_vectors_per_s": N / t_extract, "extract_s": t_extract, "all_gather_s": t_gather,
            "trials": n * n, "cosine_score_s": t_cos, "plda_score_s": t_plda, "dtype": args.dtype,
-           "plda": args.plda or "moment estimate", "backend": dist.get_backend() if dist.is_initialized() else None,
+           "plda": args.plda or ("moment estimate" if args.plda_train == "moments" else "EM on the device"), "backend": dist.get_backend() if dist.is_initialized() else None,
            "xv_finite": bool(torch.isfinite(xv).all()), "xv_norm_max_dev": float((norms - 1.0).abs().max()),
            "gathered_own_block_ok": gathered_own_block_ok}
     if args.all_pairs:
@@ -216,7 +222,7 @@ def main(argv=None, model=None, scoring=None, keep=None):
         counts = counts.cpu().numpy()
         out.update(all_pairs=int(counts.sum()), all_pairs_s=t_hist, all_pairs_eer=float(eer_from_histograms(counts[0], counts[1])))
     if keep is not None:
-        keep.update(xv=xv, labels=labels, tar=tar)
+        keep.update(xv=xv, labels=labels, tar=tar, plda=(mu, F, Sigma))
     if rank == 0:
         for name, rows in (("cosine", cos_rows), ("plda", plda_rows)):
             s = rows.cpu().numpy().astype(float)

@@ -1,0 +1,145 @@
+// The f64 MFMA GEMM tile shared by trial scoring (scoring.hip) and PLDA training (plda_train.hip).
+#pragma once
+#include "common.h"
+
+namespace sk {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+// f64 GEMM tile on the matrix cores, the core of fast / full PLDA scoring and of PLDA training.
+//   v_mfma_f64_16x16x4_f64: A: lane l holds A[l & 15][l >> 4], B: B[l >> 4][l & 15], D: four doubles per lane at row (l >> 4) + 4 * reg,
+//   col l & 15 (the f64 map, which differs from the f32 one); 64 matrix-pipe cycles each (78.6 TFLOP/s = 32 FLOP / clk / SIMD).
+// Four waves in a 2 x 2 grid, each WT x WT MFMA tiles: WT = 2 -> 64 x 64 per workgroup (small trial sets: enough workgroups to fill 256
+// CUs), WT = 4 -> 128 x 128 (half the operand traffic per FLOP, 64 accumulator doubles per lane, two workgroups per CU).  Operands are
+// staged through LDS as [row][k] with a 17-double row stride (ds_read_b64 fragment reads: 16 rows x 2 k per half-wave land on 32
+// different bank pairs but one), the next k-tile's operands are fetched into registers (16-byte loads) while this one is multiplied.
+//   B_KN = false: B is [N][K] (C = A . B^T);  B_KN = true: B is [K][N] (C = A . B)
+//   A_KM = false: A is [M][K];  A_KM = true: A is [K][M] (C = A^T . B, the "TN" product of PLDA training: K is the long dimension)
+// The A_KM form reads float32 or float64 operands (TA, TB; widened in the load) and can weight and centre them on the way into LDS:
+//   C[m][n] = sum_k w[k] (A[k][m] - ca[m]) (B[k][n] - cb[n]),   w, ca, cb optional; cs = 2 * T doubles of LDS for the two centres.
+constexpr int DK = 16, DLD = DK + 1;
+
+template <typename T> struct pair_of;
+template <> struct pair_of<double> { typedef double2 type; };
+template <> struct pair_of<float> { typedef float2 type; };
+
+// elements i, i + 1 of a row of n (zero beyond it); vec: the pair may be read with one load
+template <typename T>
+__device__ inline double2 fetch_pair(const T* __restrict__ src, bool vec, int i, int n) {
+  double2 v = {0.0, 0.0};
+  if (vec && i + 1 < n) {
+    const typename pair_of<T>::type p = *reinterpret_cast<const typename pair_of<T>::type*>(src);
+    v.x = (double)p.x; v.y = (double)p.y;
+  } else {
+    if (i < n) v.x = (double)src[0];
+    if (i + 1 < n) v.y = (double)src[1];
+  }
+  return v;
+}
+
+template <int WT, bool B_KN, bool A_KM = false, typename TA = double, typename TB = double>
+__device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict__ B, int M, int N, int K, int m0, int n0,
+                                  double* As, double* Bs, f64x4 (&acc)[WT][WT], const double* __restrict__ w = nullptr,
+                                  const double* __restrict__ ca = nullptr, const double* __restrict__ cb = nullptr, double* cs = nullptr) {
+  static_assert(!A_KM || B_KN, "the A [K][M] form comes with B [K][N]");
+  static_assert(A_KM || (std::is_same<TA, double>::value && std::is_same<TB, double>::value), "float32 operands: A_KM form only");
+  constexpr int T = 32 * WT;            // workgroup tile edge
+  constexpr int PA = T * DK / 2 / 256;  // double pairs per thread and operand
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const bool vec_a = ((A_KM ? M : K) & 1) == 0 && (reinterpret_cast<size_t>(A) & (2 * sizeof(TA) - 1)) == 0;
+  const bool vec_b = ((B_KN ? N : K) & 1) == 0 && (reinterpret_cast<size_t>(B) & (2 * sizeof(TB) - 1)) == 0;
+  double2 ra[PA], rb[PA];
+  double rw[A_KM ? PA : 1];   // A_KM: the weight of each fetched k-row, 0 beyond K (which also zeroes the centred padding)
+  if constexpr (A_KM) {
+    for (int i = tid; i < 2 * T; i += 256) {
+      const int j = i < T ? m0 + i : n0 + i - T;
+      cs[i] = i < T ? (ca && j < M ? ca[j] : 0.0) : (cb && j < N ? cb[j] : 0.0);
+    }
+  }
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < PA; ++q) {
+      const int idx = tid + 256 * q;
+      if constexpr (!A_KM) {  // A: T rows x 8 pairs along k
+        const int row = idx >> 3, kp = (idx & 7) * 2, m = m0 + row, k = k0 + kp;
+        double2 v = {0.0, 0.0};
+        if (m < M) {
+          const double* src = A + (long)m * K + k;
+          if (vec_a && k + 1 < K) v = *reinterpret_cast<const double2*>(src);
+          else { if (k < K) v.x = src[0]; if (k + 1 < K) v.y = src[1]; }
+        }
+        ra[q] = v;
+      } else {  // A [K][M]: 16 k x T/2 pairs along m
+        const int kk = idx / (T / 2), mp = (idx % (T / 2)) * 2, m = m0 + mp, k = k0 + kk;
+        double2 v = {0.0, 0.0};
+        if (k < K) v = fetch_pair(A + (long)k * M + m, vec_a, m, M);
+        ra[q] = v;
+        rw[q] = k < K ? (w ? w[k] : 1.0) : 0.0;
+      }
+      if constexpr (!B_KN) {
+        const int row = idx >> 3, kp = (idx & 7) * 2, n = n0 + row, k = k0 + kp;
+        double2 v = {0.0, 0.0};
+        if (n < N) {
+          const double* src = B + (long)n * K + k;
+          if (vec_b && k + 1 < K) v = *reinterpret_cast<const double2*>(src);
+          else { if (k < K) v.x = src[0]; if (k + 1 < K) v.y = src[1]; }
+        }
+        rb[q] = v;
+      } else if constexpr (!A_KM) {  // B [K][N]: 16 k x T/2 pairs along n
+        const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2, n = n0 + np, k = k0 + kk;
+        double2 v = {0.0, 0.0};
+        if (k < K) {
+          const double* src = B + (long)k * N + n;
+          if (vec_b && n + 1 < N) v = *reinterpret_cast<const double2*>(src);
+          else { if (n < N) v.x = src[0]; if (n + 1 < N) v.y = src[1]; }
+        }
+        rb[q] = v;
+      } else {
+        const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2, n = n0 + np, k = k0 + kk;
+        double2 v = {0.0, 0.0};
+        if (k < K) v = fetch_pair(B + (long)k * N + n, vec_b, n, N);
+        rb[q] = v;
+      }
+    }
+  };
+  auto stage = [&]() {
+#pragma unroll
+    for (int q = 0; q < PA; ++q) {
+      const int idx = tid + 256 * q;
+      const int row = idx >> 3, kp = (idx & 7) * 2;
+      const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2;
+      if constexpr (!A_KM) { As[row * DLD + kp] = ra[q].x; As[row * DLD + kp + 1] = ra[q].y; }
+      else { As[np * DLD + kk] = (ra[q].x - cs[np]) * rw[q]; As[(np + 1) * DLD + kk] = (ra[q].y - cs[np + 1]) * rw[q]; }
+      if constexpr (!B_KN) { Bs[row * DLD + kp] = rb[q].x; Bs[row * DLD + kp + 1] = rb[q].y; }
+      else if constexpr (!A_KM) { Bs[np * DLD + kk] = rb[q].x; Bs[(np + 1) * DLD + kk] = rb[q].y; }
+      else { Bs[np * DLD + kk] = rb[q].x - cs[T + np]; Bs[(np + 1) * DLD + kk] = rb[q].y - cs[T + np + 1]; }
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < WT; ++i)
+#pragma unroll
+    for (int j = 0; j < WT; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
+  fetch(0);
+  for (int k0 = 0; k0 < K; k0 += DK) {
+    __syncthreads();   // every wave is done reading the previous k-tile (and, the first time, the centres are in LDS)
+    stage();
+    __syncthreads();
+    if (k0 + DK < K) fetch(k0 + DK);
+#pragma unroll
+    for (int kk = 0; kk < DK; kk += 4) {
+      double a[WT], b[WT];
+#pragma unroll
+      for (int i = 0; i < WT; ++i) {
+        a[i] = As[(wm * 16 * WT + i * 16 + lr) * DLD + kk + lk];
+        b[i] = Bs[(wn * 16 * WT + i * 16 + lr) * DLD + kk + lk];
+      }
+#pragma unroll
+      for (int i = 0; i < WT; ++i)
+#pragma unroll
+        for (int j = 0; j < WT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+  }
+}
+
+}  // namespace sk

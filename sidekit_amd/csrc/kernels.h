@@ -1,5 +1,7 @@
 // Internal kernel-launcher interface of libsidekit_amd (not part of the C ABI).
 #pragma once
+#include <mutex>
+
 #include "common.h"
 
 namespace sk {
@@ -159,5 +161,11 @@ int launch_cmvn(float* x, long ld, int D, RowSpan rs, float eps, int B, hipStrea
 int launch_l2norm(const float* x, float* out, int D, int B, hipStream_t s);
 // x / max(||x||_2, eps) per row (F.normalize)
 int launch_normalize_rows(const float* x, float* out, int D, int B, float eps, hipStream_t s);
+
+// ---- scoring.hip --------------------------------------------------------------------------
+// The sc_* workspace: one buffer per (device, stream), grown on demand, freed by sc_release_workspace().  The caller holds
+// g_plda_mu from the lookup until the kernels that use the buffer are enqueued.
+extern std::mutex g_plda_mu;
+int plda_workspace_locked(hipStream_t st, size_t bytes, void** out);
 
 }  // namespace sk

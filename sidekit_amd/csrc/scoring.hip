@@ -13,105 +13,10 @@
 #include <utility>
 
 #include "../../include/sidekit_amd.h"
+#include "dgemm_tile.h"
 #include "kernels.h"
 
 namespace sk {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// f64 GEMM tile on the matrix cores, the core of fast / full PLDA scoring.
-//   v_mfma_f64_16x16x4_f64: A: lane l holds A[l & 15][l >> 4], B: B[l >> 4][l & 15], D: four doubles per lane at row (l >> 4) + 4 * reg,
-//   col l & 15 (the f64 map, which differs from the f32 one); 64 matrix-pipe cycles each (78.6 TFLOP/s = 32 FLOP / clk / SIMD).
-// Four waves in a 2 x 2 grid, each WT x WT MFMA tiles: WT = 2 -> 64 x 64 per workgroup (small trial sets: enough workgroups to fill 256
-// CUs), WT = 4 -> 128 x 128 (half the operand traffic per FLOP, 64 accumulator doubles per lane, two workgroups per CU).  Operands are
-// staged through LDS as [row][k] with a 17-double row stride (ds_read_b64 fragment reads: 16 rows x 2 k per half-wave land on 32
-// different bank pairs but one), the next k-tile's operands are fetched into registers (16-byte loads) while this one is multiplied.
-//   B_KN = false: B is [N][K] (C = A . B^T);  B_KN = true: B is [K][N] (C = A . B)
-constexpr int DK = 16, DLD = DK + 1;
-
-template <int WT, bool B_KN>
-__device__ inline void dgemm_tile(const double* __restrict__ A, const double* __restrict__ B, int M, int N, int K, int m0, int n0,
-                                  double* As, double* Bs, f64x4 (&acc)[WT][WT]) {
-  constexpr int T = 32 * WT;            // workgroup tile edge
-  constexpr int PA = T * DK / 2 / 256;  // double pairs per thread and operand
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
-  const bool vec_a = (K & 1) == 0 && (reinterpret_cast<size_t>(A) & 15) == 0;
-  const bool vec_b = ((B_KN ? N : K) & 1) == 0 && (reinterpret_cast<size_t>(B) & 15) == 0;
-  double2 ra[PA], rb[PA];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < PA; ++q) {
-      const int idx = tid + 256 * q;
-      {  // A: T rows x 8 pairs along k
-        const int row = idx >> 3, kp = (idx & 7) * 2, m = m0 + row, k = k0 + kp;
-        double2 v = {0.0, 0.0};
-        if (m < M) {
-          const double* src = A + (long)m * K + k;
-          if (vec_a && k + 1 < K) v = *reinterpret_cast<const double2*>(src);
-          else { if (k < K) v.x = src[0]; if (k + 1 < K) v.y = src[1]; }
-        }
-        ra[q] = v;
-      }
-      if constexpr (!B_KN) {
-        const int row = idx >> 3, kp = (idx & 7) * 2, n = n0 + row, k = k0 + kp;
-        double2 v = {0.0, 0.0};
-        if (n < N) {
-          const double* src = B + (long)n * K + k;
-          if (vec_b && k + 1 < K) v = *reinterpret_cast<const double2*>(src);
-          else { if (k < K) v.x = src[0]; if (k + 1 < K) v.y = src[1]; }
-        }
-        rb[q] = v;
-      } else {  // B [K][N]: 16 k x T/2 pairs along n
-        const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2, n = n0 + np, k = k0 + kk;
-        double2 v = {0.0, 0.0};
-        if (k < K) {
-          const double* src = B + (long)k * N + n;
-          if (vec_b && n + 1 < N) v = *reinterpret_cast<const double2*>(src);
-          else { if (n < N) v.x = src[0]; if (n + 1 < N) v.y = src[1]; }
-        }
-        rb[q] = v;
-      }
-    }
-  };
-  auto stage = [&]() {
-#pragma unroll
-    for (int q = 0; q < PA; ++q) {
-      const int idx = tid + 256 * q;
-      const int row = idx >> 3, kp = (idx & 7) * 2;
-      As[row * DLD + kp] = ra[q].x; As[row * DLD + kp + 1] = ra[q].y;
-      if constexpr (!B_KN) { Bs[row * DLD + kp] = rb[q].x; Bs[row * DLD + kp + 1] = rb[q].y; }
-      else {
-        const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2;
-        Bs[np * DLD + kk] = rb[q].x; Bs[(np + 1) * DLD + kk] = rb[q].y;
-      }
-    }
-  };
-#pragma unroll
-  for (int i = 0; i < WT; ++i)
-#pragma unroll
-    for (int j = 0; j < WT; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
-  fetch(0);
-  for (int k0 = 0; k0 < K; k0 += DK) {
-    __syncthreads();   // every wave is done reading the previous k-tile
-    stage();
-    __syncthreads();
-    if (k0 + DK < K) fetch(k0 + DK);
-#pragma unroll
-    for (int kk = 0; kk < DK; kk += 4) {
-      double a[WT], b[WT];
-#pragma unroll
-      for (int i = 0; i < WT; ++i) {
-        a[i] = As[(wm * 16 * WT + i * 16 + lr) * DLD + kk + lk];
-        b[i] = Bs[(wn * 16 * WT + i * 16 + lr) * DLD + kk + lk];
-      }
-#pragma unroll
-      for (int i = 0; i < WT; ++i)
-#pragma unroll
-        for (int j = 0; j < WT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  }
-}
 
 // C[m][n] = alpha * (sum_k A[m][k] B[n][k] + rowterm(m) + colterm(n) + cst); the two terms arrive as `nparts` partial sums each
 // (rowterm(m) = sum_p rowpart[p * M + m], fixed order), which is how plda_prep_kernel leaves the quadratic forms.
@@ -418,7 +323,7 @@ __global__ void snorm_apply_kernel(float* __restrict__ S, int ne, int nt, const 
   S[i] = 0.5f * ((v - me[r]) / se[r]) + 0.5f * ((v - mt[c]) / st[c]);
 }
 
-// ---- workspace of sc_plda_fast: E . Psi (Ne x D) and the partial quadratic forms, cached per (device, stream) so that a call
+// ---- workspace of sc_plda_fast (E . Psi (Ne x D) and the partial quadratic forms) and of the PLDA training calls (plda_train.hip), cached per (device, stream) so that a call
 // allocates nothing in the steady state (three hipMallocAsync / hipFreeAsync pairs per call were most of a 1000 x 1000 scoring).  A
 // stream's calls are ordered, so reuse needs no further synchronisation; growth waits for that stream's earlier calls first.  The
 // caller holds g_plda_mu from the lookup until its two kernels are enqueued (with the lock dropped in between, a second host
@@ -426,10 +331,10 @@ __global__ void snorm_apply_kernel(float* __restrict__ S, int ne, int nt, const 
 // sc_release_workspace() (called by the Python shim at interpreter exit and by tests); a stream handle the runtime recycles finds the
 // old entry, which is harmless for the same reason reuse is: work on one stream handle is ordered.
 struct PldaWs { void* p = nullptr; size_t bytes = 0; };
-static std::mutex g_plda_mu;
+std::mutex g_plda_mu;
 static std::map<std::pair<int, hipStream_t>, PldaWs> g_plda_ws;
 
-static int plda_workspace_locked(hipStream_t st, size_t bytes, void** out) {
+int plda_workspace_locked(hipStream_t st, size_t bytes, void** out) {
   int dev = 0;
   SK_HIP(hipGetDevice(&dev));
   PldaWs& w = g_plda_ws[{dev, st}];

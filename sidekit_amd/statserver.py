@@ -3,7 +3,7 @@
 Mirrors the attributes (``modelset, segset, start, stop, stat0, stat1``; ``statserver.py:202-231``) and
 the ~10 methods the x-vector scoring path calls: ``validate`` (:318-336), ``align_models`` /
 ``align_segments`` (:656-684), ``norm_stat1`` / ``rotate_stat1`` / ``center_stat1`` / ``whiten_stat1``
-(:797-817,852-896), ``get_mean_stat1`` (:789-795), ``mean_stat_per_model`` (:1357-1374).  GMM statistics,
+(:797-817,852-896), ``get_mean_stat1`` (:789-795), ``sum_stat_per_model`` (:1335-1355), ``mean_stat_per_model`` (:1357-1374).  GMM statistics,
 MAP and i-vector extraction are out of scope; ``read`` / ``write`` (:392-489) exchange HDF5 files with the
 reference through ``sidekit_amd.hdf5_lite``.  Values are float64
 (``STAT_TYPE``, ``sidekit/__init__.py:59``); the alignments use hashed lookups instead of per-id scans.
@@ -171,6 +171,28 @@ class StatServer:
             lam, vec = lam.real[::-1], vec.real[:, ::-1]            # largest first
             transform = vec * (1 / numpy.sqrt(lam))[numpy.newaxis, :]
         self.rotate_stat1(transform)
+
+    def sum_stat_per_model(self):
+        """Sum the statistics of the sessions sharing a model id (``statserver.py:1335-1355``) -> ``(StatServer, session_per_model)``: one
+        session per (sorted) model and the float64 session counts.  The reference scans all model ids once per class; here one grouping
+        of the ids, then the class-sum kernel (``sc_class_sums``, rows of a class added in row order) when a GPU is visible and the same
+        grouping on the host otherwise."""
+        from .factor_analyser import ClassIndex, class_sums_device
+        index = ClassIndex(self.modelset)
+        out = StatServer()
+        out.modelset = index.ids
+        out.segset = copy.deepcopy(out.modelset)
+        out.start = numpy.empty(out.segset.shape, '|O')
+        out.stop = numpy.empty(out.segset.shape, '|O')
+        import torch
+        if torch.cuda.is_available():
+            dev = torch.device("cuda", torch.cuda.current_device())
+            out.stat0, out.stat1 = (class_sums_device(torch.as_tensor(numpy.ascontiguousarray(x, dtype=STAT_TYPE)).to(dev), index)[0].cpu().numpy()
+                                    for x in (self.stat0, self.stat1))
+        else:
+            first = numpy.concatenate(([0], numpy.cumsum(index.counts)[:-1]))
+            out.stat0, out.stat1 = (numpy.add.reduceat(numpy.asarray(x, dtype=STAT_TYPE)[index.rows], first, axis=0) for x in (self.stat0, self.stat1))
+        return out, index.counts.astype(STAT_TYPE)
 
     def mean_stat_per_model(self):
         """Average the statistics of the sessions sharing a model id -> one session per (sorted) model."""
