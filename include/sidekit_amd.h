@@ -241,6 +241,29 @@ int sc_gemm_tn(const void* d_A, const void* d_B, int32_t dtype, int64_t K, int32
 int sc_dgemm_nn(const double* d_A, const double* d_B, int32_t M, int32_t N, int32_t K, double alpha, const double* d_rowv,
                 const double* d_colv, int32_t epilogue, double* d_C, void* stream);
 
+/* ---- back-end normalisation: LDA, WCCN, Mahalanobis and spectral normalisation (sidekit/statserver.py:797-1054, 1279-1333) ---------
+ * The device half, for x-vectors (one distribution per session); the D x D algebra stays on the host (sidekit_amd/backend.py).  Same
+ * conventions as PLDA training: X is XT_F32 or XT_F64 and is widened in the load, partial sums go through the sc_* workspace and are
+ * added in a fixed order, no floating-point atomics. */
+
+/* The class-centred, class-weighted scatter
+ *   G[m][n] = sum_k w[cls[k]] (X[k][m] - Mc[cls[k]][m]) (X[k][n] - Mc[cls[k]][n]),   G: D x D float64.
+ * X: N x D; d_cls: one class number per row (rows whose number is outside [0, C) are skipped); d_Mc: C x D float64 class means
+ * (sc_class_sums over the counts); d_w: C float64 class weights, or NULL for weight 1.  With w = 1 and G / N this is
+ * get_within_covariance_stat1 (:940-956), with w = 1 / n_c the Sw of get_lda_matrix_stat1 (:980-1019) and, over C, the WCCN matrix
+ * (:1031-1054).  Formed directly, never as total minus between: that difference loses |total| / |within| in relative accuracy. */
+int sc_scatter_within(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const int32_t* d_cls, const double* d_Mc, const double* d_w,
+                      int32_t C, double* d_G, void* stream);
+
+/* Centre, right-multiply and (normalize != 0) length-normalise in one pass over the rows:
+ *   Y[i][:] = f((X[i][:] - mu) . R),   f = identity, or v / max(|v|, 1e-8)  (norm_stat1, :797-800).
+ * X: N x D; d_mu: D float64 or NULL; d_R: D x P float64 row-major; d_Y: N x P, XT_F64 or XT_F32 (the float64 result rounded once); Y may
+ * not overlap X.  This is whiten_stat1 + norm_stat1 (one iteration of spectral_norm_stat1), rotate_stat1 and whiten_cholesky_stat1.  Up
+ * to P = 256 a workgroup holds whole rows and the length costs no extra pass; a normalising call with P > 256 computes the product
+ * twice (first the rows' sums of squares, through the workspace, then the scaled rows). */
+int sc_whiten_rows(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const double* d_mu, const double* d_R, int32_t P, int32_t normalize,
+                   void* d_Y, int32_t y_dtype, void* stream);
+
 /* ---- EER support (host code, no GPU needed) --------------------------------------------------- */
 
 /* sidekit.bosaris.detplot.pavx (sidekit/bosaris/detplot.py:289-351): isotonic (non-decreasing) fit of y.

@@ -20,6 +20,9 @@ an ``.npz`` with those three arrays (``tests/golden/config5.npz`` holds the ones
 without it they are estimated from the training x-vectors: ``--plda-train moments`` (the default) takes a moment estimate (between /
 within speaker covariance, on the host), ``--plda-train em`` runs PLDA training proper (``sidekit/factor_analyser.py:830-932``) with
 ``factor_analyser.plda_device`` on the gathered device tensor -- the x-vectors make no host round trip.  ``--plda FILE`` wins over both.
+``--lda RANK`` and ``--sphnorm IT`` put the reference's PLDA recipe in front of that: LDA, then ``IT`` iterations of spherical nuisance
+normalisation (``sidekit_amd.backend``), both estimated on the training part of the gathered device tensor and applied to all x-vectors on
+the device before PLDA training and PLDA scoring (cosine scoring keeps the raw x-vectors); without the flags nothing changes.
 
 ``main(argv, model=None, scoring=None, keep=None)``: ``keep`` (a dict) receives the gathered x-vectors (``"xv"``, device tensor), the labels and
 rank 0's two score matrices -- for tests that compare two runs; the model and the module that scores (``cosine_matrix_device``, ``plda_matrix_device``,
@@ -114,6 +117,8 @@ def main(argv=None, model=None, scoring=None, keep=None):
     ap.add_argument("--plda", default=None, help="PLDA (mu, F, Sigma): SIDEKIT HDF5 or .npz; default: moment estimate from the corpus")
     ap.add_argument("--plda-train", default="moments", choices=["moments", "em"],
                     help="without --plda: moment estimate on the host (default) or EM training on the device (factor_analyser.plda_device, 10 iterations)")
+    ap.add_argument("--lda", type=int, default=None, metavar="RANK", help="project the x-vectors on RANK LDA directions before PLDA (backend.lda_device; default: no LDA)")
+    ap.add_argument("--sphnorm", type=int, default=None, metavar="IT", help="IT iterations of spherical nuisance normalisation before PLDA (after --lda; default: none)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL over xGMI; gloo for CPU rehearsals")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu only with an injected model / scoring module")
     args = ap.parse_args(argv)
@@ -179,9 +184,29 @@ def main(argv=None, model=None, scoring=None, keep=None):
     cos_rows = score_sharded(lambda a, b: scoring.cosine_matrix_device(E[a:b], T, dev), n)   # rank 0 gets (n, n), device resident
     sync()
     t_cos = time.perf_counter() - t0
+    transforms = None
+    if args.lda or args.sphnorm:
+        # the reference's PLDA recipe: LDA, then spectral normalisation, estimated on the PLDA training rows and applied to every row,
+        # on the device (float64 rows from here on); identical on every rank: same gathered data, fixed summation order
+        from .. import backend
+        assert dev.type == "cuda", "--lda / --sphnorm run on the GPU (sidekit_amd.backend has no CPU fallback)"
+        t0 = time.perf_counter()
+        pv, transforms = xv, {"lda": None, "sphnorm": None}
+        if args.lda:
+            transforms["lda"] = backend.lda_device(pv[2 * n:], labels[2 * n:], args.lda)
+            pv = backend.whiten_rows_device(pv, None, transforms["lda"])
+        if args.sphnorm:
+            means, covs, _ = backend.spectral_norm_estimate_device(pv[2 * n:], labels[2 * n:], args.sphnorm, "sphNorm")
+            transforms["sphnorm"] = (means, covs)
+            pv = backend.spectral_norm_apply_device(pv, means, covs)
+        sync()
+        t_backend = time.perf_counter() - t0
+        assert pv.is_cuda and pv.shape[0] == N, "the normalised x-vectors left the device or lost rows"
+        assert args.plda_rank <= pv.shape[1], f"--plda-rank {args.plda_rank} exceeds the dimension of the normalised x-vectors ({pv.shape[1]})"
+        E, T, train = pv[:n], pv[n:2 * n], pv[2 * n:]
     if args.plda:
         mu, F, Sigma = load_plda(args.plda)
-        assert mu.shape[0] == xv.shape[1], "PLDA dimension differs from the x-vectors'"
+        assert mu.shape[0] == E.shape[1], "PLDA dimension differs from the x-vectors'"
     elif args.plda_train == "em":
         from ..factor_analyser import plda_device
         mu, F, Sigma = plda_device(train, labels[2 * n:], args.plda_rank)                 # identical on every rank: same data, fixed summation order
@@ -199,6 +224,8 @@ def main(argv=None, model=None, scoring=None, keep=None):
            "plda": args.plda or ("moment estimate" if args.plda_train == "moments" else "EM on the device"), "backend": dist.get_backend() if dist.is_initialized() else None,
            "xv_finite": bool(torch.isfinite(xv).all()), "xv_norm_max_dev": float((norms - 1.0).abs().max()),
            "gathered_own_block_ok": gathered_own_block_ok}
+    if transforms is not None:
+        out["backend_normalisation"] = {"lda_rank": args.lda, "sphnorm_iterations": args.sphnorm, "dimension": int(E.shape[1]), "seconds": t_backend}
     if args.all_pairs:
         # matrix-free: rank r counts the pairs (i, j), i in its enrolment-row shard, j over the whole corpus, i != j
         a, b = shard_range(N, rank, world)
@@ -223,6 +250,8 @@ def main(argv=None, model=None, scoring=None, keep=None):
         out.update(all_pairs=int(counts.sum()), all_pairs_s=t_hist, all_pairs_eer=float(eer_from_histograms(counts[0], counts[1])))
     if keep is not None:
         keep.update(xv=xv, labels=labels, tar=tar, plda=(mu, F, Sigma))
+        if transforms is not None:
+            keep.update(transforms=transforms, plda_rows=(E, T, train))
     if rank == 0:
         for name, rows in (("cosine", cos_rows), ("plda", plda_rows)):
             s = rows.cpu().numpy().astype(float)

@@ -17,6 +17,9 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 //   A_KM = false: A is [M][K];  A_KM = true: A is [K][M] (C = A^T . B, the "TN" product of PLDA training: K is the long dimension)
 // The A_KM form reads float32 or float64 operands (TA, TB; widened in the load) and can weight and centre them on the way into LDS:
 //   C[m][n] = sum_k w[k] (A[k][m] - ca[m]) (B[k][n] - cb[n]),   w, ca, cb optional; cs = 2 * T doubles of LDS for the two centres.
+// ROWC (with A_KM, B = A, N = M): the centre is a per-ROW one gathered through a class number, and so is the weight:
+//   C[m][n] = sum_k w[cls[k]] (A[k][m] - ca[cls[k]][m]) (A[k][n] - ca[cls[k]][n]),   ca: [C][M] class means, w: [C] or null;
+//   rows whose class number is outside [0, C) get weight 0 and no centre is read for them; cb and cs are unused.
 constexpr int DK = 16, DLD = DK + 1;
 
 template <typename T> struct pair_of;
@@ -37,11 +40,13 @@ __device__ inline double2 fetch_pair(const T* __restrict__ src, bool vec, int i,
   return v;
 }
 
-template <int WT, bool B_KN, bool A_KM = false, typename TA = double, typename TB = double>
+template <int WT, bool B_KN, bool A_KM = false, typename TA = double, typename TB = double, bool ROWC = false>
 __device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict__ B, int M, int N, int K, int m0, int n0,
                                   double* As, double* Bs, f64x4 (&acc)[WT][WT], const double* __restrict__ w = nullptr,
-                                  const double* __restrict__ ca = nullptr, const double* __restrict__ cb = nullptr, double* cs = nullptr) {
+                                  const double* __restrict__ ca = nullptr, const double* __restrict__ cb = nullptr, double* cs = nullptr,
+                                  const int* __restrict__ cls = nullptr, int C = 0) {
   static_assert(!A_KM || B_KN, "the A [K][M] form comes with B [K][N]");
+  static_assert(!ROWC || (A_KM && std::is_same<TA, TB>::value), "gathered row centres: A_KM form with B = A");
   static_assert(A_KM || (std::is_same<TA, double>::value && std::is_same<TB, double>::value), "float32 operands: A_KM form only");
   constexpr int T = 32 * WT;            // workgroup tile edge
   constexpr int PA = T * DK / 2 / 256;  // double pairs per thread and operand
@@ -51,7 +56,7 @@ __device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict
   const bool vec_b = ((B_KN ? N : K) & 1) == 0 && (reinterpret_cast<size_t>(B) & (2 * sizeof(TB) - 1)) == 0;
   double2 ra[PA], rb[PA];
   double rw[A_KM ? PA : 1];   // A_KM: the weight of each fetched k-row, 0 beyond K (which also zeroes the centred padding)
-  if constexpr (A_KM) {
+  if constexpr (A_KM && !ROWC) {
     for (int i = tid; i < 2 * T; i += 256) {
       const int j = i < T ? m0 + i : n0 + i - T;
       cs[i] = i < T ? (ca && j < M ? ca[j] : 0.0) : (cb && j < N ? cb[j] : 0.0);
@@ -70,6 +75,21 @@ __device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict
           else { if (k < K) v.x = src[0]; if (k + 1 < K) v.y = src[1]; }
         }
         ra[q] = v;
+      } else if constexpr (ROWC) {  // A [K][M] and the same rows again as B, each less its class's mean (rows of ca are M long: N = M)
+        const int kk = idx / (T / 2), mp = (idx % (T / 2)) * 2, m = m0 + mp, n = n0 + mp, k = k0 + kk;
+        double2 va = {0.0, 0.0}, vb = {0.0, 0.0};
+        double wk = 0.0;
+        if (k < K) {
+          const int c = cls[k];
+          if (c >= 0 && c < C) {
+            const bool vec_c = (M & 1) == 0 && (reinterpret_cast<size_t>(ca) & 15) == 0;
+            const double2 xa = fetch_pair(A + (long)k * M + m, vec_a, m, M), xb = fetch_pair(A + (long)k * M + n, vec_a, n, M);
+            const double2 ma = fetch_pair(ca + (long)c * M + m, vec_c, m, M), mb = fetch_pair(ca + (long)c * M + n, vec_c, n, M);
+            va.x = xa.x - ma.x; va.y = xa.y - ma.y; vb.x = xb.x - mb.x; vb.y = xb.y - mb.y;
+            wk = w ? w[c] : 1.0;
+          }
+        }
+        ra[q] = va; rb[q] = vb; rw[q] = wk;
       } else {  // A [K][M]: 16 k x T/2 pairs along m
         const int kk = idx / (T / 2), mp = (idx % (T / 2)) * 2, m = m0 + mp, k = k0 + kk;
         double2 v = {0.0, 0.0};
@@ -86,6 +106,7 @@ __device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict
           else { if (k < K) v.x = src[0]; if (k + 1 < K) v.y = src[1]; }
         }
         rb[q] = v;
+      } else if constexpr (ROWC) {  // fetched with A above
       } else if constexpr (!A_KM) {  // B [K][N]: 16 k x T/2 pairs along n
         const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2, n = n0 + np, k = k0 + kk;
         double2 v = {0.0, 0.0};
@@ -110,9 +131,10 @@ __device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict
       const int row = idx >> 3, kp = (idx & 7) * 2;
       const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2;
       if constexpr (!A_KM) { As[row * DLD + kp] = ra[q].x; As[row * DLD + kp + 1] = ra[q].y; }
+      else if constexpr (ROWC) { As[np * DLD + kk] = ra[q].x * rw[q]; As[(np + 1) * DLD + kk] = ra[q].y * rw[q]; }
       else { As[np * DLD + kk] = (ra[q].x - cs[np]) * rw[q]; As[(np + 1) * DLD + kk] = (ra[q].y - cs[np + 1]) * rw[q]; }
       if constexpr (!B_KN) { Bs[row * DLD + kp] = rb[q].x; Bs[row * DLD + kp + 1] = rb[q].y; }
-      else if constexpr (!A_KM) { Bs[np * DLD + kk] = rb[q].x; Bs[(np + 1) * DLD + kk] = rb[q].y; }
+      else if constexpr (!A_KM || ROWC) { Bs[np * DLD + kk] = rb[q].x; Bs[(np + 1) * DLD + kk] = rb[q].y; }
       else { Bs[np * DLD + kk] = rb[q].x - cs[T + np]; Bs[(np + 1) * DLD + kk] = rb[q].y - cs[T + np + 1]; }
     }
   };

@@ -1,10 +1,12 @@
 // PLDA training (sidekit/factor_analyser.py:830-932, FactorAnalyser.plda) from x-vectors that stay on the device.
 //
 // Everything with an utterance (N) or class (C) dimension runs here in float64; the D x D and rank x rank algebra (eigh, solve,
-// cholesky, one inverse) stays on the host, the split scoring.hip makes.  Three entry points:
+// cholesky, one inverse) stays on the host, the split scoring.hip makes.  Four entry points:
 //   sc_class_sums   per-class sums of the rows of X (StatServer.sum_stat_per_model, statserver.py:1335-1355) and the column sums
 //   sc_gemm_tn      G = sum_k w[k] (A[k][:] - a)^T (B[k][:] - b): the total scatter (K = N) and the three class-sized accumulators
 //   sc_dgemm_nn     C = A . B with a rank-one or a posterior-scale epilogue: the whitened class sums and the E-step
+//   sc_scatter_within  G = sum_k w[cls[k]] (X[k][:] - Mc[cls[k]][:])^T (X[k][:] - Mc[cls[k]][:]): the within-class scatter of the
+//                   back-end normalisations (statserver.py:940-1054), the TN product with a gathered per-row centre
 // x-vectors arrive as float32 or float64 and are widened in the load.  No floating-point atomics: partial sums (class slices, row
 // slabs of the TN product) are written to the sc_* workspace and added in a fixed order, so a call's bits depend on its arguments alone.
 #include "../../include/sidekit_amd.h"
@@ -92,6 +94,37 @@ __global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void dgemm_tn_kernel(const T*
     }
 }
 
+// The same grid and slabs with the centre of row k gathered through its class number (dgemm_tile's ROWC form): A = B = X, M = N = D.
+// Bounds: as above; a class number outside [0, C) gives its row weight 0 and reads no centre.
+template <int WT, typename T>
+__global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void scatter_within_kernel(const T* __restrict__ X, long K, int D, int slab,
+                                                                              const int* __restrict__ cls, const double* __restrict__ Mc,
+                                                                              const double* __restrict__ w, int C, double* __restrict__ out) {
+  constexpr int TL = 32 * WT;
+  __shared__ __attribute__((aligned(16))) double As[TL * DLD];
+  __shared__ __attribute__((aligned(16))) double Bs[TL * DLD];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const int m0 = blockIdx.y * TL, n0 = blockIdx.x * TL;
+  const long k_begin = (long)blockIdx.z * slab;
+  const int kl = (int)(K - k_begin < (long)slab ? K - k_begin : (long)slab);
+  f64x4 acc[WT][WT];
+  dgemm_tile<WT, true, true, T, T, true>(X + k_begin * D, X + k_begin * D, D, D, kl, m0, n0, As, Bs, acc, w, Mc, nullptr, nullptr, cls + k_begin, C);
+  double* dst = out + (long)blockIdx.z * D * D;
+#pragma unroll
+  for (int i = 0; i < WT; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int m = m0 + wm * 16 * WT + i * 16 + lk + 4 * q;
+      if (m >= D) continue;
+#pragma unroll
+      for (int j = 0; j < WT; ++j) {
+        const int n = n0 + wn * 16 * WT + j * 16 + lr;
+        if (n < D) dst[(long)m * D + n] = acc[i][j][q];
+      }
+    }
+}
+
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const double* __restrict__ part, int nslabs, long mn, double* __restrict__ G) {
   const long i = blockIdx.x * 256L + threadIdx.x;
   if (i >= mn) return;
@@ -131,38 +164,61 @@ __global__ __launch_bounds__(256, 4) void dgemm_nn_kernel(const double* __restri
     }
 }
 
-template <typename T>
-static int launch_gemm_tn(const T* A, const T* B, long K, int M, int N, const double* w, const double* ca, const double* cb, double* G,
-                          hipStream_t st) {
-  // 128 x 128 tiles when the output has them and K is long (the total scatter), 64 x 64 otherwise; K is cut into slabs (a multiple of the
-  // k-tile) until about 512 workgroups exist.  The cut is a function of (M, N, K) alone.
-  const bool big = M >= 128 && N >= 128 && K >= 4096;
-  const int TL = big ? 128 : 64;
-  const long tiles = (long)cdiv(M, TL) * cdiv(N, TL);
-  long nsplit = (K + 511) / 512;
+// The cut of a TN product: 128 x 128 tiles when the output has them and K is long (the total scatter), 64 x 64 otherwise; K is cut into
+// slabs (a multiple of the k-tile) until about 512 workgroups exist.  A function of (M, N, K) alone.
+struct TnCut { bool big; int TL; long nsplit, slab; };
+static TnCut tn_cut(long K, int M, int N) {
+  TnCut c;
+  c.big = M >= 128 && N >= 128 && K >= 4096;
+  c.TL = c.big ? 128 : 64;
+  const long tiles = (long)cdiv(M, c.TL) * cdiv(N, c.TL);
+  c.nsplit = (K + 511) / 512;
   const long want = tiles >= 512 ? 1 : 512 / tiles;
-  if (nsplit > want) nsplit = want;
-  long slab = (K + nsplit - 1) / nsplit;
-  slab = (slab + DK - 1) / DK * DK;
-  nsplit = (K + slab - 1) / slab;
+  if (c.nsplit > want) c.nsplit = want;
+  c.slab = (K + c.nsplit - 1) / c.nsplit;
+  c.slab = (c.slab + DK - 1) / DK * DK;
+  c.nsplit = (K + c.slab - 1) / c.slab;
+  return c;
+}
+
+// launch(big, grid, slab, out) enqueues the tile kernel; with more than one slab its partial tiles go to the workspace and are added in
+// slab order.
+template <typename Launch>
+static int launch_tn_slabs(long K, int M, int N, double* G, hipStream_t st, Launch launch) {
+  const TnCut c = tn_cut(K, M, N);
   double* out = G;
   std::unique_lock<std::mutex> lock(g_plda_mu, std::defer_lock);
-  if (nsplit > 1) {
+  if (c.nsplit > 1) {
     void* ws = nullptr;
     lock.lock();   // held until both launches are enqueued (see plda_workspace_locked)
-    SK_TRY(plda_workspace_locked(st, (size_t)nsplit * M * N * 8, &ws));
+    SK_TRY(plda_workspace_locked(st, (size_t)c.nsplit * M * N * 8, &ws));
     out = (double*)ws;
   }
-  const dim3 grid(cdiv(N, TL), cdiv(M, TL), (unsigned)nsplit);
-  if (big) hipLaunchKernelGGL((dgemm_tn_kernel<4, T>), grid, dim3(256), 0, st, A, B, K, M, N, (int)slab, w, ca, cb, out);
-  else hipLaunchKernelGGL((dgemm_tn_kernel<2, T>), grid, dim3(256), 0, st, A, B, K, M, N, (int)slab, w, ca, cb, out);
+  launch(c.big, dim3(cdiv(N, c.TL), cdiv(M, c.TL), (unsigned)c.nsplit), (int)c.slab, out);
   SK_HIP(hipGetLastError());
-  if (nsplit > 1) {
+  if (c.nsplit > 1) {
     const long mn = (long)M * N;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, st, out, (int)nsplit, mn, G);
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, st, out, (int)c.nsplit, mn, G);
     SK_HIP(hipGetLastError());
   }
   return SK_OK;
+}
+
+template <typename T>
+static int launch_gemm_tn(const T* A, const T* B, long K, int M, int N, const double* w, const double* ca, const double* cb, double* G,
+                          hipStream_t st) {
+  return launch_tn_slabs(K, M, N, G, st, [&](bool big, dim3 grid, int slab, double* out) {
+    if (big) hipLaunchKernelGGL((dgemm_tn_kernel<4, T>), grid, dim3(256), 0, st, A, B, K, M, N, slab, w, ca, cb, out);
+    else hipLaunchKernelGGL((dgemm_tn_kernel<2, T>), grid, dim3(256), 0, st, A, B, K, M, N, slab, w, ca, cb, out);
+  });
+}
+
+template <typename T>
+static int launch_scatter_within(const T* X, long K, int D, const int* cls, const double* Mc, const double* w, int C, double* G, hipStream_t st) {
+  return launch_tn_slabs(K, D, D, G, st, [&](bool big, dim3 grid, int slab, double* out) {
+    if (big) hipLaunchKernelGGL((scatter_within_kernel<4, T>), grid, dim3(256), 0, st, X, K, D, slab, cls, Mc, w, C, out);
+    else hipLaunchKernelGGL((scatter_within_kernel<2, T>), grid, dim3(256), 0, st, X, K, D, slab, cls, Mc, w, C, out);
+  });
 }
 
 }  // namespace sk
@@ -201,6 +257,16 @@ int sc_gemm_tn(const void* d_A, const void* d_B, int32_t dtype, int64_t K, int32
   SK_CHECK(K > 0 && M > 0 && Nn > 0 && (int64_t)M * Nn <= (1LL << 28), SK_EARG, "sc_gemm_tn: bad sizes (K=%lld, M=%d, Nn=%d)", (long long)K, M, Nn);
   if (dtype == XT_F32) return launch_gemm_tn((const float*)d_A, (const float*)d_B, (long)K, M, Nn, d_w, d_ca, d_cb, d_G, (hipStream_t)stream);
   return launch_gemm_tn((const double*)d_A, (const double*)d_B, (long)K, M, Nn, d_w, d_ca, d_cb, d_G, (hipStream_t)stream);
+}
+
+int sc_scatter_within(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const int32_t* d_cls, const double* d_Mc, const double* d_w,
+                      int32_t C, double* d_G, void* stream) {
+  SK_CHECK(d_X && d_cls && d_Mc && d_G, SK_EARG, "sc_scatter_within: null argument");
+  SK_CHECK(x_dtype == XT_F32 || x_dtype == XT_F64, SK_EARG, "sc_scatter_within: X must be XT_F32 or XT_F64 (got %d)", x_dtype);
+  SK_CHECK(N > 0 && N <= 0x7fffffffLL && D > 0 && D <= 16384 && C > 0, SK_EARG, "sc_scatter_within: bad sizes (N=%lld, D=%d, C=%d)",
+           (long long)N, D, C);
+  if (x_dtype == XT_F32) return launch_scatter_within((const float*)d_X, (long)N, D, d_cls, d_Mc, d_w, C, d_G, (hipStream_t)stream);
+  return launch_scatter_within((const double*)d_X, (long)N, D, d_cls, d_Mc, d_w, C, d_G, (hipStream_t)stream);
 }
 
 int sc_dgemm_nn(const double* d_A, const double* d_B, int32_t M, int32_t N, int32_t K, double alpha, const double* d_rowv,

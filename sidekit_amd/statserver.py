@@ -3,7 +3,9 @@
 Mirrors the attributes (``modelset, segset, start, stop, stat0, stat1``; ``statserver.py:202-231``) and
 the ~10 methods the x-vector scoring path calls: ``validate`` (:318-336), ``align_models`` /
 ``align_segments`` (:656-684), ``norm_stat1`` / ``rotate_stat1`` / ``center_stat1`` / ``whiten_stat1``
-(:797-817,852-896), ``get_mean_stat1`` (:789-795), ``sum_stat_per_model`` (:1335-1355), ``mean_stat_per_model`` (:1357-1374).  GMM statistics,
+(:797-817,852-896), ``get_mean_stat1`` (:789-795), ``sum_stat_per_model`` (:1335-1355), ``mean_stat_per_model`` (:1357-1374), and the
+back-end normalisations of x-vectors, which run on the GPU through ``sidekit_amd.backend`` (``get_within_covariance_stat1`` ...
+``get_wccn_choleski_stat1`` :940-1054, ``whiten_cholesky_stat1`` :898-918, spectral normalisation :1279-1333).  GMM statistics,
 MAP and i-vector extraction are out of scope; ``read`` / ``write`` (:392-489) exchange HDF5 files with the
 reference through ``sidekit_amd.hdf5_lite``.  Values are float64
 (``STAT_TYPE``, ``sidekit/__init__.py:59``); the alignments use hashed lookups instead of per-id scans.
@@ -20,6 +22,14 @@ from .bosaris import IdMap, _h5
 from .bosaris._sets import first_index
 
 STAT_TYPE = numpy.float64
+
+
+def whitening_transform(sigma):
+    """The matrix ``whiten_stat1`` multiplies by for a full covariance (``statserver.py:871-878``): ``V diag(lambda^-1/2)``, eigenvalues in
+    descending order -- not the symmetric inverse square root.  Shared with ``sidekit_amd.backend``."""
+    lam, vec = scipy.linalg.eigh(sigma)                     # ascending
+    lam, vec = lam.real[::-1], vec.real[:, ::-1]            # largest first
+    return vec * (1 / numpy.sqrt(lam))[numpy.newaxis, :]
 
 
 class StatServer:
@@ -165,12 +175,70 @@ class StatServer:
         if sigma.ndim == 1:
             self.stat1 = self.stat1 / numpy.sqrt(sigma.astype(STAT_TYPE))
             return
-        transform = sigma
-        if not isSqrInvSigma:
-            lam, vec = scipy.linalg.eigh(sigma)                     # ascending
-            lam, vec = lam.real[::-1], vec.real[:, ::-1]            # largest first
-            transform = vec * (1 / numpy.sqrt(lam))[numpy.newaxis, :]
-        self.rotate_stat1(transform)
+        self.rotate_stat1(sigma if isSqrInvSigma else whitening_transform(sigma))
+
+    # ---- back-end normalisation on the GPU (sidekit_amd/backend.py): stat1 is uploaded once per call, no CPU fallback ----------------
+
+    def _device_rows(self):
+        """``stat1`` as a float64 tensor on the current GPU and the class index of ``modelset``; x-vectors only (one distribution
+        per session, occupation 1, so that centring subtracts ``mu`` itself)."""
+        from .factor_analyser import ClassIndex, _torch
+        torch = _torch()
+        assert self.stat0.shape[1] == 1 and numpy.all(self.stat0 == 1), \
+            "the back-end normalisations take x-vectors: one distribution per session with stat0 == 1"
+        xv = torch.as_tensor(numpy.ascontiguousarray(self.stat1, dtype=STAT_TYPE)).to(torch.device("cuda", torch.cuda.current_device()))
+        return xv, ClassIndex(self.modelset)
+
+    def get_within_covariance_stat1(self):
+        """Within-class covariance, over the number of sessions (``statserver.py:940-956``)."""
+        from . import backend
+        return backend.within_covariance_device(*self._device_rows())
+
+    def get_between_covariance_stat1(self):
+        """Between-class covariance: class means about the global mean, weighted by the session counts (``statserver.py:958-978``)."""
+        from . import backend
+        return backend.between_covariance_device(*self._device_rows())
+
+    def get_lda_matrix_stat1(self, rank):
+        """LDA matrix (D, rank), columns by descending eigenvalue (``statserver.py:980-1019``; ``backend.lda_device`` on what defines it)."""
+        from . import backend
+        return backend.lda_device(*self._device_rows(), rank)
+
+    def get_mahalanobis_matrix_stat1(self):
+        """Inverse of the within-class covariance (``statserver.py:1021-1029``)."""
+        from . import backend
+        return backend.mahalanobis_device(*self._device_rows())
+
+    def get_wccn_choleski_stat1(self):
+        """Lower Cholesky factor of the inverse WCCN matrix (``statserver.py:1031-1054``)."""
+        from . import backend
+        return backend.wccn_device(*self._device_rows())
+
+    def whiten_cholesky_stat1(self, mu, sigma):
+        """Centre on ``mu`` and whiten by the Cholesky factor of ``inv(sigma)`` (2-D) or by the square roots of a diagonal covariance
+        (1-D), ``statserver.py:898-918``."""
+        from . import backend
+        if sigma.ndim == 2:
+            transform = scipy.linalg.cholesky(scipy.linalg.inv(sigma)).T
+        elif sigma.ndim == 1:
+            transform = numpy.diag(1 / numpy.sqrt(sigma.astype(STAT_TYPE)))
+        else:
+            raise Exception('Wrong dimension of Sigma, must be 1 or 2')
+        self.stat1 = backend.whiten_rows_device(self._device_rows()[0], numpy.asarray(mu, dtype=STAT_TYPE), transform).cpu().numpy()
+
+    def estimate_spectral_norm_stat1(self, it=1, mode='efr'):
+        """Means and covariances of ``it`` iterations of spectral normalisation (``statserver.py:1279-1315``): ``mode='efr'`` (total
+        covariance) or ``'sphNorm'`` (within-class covariance).  ``self.stat1`` is left as it is."""
+        from . import backend
+        xv, index = self._device_rows()
+        spectral_norm_mean, spectral_norm_cov, _ = backend.spectral_norm_estimate_device(xv, index, it, mode)
+        return spectral_norm_mean, spectral_norm_cov
+
+    def spectral_norm_stat1(self, spectral_norm_mean, spectral_norm_cov, is_sqr_inv_sigma=False):
+        """For each ``(mean, covariance)``: centre, whiten, scale to unit length (``statserver.py:1317-1333``), in place."""
+        from . import backend
+        assert len(spectral_norm_mean) == len(spectral_norm_cov), 'Number of mean vectors and covariance matrices is different'
+        self.stat1 = backend.spectral_norm_apply_device(self._device_rows()[0], spectral_norm_mean, spectral_norm_cov, is_sqr_inv_sigma).cpu().numpy()
 
     def sum_stat_per_model(self):
         """Sum the statistics of the sessions sharing a model id (``statserver.py:1335-1355``) -> ``(StatServer, session_per_model)``: one
