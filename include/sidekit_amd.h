@@ -168,6 +168,45 @@ const char* xt_last_error(void);
 int sk_resample(const void* d_in, int32_t in_dtype, int64_t n_in, int32_t orig_freq, int32_t new_freq, float* d_out,
                 int64_t out_capacity, int64_t* n_out, void* stream);
 
+/* ---- speech activity: energy VAD and chunk gathering (csrc/vad.hip) --------------------------------------------------------------
+ * What `extract_xvectors.py --vad` does to a signal before the forward (sidekit/bin/extract_xvectors.py:98-151): find speech, keep only
+ * those samples.  The detector is the reference's own energy VAD (sidekit/mixture.py:67-113 on the log-energy of
+ * sidekit/frontend/features.py:363-389, smoothed by label_fusion, sidekit/frontend/vad.py:409-428); timestamps from any detector (the
+ * reference's `<out>_vad.json` cache) are applied by sk_collect_segments.  float64 throughout, fixed-order reductions, no atomics: the
+ * bits are a function of the arguments alone. */
+
+/* power_spectrum's log-energy.  d_wav [B][wav_ld], XT_F32 or XT_I16 (widened as x / 32768); d_nsamples: B sample counts on the device
+ * (clamped to [0, wav_ld]).  Utterance b has nframes = (n - nwin) / shift + 1 frames (0 if n < nwin: the reference's `framing` is not
+ * defined there); frame t is samples [t shift, t shift + nwin), pre-emphasised inside the frame (y[0] = x[0] - prefac x[0],
+ * y[j] = x[j] - prefac x[j-1]); d_le[b][t] = log(sum_j y[j]^2), float64 [B][T_ld] (columns from nframes[b] on are zero),
+ * T_ld >= the frames of wav_ld samples.  d_nframes: int32 [B]. */
+int sk_frame_log_energy(const void* d_wav, int32_t in_dtype, int64_t wav_ld, const int32_t* d_nsamples, int32_t B, int32_t nwin, int32_t shift,
+                        double prefac, double* d_le, int32_t T_ld, int32_t* d_nframes, void* stream);
+
+/* vad_energy(log_energy, distrib_nb=3, nb_train_it=n_iter, flooring, ceiling, alpha) per utterance, then label_fusion(win=fusion_win)
+ * (0 = none, else odd, 3..255: grey closing followed by grey opening, scipy's 'reflect' boundary).  d_label uint8 [B][T_ld] (0 beyond
+ * nframes[b]); d_threshold float64 [B], in units of the standardised log-energy.  The first E-step runs with the reference's constant term
+ * A = 0 (its Mixture is scored before _compute_all ever ran).  Degenerate utterances -- no frame, zero or non-finite standard deviation
+ * (any non-finite log-energy), a NaN threshold, or no frame left labelled after the fusion -- keep ALL their frames and report a NaN
+ * threshold: the driver's `len(speech_timestamps) == 0` fallback (extract_xvectors.py:137-138). */
+int sk_vad_energy(const double* d_le, const int32_t* d_nframes, int32_t B, int32_t T_ld, int32_t n_iter, double flooring, double ceiling, double alpha,
+                  int32_t fusion_win, uint8_t* d_label, double* d_threshold, void* stream);
+
+/* Keep sample s of utterance b iff d_label[b][min(s / shift, nframes[b] - 1)] is set (an utterance without a frame is kept whole): the
+ * kept samples go to d_dst[b][0 .. out_len[b]), same element type (XT_F32 / XT_I16) as d_src; the rest of a dst row is not written.
+ * dst_ld >= src_ld; dst may not overlap src.  d_out_len: int32 [B] on the device.  The reference's x-vector path has no label-to-sample
+ * rule (its labels select feature frames); this one makes frame t own samples [t shift, (t + 1) shift) and the last frame the tail. */
+int sk_collect_labels(const void* d_src, int32_t dtype, int64_t src_ld, const int32_t* d_nsamples, const uint8_t* d_label, int32_t T_ld,
+                      const int32_t* d_nframes, int32_t B, int32_t shift, void* d_dst, int64_t dst_ld, int32_t* d_out_len, void* stream);
+
+/* collect_chunks(speech_timestamps, signal) for a batch: utterance b keeps the sample ranges [seg[2 i], seg[2 i + 1]) for i in
+ * [seg_off[b], seg_off[b + 1]), concatenated in d_dst[b][0 ..).  The CSR is passed twice: the host copy (h_nsamples, h_seg_off [B + 1],
+ * h_seg [2 n]) is validated before anything is enqueued -- 0 <= start <= end <= nsamples[b], ascending, no overlap, kept total <= dst_ld;
+ * anything else is SK_EARG -- and the device copy (d_seg_off, d_seg: the same numbers, uploaded by the caller in the order of `stream`)
+ * is what the kernel reads.  h_out_len (B, may be NULL) receives the kept lengths: no read-back on this path. */
+int sk_collect_segments(const void* d_src, int32_t dtype, int64_t src_ld, const int32_t* h_nsamples, const int32_t* h_seg_off, const int32_t* h_seg,
+                        const int32_t* d_seg_off, const int32_t* d_seg, int32_t B, void* d_dst, int64_t dst_ld, int32_t* h_out_len, void* stream);
+
 /* ---- trial scoring ------------------------------------------------------------------------- */
 
 /* sidekit.iv_scoring.cosine_scoring, the einsum of sidekit/iv_scoring.py:108-109: rows already

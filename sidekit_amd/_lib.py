@@ -63,6 +63,10 @@ SIGNATURES = {
     "xt_debug_tap": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _SZ, ctypes.POINTER(_SZ)]),
     "xt_last_error": (ctypes.c_char_p, []),
     "sk_resample": (ctypes.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I64, ctypes.POINTER(_I64), _P]),
+    "sk_frame_log_energy": (ctypes.c_int, [_P, _I32, _I64, _P, _I32, _I32, _I32, _F64, _P, _I32, _P, _P]),
+    "sk_vad_energy": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _F64, _F64, _F64, _I32, _P, _P, _P]),
+    "sk_collect_labels": (ctypes.c_int, [_P, _I32, _I64, _P, _P, _I32, _P, _I32, _I32, _P, _I64, _P, _P]),
+    "sk_collect_segments": (ctypes.c_int, [_P, _I32, _I64, _P, _P, _P, _P, _P, _I32, _P, _I64, _P, _P]),
     "sc_cosine": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P]),
     "sc_plda_fast": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _F64, _F64, _P, _P]),
     "sc_release_workspace": (ctypes.c_int, []),

@@ -6,13 +6,16 @@ length-sorted into padded batches (``--batch-size``, each row is still processed
 decoding, host -> device copies and the forward overlap (``sidekit_amd/pipeline.py``); under
 ``python -m torch.distributed.run --nproc-per-node N -m sidekit_amd.bin.extract_xvectors ...`` the wav.scp is sharded over N GPUs
 (one all-gather of the x-vectors, rank 0 writes),
-the bf16 trunk can be selected (``--dtype bf16``), ``--vad`` is refused (the reference fetches Silero
-VAD with ``torch.hub`` at run time, ``extract_xvectors.py:102`` -- no network here).  PCM wavs are
+the bf16 trunk can be selected (``--dtype bf16``).  Speech-only extraction (``extract_xvectors.py:98-151``): bare ``--vad`` is refused
+(the reference fetches Silero VAD with ``torch.hub`` at run time, ``:102``), but the timestamps such a run cached in ``<out>_vad.json``
+are applied with ``--speech-ts FILE.json``, and ``--vad-energy`` runs the reference's own energy detector on the GPU
+(``sidekit_amd/vad.py``) and writes ``<out>_vad.json`` in the same format.  PCM wavs are
 decoded with ``scipy.io.wavfile`` (``soundfile`` is not installed); ``cmd |`` entries are run through
 the shell exactly as the reference does (``:57-70``).
 """
 import argparse
 import io
+import json
 import os
 import subprocess
 
@@ -90,10 +93,12 @@ def precheck(xtractor, entries, sample_rate, workers=4):
 
 @torch.no_grad()
 def main(xtractor, wav_scp, out_file, device, sample_rate=16000, out_file_spk="", spk2utt_file="", batch_size=64, dtype="fp32",
-         workers=None, window=8, gather_always=False):
+         workers=None, window=8, gather_always=False, vad=None, vad_options=None):
     """One process: the whole wav.scp.  Under ``torch.distributed.run`` (one process per GPU, an initialised process group):
     every rank streams the contiguous shard ``shard_range(len(wav.scp), rank, world)``, the ``(N_r, E)`` blocks are gathered once
     (``gather_xvectors``: RCCL all-gather, ragged counts) and rank 0 writes the ark / scp files in wav.scp order.
+    ``vad``: None, ``"energy"`` (the GPU energy detector; the timestamps it applied are written to ``<out>_vad.json``, the reference's
+    cache format, :113-151) or a mapping key -> ``[{"start", "end"}, ...]`` read from such a file.
     With ONE rank the files are written incrementally as in a plain run (``gather_always`` takes the collective path all the same: the
     rehearsal of the N-rank code on a one-GPU box).  ``workers=None``: this rank's share of the host cores (``host_workers``)."""
     if workers is None:
@@ -110,7 +115,8 @@ def main(xtractor, wav_scp, out_file, device, sample_rate=16000, out_file_spk=""
     precheck(xtractor, [(key, ' '.join(utt2wav[key])) for key in keys[lo:hi]], sample_rate, workers)
     # decode threads -> length-sorted batches inside a sliding window -> pinned staging -> copy stream -> forward, all at
     # once (sidekit_amd/pipeline.py); every row is still computed over its own length
-    stream = StreamingExtractor(xtractor, batch_size=batch_size, window=window, workers=workers, sample_rate=sample_rate)
+    stream = StreamingExtractor(xtractor, batch_size=batch_size, window=window, workers=workers, sample_rate=sample_rate, vad=vad,
+                                vad_options=vad_options, record_timestamps=vad == "energy")
     results = stream.run((key, ' '.join(utt2wav[key])) for key in keys[lo:hi])
     out_ark = os.path.realpath(os.path.join(os.path.dirname(out_file), os.path.splitext(os.path.basename(out_file))[0]))
     sharded = dist.is_initialized() and (world > 1 or gather_always)
@@ -126,6 +132,15 @@ def main(xtractor, wav_scp, out_file, device, sample_rate=16000, out_file_spk=""
                     writer.flush()
         vecs = None
     mine = dict(results) if sharded else None
+    if vad == "energy":                      # the cache a later run (this driver's --speech-ts, or the reference's --vad) reads back
+        applied = stream.timestamps
+        if sharded:
+            parts = [None] * world
+            dist.all_gather_object(parts, applied)
+            applied = {k: v for part in parts for k, v in part.items()}
+        if rank == 0:
+            with open(os.path.splitext(out_file)[0] + "_vad.json", "w") as f:
+                json.dump({k: applied[k] for k in keys if k in applied}, f)
     if sharded:
         dev = torch.device(xtractor.device)
         block = numpy.concatenate([mine[k] for k in keys[lo:hi]]) if hi > lo else numpy.zeros((0, xtractor.embedding_size), dtype=numpy.float32)
@@ -155,7 +170,13 @@ def cli(argv=None):
     parser = argparse.ArgumentParser(description="Extract the x-vectors given a sidekit model (MI355X path)")
     parser.add_argument("--model", type=str, required=True, help="SideKit model checkpoint")
     parser.add_argument("--sample-rate", type=int, default=16000, help="Must match SideKit SR model")
-    parser.add_argument("--vad", action='store_true', help="not available: the reference downloads Silero VAD at run time")
+    parser.add_argument("--vad", action='store_true', help="not available: the reference downloads Silero VAD at run time (apply its cached timestamps with "
+                        "--speech-ts, or detect speech with --vad-energy)")
+    parser.add_argument("--vad-energy", action='store_true', help="extract from speech only: the reference's energy detector (vad_energy + label_fusion) on the GPU; "
+                        "writes the timestamps to <out>_vad.json")
+    parser.add_argument("--vad-alpha", type=float, default=0.2, help="energy detector: threshold = mu_max - alpha * sigma_max")
+    parser.add_argument("--vad-fusion", type=int, default=3, help="energy detector: odd window of the label smoothing (0: none)")
+    parser.add_argument("--speech-ts", type=str, default="", help="extract from speech only: a <out>_vad.json (key -> list of {start, end} sample ranges)")
     parser.add_argument("--wav-scp", type=str, required=True)
     parser.add_argument("--out-scp", type=str, required=True)
     parser.add_argument("--out-spk-scp", type=str, default="")
@@ -173,6 +194,14 @@ def cli(argv=None):
     assert os.path.isdir(os.path.dirname(args.out_scp)), "NO SUCH DIRECTORY: %s" % args.out_scp
     if args.vad:
         raise NotImplementedError("--vad needs torch.hub.load('snakers4/silero-vad') (remote fetch): out of scope")
+    assert not (args.vad_energy and args.speech_ts), "--vad-energy and --speech-ts exclude each other"
+    vad, vad_options = None, None
+    if args.vad_energy:
+        vad, vad_options = "energy", {"alpha": args.vad_alpha, "fusion_win": args.vad_fusion}
+    elif args.speech_ts:
+        assert os.path.isfile(args.speech_ts), "NO SUCH FILE: %s" % args.speech_ts
+        with open(args.speech_ts) as f:
+            vad = json.load(f)
     if args.out_spk_scp:
         assert os.path.isdir(os.path.dirname(args.out_spk_scp)), "NO SUCH DIRECTORY: %s" % args.out_spk_scp
         assert os.path.isfile(args.spk2utt_file), "NO SUCH FILE: %s" % args.spk2utt_file
@@ -189,7 +218,8 @@ def cli(argv=None):
         else:
             dist.init_process_group("gloo")
     xtractor, _ = load_model(args.model, device)
-    main(xtractor, args.wav_scp, args.out_scp, device, args.sample_rate, args.out_spk_scp, args.spk2utt_file, args.batch_size, args.dtype, args.workers or None, args.window, args.gather_always)
+    main(xtractor, args.wav_scp, args.out_scp, device, args.sample_rate, args.out_spk_scp, args.spk2utt_file, args.batch_size, args.dtype, args.workers or None, args.window, args.gather_always,
+         vad, vad_options)
     if dist.is_initialized():
         dist.destroy_process_group()
 

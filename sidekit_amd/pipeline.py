@@ -135,6 +135,8 @@ class _Staging:
         self.host = {}
         self.dev = {}
         self.out_host = None
+        self.dev2 = {}          # speech-only extraction: the compacted batch (the forward's input), per dtype
+        self.pins = {}          # and small pinned arrays (lengths in, lengths / labels out)
         self.copied = torch.cuda.Event() if self.cuda else None
         self.done = torch.cuda.Event() if self.cuda else None
 
@@ -158,6 +160,25 @@ class _Staging:
             else:
                 self.dev[dtype] = h
         return self.host[dtype][:need].view(rows, cols), self.dev[dtype][:need].view(rows, cols)
+
+    def second(self, dtype, rows, cols, copy_stream):
+        """(rows, cols) view of the slot's SECOND device buffer of this dtype: what the gather kernels write on the copy stream and the
+        forward reads.  Grown with the first one, under the same ordering rule as in ``buffers``."""
+        need = max(rows * cols, self.dev[dtype].numel())
+        d = self.dev2.get(dtype)
+        if d is None or d.numel() < need:
+            d = torch.empty(need, dtype=dtype, device=self.device)
+            copy_stream.wait_stream(torch.cuda.current_stream(self.device))
+            d.record_stream(copy_stream)
+            self.dev2[dtype] = d
+        return self.dev2[dtype][:rows * cols].view(rows, cols)
+
+    def pinned(self, name, dtype, n):
+        p = self.pins.get(name)
+        if p is None or p.numel() < n or p.dtype != dtype:
+            p = torch.empty(max(n, 1), dtype=dtype, pin_memory=True)
+            self.pins[name] = p
+        return p[:n]
 
     def out(self, rows, cols):
         if self.out_host is None or self.out_host.shape[0] < rows or self.out_host.shape[1] != cols:
@@ -217,7 +238,7 @@ class StreamingExtractor:
     batch (length-sorted inside a window of ``window * batch_size`` utterances), not in input order."""
 
     def __init__(self, model, batch_size=256, window=8, workers=None, pending=3, sample_rate=16000, norm_embedding=True, stage_ahead=6,
-                 max_samples_per_batch=1 << 26):
+                 max_samples_per_batch=1 << 26, vad=None, vad_options=None, record_timestamps=False):
         # pending / stage_ahead: batches waiting for their read-back / staged ahead of the launches.  Round 6 (scripts/pipeline_bench.py, 32 768 files, 8 decode
         # workers, three alternating runs each, k files/s): 2 / 2 (the default up to round 5) 40.3 / 38.8 / 40.8; 2 / 3 41.3 / 41.3 / 41.0; 3 / 6 41.6 / 41.7 / 41.3;
         # 4 / 8 41.1 / 40.9 / 40.9 -- a deeper queue rides out the host's jitter (a staging slot is one pinned + one device buffer of a batch of int16 samples)
@@ -237,7 +258,21 @@ class StreamingExtractor:
         # staging slots: the batches whose forwards are in flight beyond the newest one, those waiting for their read-back, those staged ahead, + 1
         in_flight = max(1, getattr(model, "pipeline_depth", 2) - 1) if self.pipelined else 1
         self.ring = [_Staging(self.device) for _ in range(self.pending + self.stage_ahead + in_flight)]
-        self.stats = {"utterances": 0, "batches": 0, "samples": 0, "padded_samples": 0, "native_reads": 0}
+        self.stats = {"utterances": 0, "batches": 0, "samples": 0, "padded_samples": 0, "native_reads": 0, "speech_samples": 0}
+        # Speech-only extraction (extract_xvectors.py --vad, :98-151).  vad="energy": log-energy, detector and gather (csrc/vad.hip) run on the
+        # COPY stream behind the batch's host -> device copy, into the slot's second device buffer; the forward is launched one batch later, so
+        # the read-back of the new lengths (xt_forward* takes them from host memory) has normally finished by the time the host asks for it.
+        # vad=<mapping key -> [{"start", "end"}, ...]> applies timestamps (a key that is missing keeps its whole signal): no read-back.
+        if vad is not None and not (vad == "energy" or hasattr(vad, "get")):
+            raise ValueError("vad: None, 'energy' or a mapping key -> list of {'start', 'end'}")
+        if vad is not None and not self.cuda:
+            raise RuntimeError("vad: speech-only extraction runs on the GPU (no CPU fallback)")
+        self.vad = vad
+        if vad is not None:
+            self.ring.append(_Staging(self.device))         # one more slot: a batch sits between its upload and its forward
+        self.vad_options = dict(vad_options or {})
+        self.record_timestamps = bool(record_timestamps)
+        self.timestamps = {}      # key -> the [{"start", "end"}, ...] that was applied (record_timestamps=True)
 
     def _resample(self, sample, rate):
         """A file at another rate: the GPU resampler (``sk_resample``), result back on the host as float32 for the staging path.
@@ -311,6 +346,7 @@ class StreamingExtractor:
         self.stats["utterances"] += rows
         self.stats["batches"] += 1
         self.stats["samples"] += sum(lens)
+        self.stats["speech_samples"] += sum(lens)
         self.stats["padded_samples"] += rows * cols
         self.stats["native_reads"] += n_native
         keys = [it.key for it in items]
@@ -320,6 +356,77 @@ class StreamingExtractor:
                 # before this one is collected, so two batches are in flight, half a step apart (Xtractor.submit)
                 return slot, keys, self.model.submit(dev, lengths=lens, norm_embedding=self.norm_embedding), rows
             out = self.model(dev, is_eval=True, norm_embedding=self.norm_embedding, lengths=lens)
+        return self._read_back(slot, keys, out, rows)
+
+    # ---- speech-only extraction: the same batch in two steps, upload + detector first, the forward a batch later ----------------------------
+    def _upload_speech(self, slot, items, host, dev, as_int16, n_native):
+        from . import vad as vad_mod
+        lens = [it.length for it in items]
+        rows, cols = len(items), max(lens)
+        dev2 = slot.second(dev.dtype, rows, cols, self.copy_stream)
+        lens_h = slot.pinned("lens", torch.int32, rows)
+        lens_h.numpy()[:] = lens
+        got = {}
+        with torch.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(slot.done)          # the slot's previous batch has left both device buffers
+            dev.copy_(host, non_blocking=True)
+            if self.vad == "energy":
+                opts = dict(vad_mod.ENERGY_DEFAULTS)
+                opts.update(self.vad_options)
+                d_lens = lens_h.to(self.device, non_blocking=True)
+                le, nframes = vad_mod.frame_log_energy(dev, d_lens)
+                label, _ = vad_mod.vad_energy_device(le, nframes, **opts)
+                _, out_len = vad_mod.collect_chunks_device(dev, d_lens, labels=label, nframes=nframes, out=dev2)
+                got["out_len"] = slot.pinned("out_len", torch.int32, rows)
+                got["out_len"].copy_(out_len, non_blocking=True)
+                if self.record_timestamps:
+                    got["label"] = slot.pinned("label", torch.uint8, label.numel()).view(label.shape)
+                    got["label"].copy_(label, non_blocking=True)
+                    got["nframes"] = slot.pinned("nframes", torch.int32, rows)
+                    got["nframes"].copy_(nframes, non_blocking=True)
+            else:
+                got["segments"] = [self.vad.get(it.key) or [{"start": 0, "end": it.length}] for it in items]
+                _, got["new"] = vad_mod.collect_chunks_device(dev, lens, segments=got["segments"], out=dev2)
+            slot.copied.record(self.copy_stream)
+        return slot, items, dev, dev2, n_native, got
+
+    def _launch_speech(self, slot, items, dev, dev2, n_native, got):
+        from . import vad as vad_mod
+        lens = [it.length for it in items]
+        rows, cols = len(items), max(lens)
+        if "out_len" in got:
+            slot.copied.synchronize()                       # queued a batch ago: the lengths are normally there already
+            new = [int(v) for v in got["out_len"].numpy()]
+        else:
+            new = [int(v) for v in got["new"]]
+        compute = torch.cuda.current_stream(self.device)
+        compute.wait_event(slot.copied)
+        # what is left must still be a signal the front-end accepts (more than n_fft / 2 samples); otherwise the utterance is kept whole
+        need = getattr(getattr(self.model, "preprocessor", None), "n_fft", 0) // 2
+        whole = [r for r in range(rows) if new[r] <= need < lens[r]]
+        for r in whole:
+            dev2[r, :lens[r]].copy_(dev[r, :lens[r]])
+            new[r] = lens[r]
+        if self.record_timestamps:
+            for r, it in enumerate(items):
+                if r in whole:
+                    self.timestamps[it.key] = [{"start": 0, "end": it.length}]
+                elif "segments" in got:
+                    self.timestamps[it.key] = [{"start": int(s["start"]), "end": int(s["end"])} for s in got["segments"][r]]
+                else:
+                    self.timestamps[it.key] = vad_mod.timestamps_from_labels(got["label"][r, :int(got["nframes"][r])].numpy(), it.length)
+        self.stats["utterances"] += rows
+        self.stats["batches"] += 1
+        self.stats["samples"] += sum(lens)
+        self.stats["speech_samples"] += sum(new)
+        self.stats["padded_samples"] += rows * max(new)
+        self.stats["native_reads"] += n_native
+        keys = [it.key for it in items]
+        x = dev2[:, :max(new)]
+        with torch.no_grad():
+            if self.pipelined:
+                return slot, keys, self.model.submit(x, lengths=new, norm_embedding=self.norm_embedding), rows
+            out = self.model(x, is_eval=True, norm_embedding=self.norm_embedding, lengths=new)
         return self._read_back(slot, keys, out, rows)
 
     def _finish(self, slot, keys, ticket, rows):
@@ -358,8 +465,18 @@ class StreamingExtractor:
         def finish_oldest():
             launched.append(self._finish(*inflight.popleft()))
 
+        uploaded = collections.deque()        # speech-only: batches whose copy + detector are queued, forward not yet launched
+
         def launch_oldest():
-            entry = self._launch(*staged.popleft().result())
+            if self.vad is None:
+                entry = self._launch(*staged.popleft().result())
+            else:
+                # upload batch k, then launch the forward of batch k - 1, whose lengths were asked for a whole batch ago
+                if staged:
+                    uploaded.append(self._upload_speech(*staged.popleft().result()))
+                if not uploaded or (len(uploaded) < 2 and staged):
+                    return
+                entry = self._launch_speech(*uploaded.popleft())
             if not self.pipelined:
                 launched.append(entry)
                 return
@@ -375,13 +492,13 @@ class StreamingExtractor:
             free.append(slot)
 
         try:
-            yield from self._run(entries, span, free, staged, launched, inflight, launch_oldest, collect_oldest)
+            yield from self._run(entries, span, free, staged, launched, inflight, launch_oldest, collect_oldest, uploaded)
         finally:
             if self.pipelined and inflight:       # abandoned half way (an exception, or the consumer stopped iterating): leave no ticket behind
                 inflight.clear()
                 self.model.discard_pending()
 
-    def _run(self, entries, span, free, staged, launched, inflight, launch_oldest, collect_oldest):
+    def _run(self, entries, span, free, staged, launched, inflight, launch_oldest, collect_oldest, uploaded):
         with concurrent.futures.ThreadPoolExecutor(self.workers) as pool, concurrent.futures.ThreadPoolExecutor(self.stage_ahead) as stager:
             while True:
                 chunk = list(itertools.islice(entries, span))
@@ -404,7 +521,7 @@ class StreamingExtractor:
                         launch_oldest()
                         while len(launched) + len(inflight) > self.pending:
                             yield from collect_oldest()
-            while staged:
+            while staged or uploaded:
                 launch_oldest()
             while launched or inflight:
                 yield from collect_oldest()
