@@ -253,6 +253,32 @@ int sc_topk_stats(const float* d_scores, int32_t n_rows, int32_t n_cols, int32_t
 int sc_snorm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t,
                    const float* d_std_t, void* stream);
 
+/* Cohort score normalisation: znorm / tnorm / ztnorm (sidekit/score_normalization.py:44-117) and s-norm of an enrolment x test
+ * trial matrix (the general form of :120-140).
+ *
+ * sc_cohort_moments: for every row i of X (N x D) the mean and the population standard deviation (numpy's .std(), :69,90) of
+ *   v_ij = (<X_i, C_j> - col_shift[j]) * col_scale[j]    over the M cohort rows j   (col_shift = col_scale = NULL: shift 0, scale 1),
+ * formed from the accumulators of sc_cosine's GEMM: the N x M cohort score matrix is never written.  self_offset >= 0 drops the
+ * pair j == i + self_offset (X is rows [self_offset, self_offset + N) of C, the convention of sc_cosine_hist; the divisor of such a
+ * row is M - 1: the diagonal-free statistics of :64-66), < 0 keeps every pair.  The sums are float64, added in an order that depends
+ * on M alone (partials through the sc_* workspace, no floating-point atomics); the variance is clamped at 0.  D % 4 == 0.
+ * M == 0, or a row that keeps no pair, is SK_EARG; N == 0 does nothing. */
+int sc_cohort_moments(const float* d_X, int32_t N, const float* d_C, int32_t M, int32_t D, const float* d_col_shift,
+                      const float* d_col_scale, int32_t self_offset, float* d_mean, float* d_std, void* stream);
+
+/* In place, S: Ne x Nt.  Both pairs: the s-norm of sc_snorm_apply (the same bits).  The enrolment pair alone (d_mean_t = d_std_t =
+ * NULL): S[i][j] <- (S[i][j] - mean_e[i]) / std_e[i], z-norm (:70, applied per model).  The test pair alone:
+ * S[i][j] <- (S[i][j] - mean_t[j]) / std_t[j], t-norm (:91).  Neither: SK_EARG.  A zero std gives the inf / NaN IEEE division gives,
+ * as in the reference. */
+int sc_norm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t,
+                  const float* d_std_t, void* stream);
+
+/* Mean and population std of the rows (axis = 1: scoremat.mean(1) / .std(1), :68-69) or the columns (axis = 0: :89-90) of a
+ * rows x cols float32 score matrix; float64 sums in a fixed order.  skip_diag != 0 (square matrices only) leaves S[i][i] out and
+ * divides by n - 1 (:64-66). */
+int sc_matrix_moments(const float* d_S, int32_t rows, int32_t cols, int32_t axis, int32_t skip_diag, float* d_mean, float* d_std,
+                      void* stream);
+
 /* ---- PLDA training: sidekit.factor_analyser.FactorAnalyser.plda (sidekit/factor_analyser.py:830-932) ----------------------------
  * The device half of the EM: everything with an utterance (N) or class (C) dimension, in float64 on the f64 matrix cores; the D x D and
  * rank x rank algebra stays on the host (sidekit_amd/factor_analyser.py).  X is XT_F32 or XT_F64 and is widened in the load.  No

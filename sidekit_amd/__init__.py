@@ -26,7 +26,9 @@ _LAZY = {
     "cosine_scoring": "iv_scoring", "PLDA_scoring": "iv_scoring", "fast_PLDA_scoring": "iv_scoring", "full_PLDA_scoring": "iv_scoring",
     "mahalanobis_scoring": "iv_scoring", "two_covariance_scoring": "iv_scoring",
     "FactorAnalyser": "factor_analyser",
-    "asnorm": "score_normalization",
+    "asnorm": "score_normalization", "znorm": "score_normalization", "tnorm": "score_normalization", "ztnorm": "score_normalization",
+    "asnorm_trials": "score_normalization", "cohort_stats_device": "score_normalization", "znorm_device": "score_normalization",
+    "tnorm_device": "score_normalization", "snorm_device": "score_normalization", "ztnorm_device": "score_normalization",
     "vad_energy": "frontend.vad",
     "write_matrix_hdf5": "sidekit_io", "read_plda_hdf5": "sidekit_io", "write_plda_hdf5": "sidekit_io",
 }

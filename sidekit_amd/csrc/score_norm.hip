@@ -1,0 +1,272 @@
+// Cohort score normalisation: z-, t-, zt- and s-norm of a trial matrix (sidekit/score_normalization.py:44-117, and the
+// enrolment x test form of :120-140).
+//
+// What a normalisation needs from an impostor cohort is two numbers per enrolment (or test) vector: the mean and the standard
+// deviation of its scores against the cohort.  sc_cohort_moments forms them straight from the accumulators of the cosine GEMM
+// (f32 MFMA, the arithmetic of sc_cosine), so the (N x M) cohort score matrix is never written; sc_matrix_moments does the same for
+// a score matrix that already exists (the Scores-level mirrors); sc_norm_apply is the elementwise pass.  Sums are float64, partial
+// sums go through the sc_* workspace and are added in a fixed order: no floating-point atomics.
+#include "../../include/sidekit_amd.h"
+#include "kernels.h"
+
+namespace sk {
+
+// Tile: 128 cohort rows x 128 X rows per 256-thread workgroup, four waves of 64 x 64 (2 x 2 accumulator tiles), k-tiles of 32 through
+// LDS with the next k-tile prefetched into registers: the loop of gemm128_kernel.  The COHORT is the MFMA's row operand, so a lane's
+// 32 accumulator values per 32 x 32 tile are 32 cohort scores of ONE X row: its running sum and sum of squares are two doubles per
+// column tile (8 registers), not two per accumulator row (128).  a * b is commutative, so every score is the k-ordered FMA chain
+// sc_cosine computes.  A workgroup walks the `tiles_per_slab` cohort tiles of slab blockIdx.y; the slab size depends on M alone, so a
+// row's additions -- lane (i, q) order inside a tile, tiles in order, the two lane halves, the two cohort-side waves, then the slabs
+// in cohort_moments_final_kernel -- do not depend on N, on the row's place in its tile or on the launch.
+constexpr int CT = 128, CLD = 36;
+
+template <bool AFFINE>
+__global__ __launch_bounds__(256, 2) void cohort_moments_kernel(const float* __restrict__ X, int N, const float* __restrict__ C, int M, int D,
+                                                                const float* __restrict__ shift, const float* __restrict__ scale, long self_off,
+                                                                int tiles_per_slab, double* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) float Cs[CT * CLD];
+  __shared__ __attribute__((aligned(16))) float Xs[CT * CLD];
+  __shared__ double red[CT][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;   // wm: cohort side, wn: X side
+  const int n0 = blockIdx.x * CT;
+  const int tiles_m = (M + CT - 1) / CT, t0 = blockIdx.y * tiles_per_slab, t1 = t0 + tiles_per_slab < tiles_m ? t0 + tiles_per_slab : tiles_m;
+  const int nk = (D + 31) / 32;
+  const int srow = tid >> 3, sk4 = (tid & 7) * 4;   // 32 rows x 8 chunks per pass, four passes per operand
+  float4 rc[4], rx[4];
+  auto fetch = [&](int c0, int k0) {   // (the zero is a prvalue: a named float4 in the ternary makes it a select of ADDRESSES and the registers an array in scratch)
+    const int k = k0 + sk4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int row = srow + q * 32;
+      rc[q] = (c0 + row < M && k < D) ? *reinterpret_cast<const float4*>(C + (long)(c0 + row) * D + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+      rx[q] = (n0 + row < N && k < D) ? *reinterpret_cast<const float4*>(X + (long)(n0 + row) * D + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
+  fetch(t0 * CT, 0);
+  for (int t = t0; t < t1; ++t) {
+    const int c0 = t * CT;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+    for (int kt = 0; kt < nk; ++kt) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        *reinterpret_cast<float4*>(&Cs[(srow + q * 32) * CLD + sk4]) = rc[q];
+        *reinterpret_cast<float4*>(&Xs[(srow + q * 32) * CLD + sk4]) = rx[q];
+      }
+      __syncthreads();
+      const bool wrap = kt + 1 == nk;           // then: the next cohort tile's first k-tile
+      if (!wrap || t + 1 < t1) fetch(wrap ? c0 + CT : c0, wrap ? 0 : (kt + 1) * 32);
+#pragma unroll
+      for (int kk = 0; kk < 32; kk += 8) {
+        float4 a[2], b[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          a[i] = *reinterpret_cast<const float4*>(&Cs[(wm * 64 + i * 32 + r) * CLD + kk + 4 * h]);
+          b[i] = *reinterpret_cast<const float4*>(&Xs[(wn * 64 + i * 32 + r) * CLD + kk + 4 * h]);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
+      }
+      __syncthreads();
+    }
+    // acc[i][j][q] = <C[c0 + wm*64 + i*32 + (q&3) + 8*(q>>2) + 4*h], X[n0 + wn*64 + j*32 + r]>
+    // (a dropped value enters the sums as an exact zero: the kept values' additions are unchanged by it)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const long drop = self_off >= 0 ? (long)(n0 + wn * 64 + j * 32 + r) + self_off : -1L;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int m = c0 + wm * 64 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+          double v = (double)acc[i][j][q];
+          if constexpr (AFFINE) {
+            const int mc = m < M ? m : M - 1;
+            v = (v - (double)shift[mc]) * (double)scale[mc];
+          }
+          v = (m < M && (long)m != drop) ? v : 0.0;
+          s1[j] += v;
+          s2[j] = fma(v, v, s2[j]);
+        }
+    }
+  }
+  // the two lane halves hold the two interleaved halves of a tile's cohort rows, the two wm waves its two 64-row halves
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    s1[j] += __shfl_xor(s1[j], 32);
+    s2[j] += __shfl_xor(s2[j], 32);
+    if (wm == 1 && h == 0) { red[wn * 64 + j * 32 + r][0] = s1[j]; red[wn * 64 + j * 32 + r][1] = s2[j]; }
+  }
+  __syncthreads();
+  if (wm == 0 && h == 0) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int row = wn * 64 + j * 32 + r, n = n0 + row;
+      if (n >= N) continue;
+      double* o = part + ((long)blockIdx.y * N + n) * 2;
+      o[0] = s1[j] + red[row][0];
+      o[1] = s2[j] + red[row][1];
+    }
+  }
+}
+
+// mean and population std of the values a row kept: the slabs' partials in slab order, variance clamped at 0
+__global__ __launch_bounds__(256) void cohort_moments_final_kernel(const double* __restrict__ part, int N, int slabs, int M, long self_off,
+                                                                   float* __restrict__ mean, float* __restrict__ stdv) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  double a = 0.0, b = 0.0;
+  for (int p = 0; p < slabs; ++p) {
+    a += part[((long)p * N + i) * 2];
+    b += part[((long)p * N + i) * 2 + 1];
+  }
+  const long d = self_off >= 0 ? (long)i + self_off : -1L;
+  const double cnt = (double)(M - ((d >= 0 && d < (long)M) ? 1 : 0));
+  const double m = a / cnt, var = b / cnt - m * m;
+  mean[i] = (float)m;
+  stdv[i] = (float)sqrt(var > 0.0 ? var : 0.0);
+}
+
+// ---- moments of a score matrix that exists (the Scores-level mirrors) ------------------------------------------------------------
+// per row: one workgroup per row, every thread a strided float64 partial, the 256 partials added in thread order
+__global__ __launch_bounds__(256) void row_moments_kernel(const float* __restrict__ S, int cols, int skip_diag, float* __restrict__ mean,
+                                                          float* __restrict__ stdv) {
+  __shared__ double red[2 * 256];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* x = S + (long)row * cols;
+  double s1 = 0.0, s2 = 0.0;
+  for (int c = tid; c < cols; c += 256) {
+    if (skip_diag && c == row) continue;
+    const double v = (double)x[c];
+    s1 += v;
+    s2 = fma(v, v, s2);
+  }
+  red[tid] = s1; red[256 + tid] = s2;
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0, b = 0.0;
+    for (int q = 0; q < 256; ++q) { a += red[q]; b += red[256 + q]; }
+    const double cnt = (double)(cols - (skip_diag ? 1 : 0));
+    const double m = a / cnt, var = b / cnt - m * m;
+    mean[row] = (float)m;
+    stdv[row] = (float)sqrt(var > 0.0 ? var : 0.0);
+  }
+}
+
+// per column: 64 columns x 4 row phases per workgroup (coalesced 256-B row segments); a phase sums its rows in order, the four phases
+// are added in phase order
+__global__ __launch_bounds__(256) void col_moments_kernel(const float* __restrict__ S, int rows, int cols, int skip_diag, float* __restrict__ mean,
+                                                          float* __restrict__ stdv) {
+  __shared__ double red[4][64][2];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
+  double s1 = 0.0, s2 = 0.0;
+  if (c < cols)
+    for (int rr = ph; rr < rows; rr += 4) {
+      if (skip_diag && rr == c) continue;
+      const double v = (double)S[(long)rr * cols + c];
+      s1 += v;
+      s2 = fma(v, v, s2);
+    }
+  red[ph][threadIdx.x & 63][0] = s1; red[ph][threadIdx.x & 63][1] = s2;
+  __syncthreads();
+  if (ph == 0 && c < cols) {
+    double a = 0.0, b = 0.0;
+    for (int p = 0; p < 4; ++p) { a += red[p][threadIdx.x][0]; b += red[p][threadIdx.x][1]; }
+    const double cnt = (double)(rows - (skip_diag ? 1 : 0));
+    const double m = a / cnt, var = b / cnt - m * m;
+    mean[c] = (float)m;
+    stdv[c] = (float)sqrt(var > 0.0 ? var : 0.0);
+  }
+}
+
+// S[i][j] <- (S[i][j] - m[k]) / s[k],  k = i (z-norm) or j (t-norm)
+template <bool BY_ROW>
+__global__ void norm_apply_kernel(float* __restrict__ S, int ne, int nt, const float* __restrict__ m, const float* __restrict__ s) {
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= (long)ne * nt) return;
+  const int k = BY_ROW ? (int)(i / nt) : (int)(i % nt);
+  S[i] = (S[i] - m[k]) / s[k];
+}
+
+}  // namespace sk
+
+using namespace sk;
+
+extern "C" {
+
+int sc_cohort_moments(const float* d_X, int32_t N, const float* d_C, int32_t M, int32_t D, const float* d_col_shift, const float* d_col_scale,
+                      int32_t self_offset, float* d_mean, float* d_std, void* stream) {
+  SK_CHECK(N >= 0 && M > 0 && D > 0 && D % 4 == 0, SK_EARG, "sc_cohort_moments: need N >= 0, M > 0 and D a positive multiple of 4 (N=%d, M=%d, D=%d)", N, M, D);
+  SK_CHECK((d_col_shift == nullptr) == (d_col_scale == nullptr), SK_EARG, "sc_cohort_moments: col_shift and col_scale come together or not at all");
+  SK_CHECK(!(M == 1 && self_offset == 0 && N > 0), SK_EARG, "sc_cohort_moments: row 0 keeps no pair (M = 1 and self_offset = 0)");
+  if (N == 0) return SK_OK;
+  SK_CHECK(d_X && d_C && d_mean && d_std, SK_EARG, "sc_cohort_moments: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  // the slab size is a function of M alone (at most 64 slabs, at least two cohort tiles each): N = 1000 against M = 20 000 is
+  // 8 row tiles x 53 slabs of workgroups, and a row's summation order is the same whatever N it arrives with
+  const int tiles_m = cdiv(M, CT), per = tiles_m > 128 ? cdiv(tiles_m, 64) : 2, slabs = cdiv(tiles_m, per);
+  constexpr int ROWS = 32768;   // rows per launch: bounds the partials at slabs x 32768 x 16 B (32 MB at 64 slabs)
+  const int rows_max = N < ROWS ? N : ROWS;
+  void* ws = nullptr;
+  std::lock_guard<std::mutex> lock(g_plda_mu);   // held until every launch is enqueued (see plda_workspace_locked)
+  SK_TRY(plda_workspace_locked(st, (size_t)slabs * rows_max * 16, &ws));
+  for (int r0 = 0; r0 < N; r0 += ROWS) {
+    const int n = N - r0 < ROWS ? N - r0 : ROWS;
+    const long self_off = self_offset >= 0 ? (long)self_offset + r0 : -1L;
+    const float* x = d_X + (long)r0 * D;
+    const dim3 grid(cdiv(n, CT), slabs);
+    if (d_col_shift) hipLaunchKernelGGL(cohort_moments_kernel<true>, grid, dim3(256), 0, st, x, n, d_C, M, D, d_col_shift, d_col_scale, self_off, per, (double*)ws);
+    else hipLaunchKernelGGL(cohort_moments_kernel<false>, grid, dim3(256), 0, st, x, n, d_C, M, D, d_col_shift, d_col_scale, self_off, per, (double*)ws);
+    SK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cohort_moments_final_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const double*)ws, n, slabs, M, self_off, d_mean + r0, d_std + r0);
+    SK_HIP(hipGetLastError());
+  }
+  return SK_OK;
+}
+
+int sc_matrix_moments(const float* d_S, int32_t rows, int32_t cols, int32_t axis, int32_t skip_diag, float* d_mean, float* d_std, void* stream) {
+  SK_CHECK(d_S && d_mean && d_std && rows > 0 && cols > 0 && (axis == 0 || axis == 1), SK_EARG, "sc_matrix_moments: bad arguments (axis is 0 or 1)");
+  SK_CHECK(!skip_diag || (rows == cols && rows > 1), SK_EARG, "sc_matrix_moments: skip_diag needs a square matrix of at least 2 x 2 (%d x %d)", rows, cols);
+  hipStream_t st = (hipStream_t)stream;
+  if (axis == 1) hipLaunchKernelGGL(row_moments_kernel, dim3(rows), dim3(256), 0, st, d_S, cols, skip_diag ? 1 : 0, d_mean, d_std);
+  else hipLaunchKernelGGL(col_moments_kernel, dim3(cdiv(cols, 64)), dim3(256), 0, st, d_S, rows, cols, skip_diag ? 1 : 0, d_mean, d_std);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
+int sc_norm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t, const float* d_std_t,
+                  void* stream) {
+  const bool e = d_mean_e && d_std_e, t = d_mean_t && d_std_t;
+  SK_CHECK(d_S && Ne > 0 && Nt > 0 && (e || t), SK_EARG, "sc_norm_apply: need the matrix and at least one (mean, std) pair");
+  SK_CHECK((d_mean_e == nullptr) == (d_std_e == nullptr) && (d_mean_t == nullptr) == (d_std_t == nullptr), SK_EARG,
+           "sc_norm_apply: a mean and its std come together");
+  if (e && t) return sc_snorm_apply(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);   // the same kernel: the same bits
+  const dim3 grid((unsigned)(((long)Ne * Nt + 255) / 256));
+  if (e) hipLaunchKernelGGL(norm_apply_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d_S, Ne, Nt, d_mean_e, d_std_e);
+  else hipLaunchKernelGGL(norm_apply_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d_S, Ne, Nt, d_mean_t, d_std_t);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
+}  // extern "C"

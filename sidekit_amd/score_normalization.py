@@ -1,12 +1,22 @@
-"""Adaptive symmetric score normalisation -- mirror of ``sidekit.score_normalization.asnorm``
-(``sidekit/score_normalization.py:120-140``), the normalisation behind the reference's "norm EER"
-(``sidekit/nnet/xvector.py:261``).
+"""Score normalisation -- mirror of ``sidekit/score_normalization.py``: ``asnorm`` (:120-140, the normalisation behind the reference's
+"norm EER", ``sidekit/nnet/xvector.py:261``), ``znorm`` (:44-72), ``tnorm`` (:75-93) and ``ztnorm`` (:96-117), plus the device-level forms a
+real trial list needs: an enrolment x test matrix normalised against an impostor cohort without ever forming the cohort score matrix.
 
-All-vs-all cosine scores of the enrolment x-vectors, cohort scores against the L2-normalised cohort,
+``asnorm``: all-vs-all cosine scores of the enrolment x-vectors, cohort scores against the L2-normalised cohort,
 mean / std of each row's 200 best cohort scores, then the symmetric normalisation
 ``0.5 (s - m_i)/sd_i + 0.5 (s - m_j)/sd_j``.  On the GPU: two f32 MFMA GEMMs (``sc_cosine``), an exact
 radix-select top-k statistics kernel (``sc_topk_stats``) and an elementwise pass (``sc_snorm_apply``).
+
+Cohort statistics over the WHOLE cohort (z-, t-, zt-, plain s-norm) come from ``sc_cohort_moments``: per-row float64 sums taken from the
+accumulators of the cosine GEMM.  The adaptive (top-k) statistics need the scores themselves; they run over row blocks whose score buffer
+stays inside ``max_workspace_bytes``.  The ``Scores``-level functions receive host matrices: ``sc_matrix_moments`` + ``sc_norm_apply``.
+
+Two stated deviations from the reference's ``znorm`` ("Score normalisation"): the per-model statistics are applied
+along rows (the reference's line 70 broadcasts them along the segment axis: it raises unless the matrix is square, and then normalises
+columns), and with ``sym=True`` the std is the square root of the variance of the ``n - 1`` off-diagonal values (lines 64-66 omit the
+root and centre along the wrong axis).
 """
+import copy
 import ctypes
 
 import numpy
@@ -42,3 +52,231 @@ def asnorm(enrol_xv, cohort_xv, ndx=None, topk=200, device=None):
         _lib.check(lib.sc_topk_stats(calib.data_ptr(), n, c.shape[0], int(topk), mean.data_ptr(), std.data_ptr(), st))
         _lib.check(lib.sc_snorm_apply(scores.data_ptr(), n, n, mean.data_ptr(), std.data_ptr(), mean.data_ptr(), std.data_ptr(), st))
     return scores.cpu().numpy()
+
+
+# ---- device level ----------------------------------------------------------------------------------------------------------------
+_NO_GPU = "sidekit_amd computes on the GPU only (no CPU fallback) and no GPU is visible"
+
+
+def _shape2(x, what):
+    shape = tuple(x.shape)
+    if len(shape) != 2:
+        raise ValueError(f"{what} must be a matrix, got shape {shape}")
+    return shape
+
+
+def _check_xv(xv, cohort_xv, what="x-vectors"):
+    """Shape checks that need no device: (N, D) against (M, D), D a multiple of 4 (the GEMM's k granularity), a non-empty cohort."""
+    (n, d), (m, dc) = _shape2(xv, what), _shape2(cohort_xv, "cohort")
+    if dc != d or d % 4:
+        raise ValueError(f"x-vector dimension must match and be a multiple of 4 ({what}: {d}, cohort: {dc})")
+    if m == 0:
+        raise ValueError("the cohort is empty")
+    return n, m, d
+
+
+def _device_of(*xs):
+    if not torch.cuda.is_available():
+        raise RuntimeError(_NO_GPU)
+    for x in xs:
+        if torch.is_tensor(x) and x.is_cuda:
+            return x.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _f32(x, device):
+    return torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def cohort_stats_device(xv, cohort_xv, topk=None, self_offset=None, col_shift=None, col_scale=None, max_workspace_bytes=1 << 30,
+                        normalize=False):
+    """Per row of ``xv`` (N, D): ``(mean, std)`` of its cosine scores against the cohort (M, D), float32 **device tensors**; rows are used
+    as given (``normalize=True`` L2-normalises the cohort first, as the reference's ``asnorm`` does).
+
+    ``topk=None``: every cohort score counts, population std (``sc_cohort_moments``; the (N, M) scores are never stored).  ``self_offset``
+    drops the pair ``j == i + self_offset`` (``xv`` is a row range of the cohort); ``col_shift`` / ``col_scale`` (M each, together) turn
+    the scores into ``(s_ij - shift_j) * scale_j`` first: cohort scores that were themselves z-normalised, for zt-norm.
+    ``topk=k``: mean and unbiased std of the k best cohort scores (``sc_topk_stats``), over row blocks whose (rows, M) float32 score
+    buffer fits in ``max_workspace_bytes``."""
+    n, m, d = _check_xv(xv, cohort_xv)
+    if (col_shift is None) != (col_scale is None):
+        raise ValueError("col_shift and col_scale come together")
+    if topk is not None:
+        if self_offset is not None or col_shift is not None:
+            raise ValueError("self_offset / col_shift / col_scale apply to whole-cohort statistics (topk=None) only")
+        if not 1 < int(topk) <= m:
+            raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={m})")
+    if col_shift is not None and (tuple(col_shift.shape) != (m,) or tuple(col_scale.shape) != (m,)):
+        raise ValueError(f"col_shift and col_scale must have one entry per cohort row ({m})")
+    device = _device_of(xv, cohort_xv)
+    x = _f32(xv, device)
+    if normalize:
+        from .iv_scoring import normalize_rows_device
+        c = normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), device)
+    else:
+        c = _f32(cohort_xv, device)
+    mean = torch.empty(n, dtype=torch.float32, device=device)
+    std = torch.empty(n, dtype=torch.float32, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        st = _stream(device)
+        if topk is None:
+            shift = None if col_shift is None else _f32(col_shift, device)
+            scale = None if col_scale is None else _f32(col_scale, device)
+            _lib.check(lib.sc_cohort_moments(x.data_ptr(), n, c.data_ptr(), m, d, _ptr(shift), _ptr(scale),
+                                             -1 if self_offset is None else int(self_offset), mean.data_ptr(), std.data_ptr(), st))
+        elif n:
+            rows = max(1, min(n, int(max_workspace_bytes) // (4 * m)))
+            calib = torch.empty((rows, m), dtype=torch.float32, device=device)
+            for r0 in range(0, n, rows):
+                nr = min(rows, n - r0)
+                _lib.check(lib.sc_cosine(x[r0:].data_ptr(), nr, c.data_ptr(), m, d, calib.data_ptr(), st))
+                _lib.check(lib.sc_topk_stats(calib.data_ptr(), nr, m, int(topk), mean[r0:].data_ptr(), std[r0:].data_ptr(), st))
+    return mean, std
+
+
+def _check_scores(scores, ne, nt):
+    if not (torch.is_tensor(scores) and scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous()):
+        raise ValueError("scores must be a contiguous float32 device tensor (it is normalised in place)")
+    if scores.dim() != 2 or (ne is not None and scores.shape[0] != ne) or (nt is not None and scores.shape[1] != nt):
+        raise ValueError(f"scores have shape {tuple(scores.shape)}, the x-vectors say ({ne if ne is not None else 'any'}, {nt if nt is not None else 'any'})")
+
+
+def _apply(scores, enrol=None, test=None):
+    """``sc_norm_apply`` in place: ``enrol`` / ``test`` are (mean, std) pairs or None."""
+    me, se = enrol if enrol is not None else (None, None)
+    mt, sd = test if test is not None else (None, None)
+    with torch.cuda.device(scores.device):
+        _lib.check(_lib.lib().sc_norm_apply(scores.data_ptr(), scores.shape[0], scores.shape[1], _ptr(me), _ptr(se), _ptr(mt), _ptr(sd),
+                                            _stream(scores.device)))
+    return scores
+
+
+def znorm_device(scores, enroll_xv, cohort_xv, normalize=False):
+    """z-norm of a device (Ne, Nt) float32 score tensor, in place: ``(s_ij - m_i) / sd_i`` with the statistics of enrolment i's cohort scores."""
+    _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
+    _check_scores(scores, enroll_xv.shape[0], None)
+    return _apply(scores, enrol=cohort_stats_device(enroll_xv, cohort_xv, normalize=normalize))
+
+
+def tnorm_device(scores, test_xv, cohort_xv, normalize=False):
+    """t-norm, in place: ``(s_ij - m_j) / sd_j`` with the statistics of test segment j's cohort scores."""
+    _check_xv(test_xv, cohort_xv, "test x-vectors")
+    _check_scores(scores, None, test_xv.shape[0])
+    return _apply(scores, test=cohort_stats_device(test_xv, cohort_xv, normalize=normalize))
+
+
+def snorm_device(scores, enroll_xv, test_xv, cohort_xv, topk=None, normalize=False, max_workspace_bytes=1 << 30):
+    """s-norm, in place: ``0.5 ((s - m_i)/sd_i + (s - m_j)/sd_j)``; ``topk=k`` makes it adaptive (statistics of each side's k best
+    cohort scores, unbiased std, as ``asnorm``).  ``test_xv is enroll_xv`` computes the statistics once."""
+    _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
+    _check_xv(test_xv, cohort_xv, "test x-vectors")
+    _check_scores(scores, enroll_xv.shape[0], test_xv.shape[0])
+    if normalize:
+        from .iv_scoring import normalize_rows_device
+        cohort_xv = normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), scores.device)
+    e = cohort_stats_device(enroll_xv, cohort_xv, topk=topk, max_workspace_bytes=max_workspace_bytes)
+    t = e if test_xv is enroll_xv else cohort_stats_device(test_xv, cohort_xv, topk=topk, max_workspace_bytes=max_workspace_bytes)
+    return _apply(scores, enrol=e, test=t)
+
+
+def ztnorm_device(scores, enroll_xv, test_xv, cohort_xv, normalize=False):
+    """z-norm followed by t-norm against the z-normalised cohort (``ztnorm``, :96-117, with ``znorm`` as this module defines it), in place;
+    neither the cohort x cohort nor the cohort x test matrix is formed."""
+    _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
+    _check_xv(test_xv, cohort_xv, "test x-vectors")
+    _check_scores(scores, enroll_xv.shape[0], test_xv.shape[0])
+    if normalize:
+        from .iv_scoring import normalize_rows_device
+        cohort_xv = normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), scores.device)
+    cohort = _f32(cohort_xv, scores.device)
+    m_c, sd_c = cohort_stats_device(cohort, cohort, self_offset=0)                         # znorm(imp_test, imp_imp, sym=True): per cohort model
+    test = cohort_stats_device(test_xv, cohort, col_shift=m_c, col_scale=1.0 / sd_c)       # tnorm's statistics of the z-normalised imp_test
+    _apply(scores, enrol=cohort_stats_device(enroll_xv, cohort))                           # znorm(enrol_test, enrol_imp)
+    return _apply(scores, test=test)
+
+
+def asnorm_trials(enroll_xv, test_xv, cohort_xv, topk=200, normalize=True, max_workspace_bytes=1 << 30):
+    """Adaptive s-norm of an enrolment x test trial set: the (Ne, Nt) normalised cosine matrix as a float32 **device tensor**.  With
+    ``test_xv is enroll_xv`` this is ``asnorm``."""
+    _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
+    _check_xv(test_xv, cohort_xv, "test x-vectors")
+    if not 1 < int(topk) <= cohort_xv.shape[0]:
+        raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={cohort_xv.shape[0]})")
+    device = _device_of(enroll_xv, test_xv, cohort_xv)
+    e = _f32(enroll_xv, device)
+    t = e if test_xv is enroll_xv else _f32(test_xv, device)
+    scores = torch.empty((e.shape[0], t.shape[0]), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().sc_cosine(e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], scores.data_ptr(), _stream(device)))
+    return snorm_device(scores, e, t, cohort_xv, topk=topk, normalize=normalize, max_workspace_bytes=max_workspace_bytes)
+
+
+def matrix_moments_device(scoremat, axis, skip_diag=False):
+    """``(mean, std)`` (population std, float32 device tensors) of the rows (``axis=1``) or columns (``axis=0``) of a score matrix;
+    ``skip_diag`` (square matrices only) leaves the diagonal out and divides by ``n - 1``."""
+    rows, cols = _shape2(scoremat, "scoremat")
+    if axis not in (0, 1):
+        raise ValueError("axis is 0 or 1")
+    if skip_diag and (rows != cols or rows < 2):
+        raise ValueError(f"skip_diag needs a square matrix of at least 2 x 2, got {rows} x {cols}")
+    if rows == 0 or cols == 0:
+        raise ValueError("empty score matrix")
+    device = _device_of(scoremat)
+    s = _f32(scoremat, device)
+    n = rows if axis == 1 else cols
+    mean = torch.empty(n, dtype=torch.float32, device=device)
+    std = torch.empty(n, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().sc_matrix_moments(s.data_ptr(), rows, cols, int(axis), int(bool(skip_diag)), mean.data_ptr(), std.data_ptr(),
+                                                _stream(device)))
+    return mean, std
+
+
+# ---- Scores level: the reference's signatures ------------------------------------------------------------------------------------
+def _same_ids(a, b, what):
+    if a.shape != b.shape or not bool((a == b).all()):
+        raise ValueError(f"the two Scores objects do not share their {what}")
+
+
+def _normalised(scores, mat):
+    """``scores.scoremat`` <- the device result, in the matrix's own float type (the arithmetic was float32 on the GPU)."""
+    dtype = scores.scoremat.dtype if scores.scoremat.dtype.kind == "f" else numpy.float64
+    scores.scoremat = mat.cpu().numpy().astype(dtype)
+    return scores
+
+
+def znorm(enrol_test_scores, enrol_imp_scores, sym=False):
+    """``sidekit.score_normalization.znorm`` (:44-72): every model's scores minus the mean, over the std, of its impostor scores (rows of
+    ``enrol_imp_scores``; ``sym=True``: the two model sets are the same cohort, the diagonal is left out).  See the module docstring for
+    the two deviations from the reference's lines 64-70."""
+    scores_znorm = copy.deepcopy(enrol_test_scores)
+    scores_znorm.sort()
+    enrol_imp_scores.sort()
+    _same_ids(scores_znorm.modelset, enrol_imp_scores.modelset, "modelset")
+    if sym and enrol_imp_scores.scoremat.shape[0] != enrol_imp_scores.scoremat.shape[1]:
+        raise ValueError("sym=True needs a square impostor x impostor matrix")
+    stats = matrix_moments_device(enrol_imp_scores.scoremat, 1, skip_diag=sym)
+    return _normalised(scores_znorm, _apply(_f32(scores_znorm.scoremat, stats[0].device), enrol=stats))
+
+
+def tnorm(enrol_test_scores, imp_test_scores):
+    """``sidekit.score_normalization.tnorm`` (:75-93): every test segment's scores minus the mean, over the std, of the impostor models'
+    scores on that segment (columns of ``imp_test_scores``)."""
+    scores_tnorm = copy.deepcopy(enrol_test_scores)
+    scores_tnorm.sort()
+    imp_test_scores.sort()
+    _same_ids(scores_tnorm.segset, imp_test_scores.segset, "segset")
+    stats = matrix_moments_device(imp_test_scores.scoremat, 0)
+    return _normalised(scores_tnorm, _apply(_f32(scores_tnorm.scoremat, stats[0].device), test=stats))
+
+
+def ztnorm(enrol_test_scores, enrol_imp_scores, imp_test_scores, imp_imp_scores):
+    """``sidekit.score_normalization.ztnorm`` (:96-117): z-norm of the trials and of the impostor x test scores, then t-norm."""
+    z_enrol_test_scores = znorm(enrol_test_scores, enrol_imp_scores)
+    z_imp_test_scores = znorm(imp_test_scores, imp_imp_scores, sym=True)
+    return tnorm(z_enrol_test_scores, z_imp_test_scores)

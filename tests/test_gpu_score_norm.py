@@ -1,0 +1,284 @@
+"""Cohort score normalisation on the GPU: sc_cohort_moments / sc_norm_apply / sc_matrix_moments and the Python surface over them
+(sidekit_amd.score_normalization), against the reference's golden results and float64 numpy."""
+import ctypes
+import os
+import sys
+
+import numpy
+import pytest
+import torch
+
+from sidekit_amd import _lib
+from sidekit_amd import score_normalization as sn
+from sidekit_amd.bosaris import Scores
+
+pytestmark = pytest.mark.gpu
+TOL = dict(rtol=5e-5, atol=5e-5)      # normalised scores: the tolerance of the asnorm tests (same arithmetic, same 1 / std amplification)
+
+
+def _st(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _unit(rs, n, d):
+    x = rs.randn(n, d).astype(numpy.float32)
+    return x / numpy.linalg.norm(x, axis=1, keepdims=True)
+
+
+def _cosine(x, c):
+    """float32 products of sc_cosine, as float64 numpy"""
+    out = torch.empty((x.shape[0], c.shape[0]), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().sc_cosine(x.data_ptr(), x.shape[0], c.data_ptr(), c.shape[0], x.shape[1], out.data_ptr(), _st(x.device)))
+    return out.cpu().numpy().astype(numpy.float64)
+
+
+def _moments(x, c, shift=None, scale=None, self_offset=-1):
+    mean = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    std = torch.empty_like(mean)
+    _lib.check(_lib.lib().sc_cohort_moments(x.data_ptr(), x.shape[0], c.data_ptr(), c.shape[0], x.shape[1],
+                                            None if shift is None else shift.data_ptr(), None if scale is None else scale.data_ptr(),
+                                            self_offset, mean.data_ptr(), std.data_ptr(), _st(x.device)))
+    return mean, std
+
+
+def _ids(prefix, n):
+    return numpy.array([f"{prefix}{i:04d}" for i in range(n)], dtype="|O")
+
+
+def _scores(models, segs, mat, cls=Scores):
+    s = cls()
+    s.modelset, s.segset, s.scoremat, s.scoremask = models, segs, numpy.array(mat, dtype=numpy.float64), numpy.ones(mat.shape, dtype="bool")
+    return s
+
+
+@pytest.fixture(scope="module")
+def fx(golden_dir):
+    return dict(numpy.load(os.path.join(golden_dir, "score_norm.npz")))
+
+
+def test_golden_tnorm_znorm_asnorm(gpu, fx, golden_dir):
+    e, t, c = (torch.from_numpy(fx[k]).to(gpu) for k in ("enrol", "test", "cohort"))
+    s = torch.from_numpy(_cosine(e, t).astype(numpy.float32)).to(gpu)
+    got = sn.tnorm_device(s.clone(), t, c)
+    assert got.dtype == torch.float32 and got.is_cuda
+    numpy.testing.assert_allclose(got.cpu().numpy(), fx["tnorm"], **TOL)
+    numpy.testing.assert_allclose(sn.znorm_device(s.clone(), e, c).cpu().numpy(), fx["znorm"], **TOL)
+    # Scores level, from host matrices whose models / segments arrive unsorted
+    e64, t64, c64 = (fx[k].astype(numpy.float64) for k in ("enrol", "test", "cohort"))
+    rs = numpy.random.RandomState(1)
+    pe, pt, pc = rs.permutation(37), rs.permutation(53), rs.permutation(301)
+    em, ts, cm = _ids("enr", 37), _ids("tst", 53), _ids("imp", 301)
+    enrol_test = _scores(em[pe], ts[pt], (e64 @ t64.T)[pe][:, pt])
+    before = enrol_test.scoremat.copy()
+    tn = sn.tnorm(enrol_test, _scores(cm[pc], ts, (c64 @ t64.T)[pc]))
+    assert list(tn.modelset) == list(em) and list(tn.segset) == list(ts) and tn.scoremat.dtype == numpy.float64
+    numpy.testing.assert_allclose(tn.scoremat, fx["tnorm"], **TOL)
+    zn = sn.znorm(enrol_test, _scores(em, cm[pc], (e64 @ c64.T)[:, pc]))
+    assert list(zn.modelset) == list(em) and list(zn.segset) == list(ts)
+    numpy.testing.assert_allclose(zn.scoremat, fx["znorm"], **TOL)
+    numpy.testing.assert_array_equal(enrol_test.scoremat, before)                    # deep copy: the argument keeps its order and values
+    # the adaptive coincidence case: enrolment against itself is the reference's asnorm
+    ax = numpy.load(os.path.join(golden_dir, "asnorm.npz"))
+    en = torch.from_numpy(ax["enrol"]).to(gpu)
+    got = sn.asnorm_trials(en, en, torch.from_numpy(ax["cohort"]).to(gpu))
+    assert got.shape == (64, 64) and got.is_cuda
+    numpy.testing.assert_allclose(got.cpu().numpy(), ax["snorm"], **TOL)
+    numpy.testing.assert_allclose(got.cpu().numpy(), sn.asnorm(ax["enrol"], ax["cohort"]), **TOL)
+
+
+@pytest.mark.parametrize("N,M,D", [(1, 1, 4), (1, 257, 8), (255, 1, 256), (257, 513, 256), (300, 255, 132)])
+def test_cohort_moments_ragged_shapes(gpu, N, M, D):
+    """Shapes that straddle every tile edge, against float64 numpy on the float32 products of sc_cosine: 2e-6 absolute, the agreement
+    test_cosine_scoring_golden asks of the products themselves."""
+    rs = numpy.random.RandomState(N + M + D)
+    x, c = torch.from_numpy(_unit(rs, N, D)).to(gpu), torch.from_numpy(_unit(rs, M, D)).to(gpu)
+    mean, std = _moments(x, c)
+    s = _cosine(x, c)
+    numpy.testing.assert_allclose(mean.cpu().numpy(), s.mean(1), rtol=0, atol=2e-6)
+    numpy.testing.assert_allclose(std.cpu().numpy(), s.std(1), rtol=0, atol=2e-6)
+    if M == 1:
+        assert (std == 0).all()
+    m2, s2 = sn.cohort_stats_device(x, c)                                              # the Python entry: the same call
+    assert torch.equal(m2, mean) and torch.equal(s2, std)
+
+
+@pytest.mark.parametrize("r", [0, 255, 256])
+def test_cohort_moments_self_offset(gpu, r):
+    """X = rows [r, r + 300) of a 600-row cohort: the statistics of the explicit matrix with the pairs j == i + r masked out."""
+    n, M = 300, 600
+    c = torch.from_numpy(_unit(numpy.random.RandomState(5), M, 256)).to(gpu)
+    x = c[r:r + n].contiguous()
+    mean, std = _moments(x, c, self_offset=r)
+    s = _cosine(x, c)
+    keep = numpy.ones((n, M), dtype=bool)
+    keep[numpy.arange(n), numpy.arange(n) + r] = False
+    kept = s[keep].reshape(n, M - 1)
+    assert numpy.all(s[~keep] > 0.999)                                                 # the masked pairs are the self-scores
+    numpy.testing.assert_allclose(mean.cpu().numpy(), kept.mean(1), rtol=0, atol=2e-6)
+    numpy.testing.assert_allclose(std.cpu().numpy(), kept.std(1), rtol=0, atol=2e-6)
+
+
+def test_cohort_moments_col_shift_and_scale(gpu):
+    """The statistics of (S - shift) * scale formed explicitly in float64.  The kernel evaluates the same float64 expression on the same
+    float32 products; what is left is the order of float64 sums (1e-13 here) and the rounding of the two float32 results: 2^-23."""
+    rs = numpy.random.RandomState(6)
+    x, c = torch.from_numpy(_unit(rs, 257, 256)).to(gpu), torch.from_numpy(_unit(rs, 513, 256)).to(gpu)
+    shift = (0.1 * rs.randn(513)).astype(numpy.float32)
+    scale = rs.uniform(0.5, 20.0, 513).astype(numpy.float32)
+    mean, std = _moments(x, c, torch.from_numpy(shift).to(gpu), torch.from_numpy(scale).to(gpu))
+    v = (_cosine(x, c) - shift.astype(numpy.float64)) * scale.astype(numpy.float64)
+    numpy.testing.assert_allclose(mean.cpu().numpy(), v.mean(1), rtol=1.2e-7, atol=1e-9)
+    numpy.testing.assert_allclose(std.cpu().numpy(), v.std(1), rtol=1.2e-7, atol=1e-9)
+    m2, s2 = sn.cohort_stats_device(x, c, col_shift=torch.from_numpy(shift).to(gpu), col_scale=torch.from_numpy(scale).to(gpu))
+    assert torch.equal(m2, mean) and torch.equal(s2, std)
+
+
+def test_identical_cohort_rows_give_a_tiny_finite_std(gpu):
+    """64 identical cohort rows: the variance is a difference of two float64 roundings of a sum of 64 squares no larger than 1."""
+    rs = numpy.random.RandomState(7)
+    x = torch.from_numpy(_unit(rs, 130, 256)).to(gpu)
+    c = torch.from_numpy(numpy.repeat(_unit(rs, 1, 256), 64, axis=0)).to(gpu)
+    mean, std = _moments(x, c)
+    assert torch.isfinite(std).all() and (std >= 0).all() and (std <= 1e-6).all(), std.max()
+    numpy.testing.assert_allclose(mean.cpu().numpy(), _cosine(x, c)[:, 0], rtol=0, atol=2e-6)
+
+
+def test_cohort_moments_bits_do_not_depend_on_stream_or_on_n(gpu):
+    rs = numpy.random.RandomState(8)
+    c = torch.from_numpy(_unit(rs, 600, 256)).to(gpu)
+    x = c[100:400].contiguous()
+    whole = _moments(x, c, self_offset=100)
+    torch.cuda.synchronize()
+    for _ in range(2):
+        stream = torch.cuda.Stream(device=gpu)
+        with torch.cuda.stream(stream):
+            again = _moments(x, c, self_offset=100)
+        stream.synchronize()
+        assert torch.equal(again[0], whole[0]) and torch.equal(again[1], whole[1])
+    lo, hi = _moments(x[:150].contiguous(), c, self_offset=100), _moments(x[150:].contiguous(), c, self_offset=250)
+    assert torch.equal(torch.cat((lo[0], hi[0])), whole[0]) and torch.equal(torch.cat((lo[1], hi[1])), whole[1])
+    odd = _moments(x[77:].contiguous(), c, self_offset=177)                            # another place in the tile, the same bits
+    assert torch.equal(odd[0], whole[0][77:]) and torch.equal(odd[1], whole[1][77:])
+
+
+def test_norm_apply(gpu):
+    """Both pairs: the bits of sc_snorm_apply.  One pair: one float32 subtraction and one division, both correctly rounded, so numpy's
+    float32 result to one unit in the last place; a zero std gives numpy's inf / NaN."""
+    lib = _lib.lib()
+    rs = numpy.random.RandomState(9)
+    ne, nt = 37, 53
+    S = rs.randn(ne, nt).astype(numpy.float32)
+    me, se = rs.randn(ne).astype(numpy.float32), rs.uniform(0.1, 2, ne).astype(numpy.float32)
+    mt, sd = rs.randn(nt).astype(numpy.float32), rs.uniform(0.1, 2, nt).astype(numpy.float32)
+    se[3] = 0.0
+    sd[5] = 0.0
+    S[3, 0] = me[3]                                                                    # 0 / 0
+    S[1, 5] = mt[5]
+    d = {k: torch.from_numpy(v).to(gpu) for k, v in dict(me=me, se=se, mt=mt, sd=sd).items()}
+
+    def apply(fn, *ptrs):
+        s = torch.from_numpy(S).to(gpu)
+        _lib.check(fn(s.data_ptr(), ne, nt, *[None if p is None else p.data_ptr() for p in ptrs], _st(gpu)))
+        return s.cpu().numpy()
+
+    both = apply(lib.sc_norm_apply, d["me"], d["se"], d["mt"], d["sd"])
+    numpy.testing.assert_array_equal(both.view(numpy.uint32), apply(lib.sc_snorm_apply, d["me"], d["se"], d["mt"], d["sd"]).view(numpy.uint32))
+    with numpy.errstate(divide="ignore", invalid="ignore"):
+        want_z, want_t = (S - me[:, None]) / se[:, None], (S - mt) / sd
+    z = apply(lib.sc_norm_apply, d["me"], d["se"], None, None)
+    t = apply(lib.sc_norm_apply, None, None, d["mt"], d["sd"])
+    assert numpy.isnan(z[3, 0]) and numpy.isinf(z[3, 1:]).all() and numpy.isnan(t[1, 5]) and numpy.isinf(t[0, 5])
+    numpy.testing.assert_allclose(z, want_z, rtol=1.2e-7, atol=0)
+    numpy.testing.assert_allclose(t, want_t, rtol=1.2e-7, atol=0)
+    s = torch.from_numpy(S).to(gpu)
+    assert lib.sc_norm_apply(s.data_ptr(), ne, nt, None, None, None, None, _st(gpu)) == _lib.SK_EARG
+
+
+@pytest.mark.parametrize("rows,cols", [(37, 53), (129, 129)])
+def test_matrix_moments(gpu, rows, cols):
+    """float64 numpy on the same float32 values; what is left is the rounding of the float32 results."""
+    S = (0.3 * numpy.random.RandomState(rows).randn(rows, cols)).astype(numpy.float32)
+    s64 = S.astype(numpy.float64)
+    for axis in (0, 1):
+        mean, std = sn.matrix_moments_device(torch.from_numpy(S).to(gpu), axis)
+        numpy.testing.assert_allclose(mean.cpu().numpy(), s64.mean(axis), rtol=1.2e-7, atol=1e-9)
+        numpy.testing.assert_allclose(std.cpu().numpy(), s64.std(axis), rtol=1.2e-7, atol=1e-9)
+        if rows != cols:
+            with pytest.raises(ValueError):
+                sn.matrix_moments_device(torch.from_numpy(S).to(gpu), axis, skip_diag=True)
+            continue
+        off = s64[~numpy.eye(rows, dtype=bool)].reshape(rows, rows - 1) if axis == 1 else s64.T[~numpy.eye(rows, dtype=bool)].reshape(rows, rows - 1)
+        mean, std = sn.matrix_moments_device(torch.from_numpy(S).to(gpu), axis, skip_diag=True)
+        numpy.testing.assert_allclose(mean.cpu().numpy(), off.mean(1), rtol=1.2e-7, atol=1e-9)
+        numpy.testing.assert_allclose(std.cpu().numpy(), off.std(1), rtol=1.2e-7, atol=1e-9)
+
+
+def test_ztnorm_device_against_scores_level_and_float64(gpu, fx):
+    """zt-norm with (Ne, Nt, M) = (37, 53, 301).  UNPINNED by the reference: its znorm cannot normalise a non-square matrix
+    (score_normalization.py:70) and its sym=True statistics omit the square root (:64-66), so the yardstick is the float64 restatement
+    below of the definition DESIGN.md states, which the device form and the Scores-level form must both meet."""
+    e, t, c = (torch.from_numpy(fx[k]).to(gpu) for k in ("enrol", "test", "cohort"))
+    s, ei, it, ii = _cosine(e, t), _cosine(e, c), _cosine(c, t), _cosine(c, c)
+    M = 301
+    off = ~numpy.eye(M, dtype=bool)
+    z_s = (s - ei.mean(1)[:, None]) / ei.std(1)[:, None]
+    m_c = (ii * off).sum(1) / (M - 1)
+    sd_c = numpy.sqrt((((ii - m_c[:, None]) ** 2) * off).sum(1) / (M - 1))
+    z_it = (it - m_c[:, None]) / sd_c[:, None]
+    want = (z_s - z_it.mean(0)) / z_it.std(0)
+    got = sn.ztnorm_device(torch.from_numpy(s.astype(numpy.float32)).to(gpu), e, t, c)
+    numpy.testing.assert_allclose(got.cpu().numpy(), want, **TOL)
+    em, ts, cm = _ids("enr", 37), _ids("tst", 53), _ids("imp", M)
+    host = sn.ztnorm(_scores(em, ts, s), _scores(em, cm, ei), _scores(cm, ts, it), _scores(cm, cm, ii))
+    assert list(host.modelset) == list(em) and list(host.segset) == list(ts)
+    numpy.testing.assert_allclose(host.scoremat, want, **TOL)
+    numpy.testing.assert_allclose(host.scoremat, got.cpu().numpy(), **TOL)
+    plain = sn.snorm_device(torch.from_numpy(s.astype(numpy.float32)).to(gpu), e, t, c)          # whole-cohort s-norm, while the matrices are here
+    numpy.testing.assert_allclose(plain.cpu().numpy(), 0.5 * ((s - ei.mean(1)[:, None]) / ei.std(1)[:, None] + (s - it.mean(0)) / it.std(0)), **TOL)
+
+
+def test_adaptive_statistics_in_bounded_memory(gpu):
+    N, M, k, ws = 4096, 2048, 20, 1 << 20
+    rs = numpy.random.RandomState(10)
+    x, c = torch.from_numpy(_unit(rs, N, 256)).to(gpu), torch.from_numpy(_unit(rs, M, 256)).to(gpu)
+    whole = sn.cohort_stats_device(x, c, topk=k)
+    del whole
+    whole = sn.cohort_stats_device(x, c, topk=k)                                       # (N, M) scores in one block
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(gpu)
+    base = torch.cuda.memory_allocated(gpu)
+    blocked = sn.cohort_stats_device(x, c, topk=k, max_workspace_bytes=ws)             # 128 rows at a time
+    torch.cuda.synchronize()
+    rise = torch.cuda.max_memory_allocated(gpu) - base
+    assert rise <= ws + 2 * N * 4 + (1 << 20), rise
+    assert torch.equal(blocked[0], whole[0]) and torch.equal(blocked[1], whole[1])
+    torch.cuda.reset_peak_memory_stats(gpu)
+    base = torch.cuda.memory_allocated(gpu)
+    sn.cohort_stats_device(x, c)                                                       # whole-cohort statistics: no score buffer at all
+    torch.cuda.synchronize()
+    assert torch.cuda.max_memory_allocated(gpu) - base <= 2 * N * 4 + (1 << 20)
+    with pytest.raises(ValueError):
+        sn.cohort_stats_device(x[:4], c[:10], topk=20)
+
+
+def test_drop_in_names_after_install_as_sidekit(gpu, fx):
+    import sidekit_amd
+    saved = {k: v for k, v in sys.modules.items() if k == "sidekit" or k.startswith("sidekit.")}
+    try:
+        sidekit_amd.install_as_sidekit()
+        import sidekit
+        from sidekit.score_normalization import tnorm, znorm, ztnorm
+        assert sidekit.tnorm is tnorm and sidekit.znorm is znorm and sidekit.ztnorm is ztnorm
+        e64, t64, c64 = (fx[k].astype(numpy.float64) for k in ("enrol", "test", "cohort"))
+        em, ts, cm = _ids("enr", 37), _ids("tst", 53), _ids("imp", 301)
+        mk = lambda models, segs, mat: _scores(models, segs, mat, sidekit.bosaris.Scores)
+        tn = sidekit.score_normalization.tnorm(mk(em, ts, e64 @ t64.T), mk(cm, ts, c64 @ t64.T))
+        numpy.testing.assert_allclose(tn.scoremat, fx["tnorm"], **TOL)
+        zn = sidekit.score_normalization.znorm(mk(em, ts, e64 @ t64.T), mk(em, cm, e64 @ c64.T))
+        numpy.testing.assert_allclose(zn.scoremat, fx["znorm"], **TOL)
+        zt = sidekit.score_normalization.ztnorm(mk(em, ts, e64 @ t64.T), mk(em, cm, e64 @ c64.T), mk(cm, ts, c64 @ t64.T), mk(cm, cm, c64 @ c64.T))
+        assert isinstance(zt, sidekit.bosaris.Scores) and zt.validate() and zt.scoremat.shape == (37, 53) and numpy.isfinite(zt.scoremat).all()
+    finally:
+        for k in [k for k in sys.modules if k == "sidekit" or k.startswith("sidekit.")]:
+            del sys.modules[k]
+        sys.modules.update(saved)
