@@ -240,6 +240,19 @@ int sc_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, i
                    const int32_t* d_labels_t, int32_t self_offset, float lo, float hi, int32_t nbins, uint64_t* d_hist_tar,
                    uint64_t* d_hist_non, void* stream);
 
+/* The same histograms of cohort-normalised scores: every score of sc_cosine goes through the expression of sc_norm_apply before it
+ * is binned -- the enrolment pair alone (z-norm) (s - mean_e[i]) / std_e[i], the test pair alone (t-norm) (s - mean_t[j]) / std_t[j],
+ * both (s-norm, adaptive or not) 0.5 ((s - mean_e[i]) / std_e[i]) + 0.5 ((s - mean_t[j]) / std_t[j]) -- with IEEE float32 operations in
+ * that order, so the counts are exactly those of sc_cosine + sc_norm_apply + binning the matrix, which is never formed.  d_mean_e /
+ * d_std_e: Ne entries, d_mean_t / d_std_t: Nt entries (sc_cohort_moments or sc_topk_stats produce them); a mean and its std come
+ * together and at least one pair is given, anything else is SK_EARG.  A score that normalises to NaN (a zero or non-finite std) has no
+ * bin: callers check the stds first (sidekit_amd.iv_scoring.cosine_histograms does).  Everything else -- labels, self_offset, lo / hi /
+ * nbins, the stream contract -- is sc_cosine_hist's.  zt-norm (t-norm against a z-normalised cohort) is a different chain and not here. */
+int sc_cosine_hist_norm(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, const int32_t* d_labels_e,
+                        const int32_t* d_labels_t, int32_t self_offset, const float* d_mean_e, const float* d_std_e,
+                        const float* d_mean_t, const float* d_std_t, float lo, float hi, int32_t nbins, uint64_t* d_hist_tar,
+                        uint64_t* d_hist_non, void* stream);
+
 /* Speaker-mean enrolment + cosine over a listed trial set, sidekit/bin/compute_spk_cosine.py:18-26:
  * out[k] = <E[enr_idx[k]], T[tst_idx[k]]> / (|E| |T|), float32 in, float64 maths. */
 int sc_cosine_trials(const float* d_E, const float* d_T, int32_t D, const int32_t* d_enr_idx, const int32_t* d_tst_idx,

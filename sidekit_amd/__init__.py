@@ -29,6 +29,7 @@ _LAZY = {
     "asnorm": "score_normalization", "znorm": "score_normalization", "tnorm": "score_normalization", "ztnorm": "score_normalization",
     "asnorm_trials": "score_normalization", "cohort_stats_device": "score_normalization", "znorm_device": "score_normalization",
     "tnorm_device": "score_normalization", "snorm_device": "score_normalization", "ztnorm_device": "score_normalization",
+    "normalised_histograms": "score_normalization", "normalised_range_from_sample": "score_normalization",
     "vad_energy": "frontend.vad",
     "write_matrix_hdf5": "sidekit_io", "read_plda_hdf5": "sidekit_io", "write_plda_hdf5": "sidekit_io",
 }

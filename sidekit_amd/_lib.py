@@ -72,6 +72,7 @@ SIGNATURES = {
     "sc_release_workspace": (ctypes.c_int, []),
     "sc_normalize_rows": (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
     "sc_cosine_hist": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _I32, ctypes.c_float, ctypes.c_float, _I32, _P, _P, _P]),
+    "sc_cosine_hist_norm": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I32, _P, _P, _P]),
     "sc_cosine_trials": (ctypes.c_int, [_P, _P, _I32, _P, _P, _I64, _P, _P]),
     "sc_topk_stats": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
     "sc_snorm_apply": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),

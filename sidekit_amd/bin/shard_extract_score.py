@@ -9,8 +9,11 @@ set OF THOSE x-vectors is scored: the first ``--trials`` utterances are the enro
 (full trial mask, target = same synthetic speaker), the remainder trains the PLDA parameters.  Scoring is sharded by enrolment
 rows and stays on the device end to end: cosine (f32 MFMA) and fast PLDA (f64 MFMA) row blocks are gathered on rank 0, which
 prints EERs and timings as one JSON line.  ``--all-pairs`` adds the matrix-free path: every pair of the corpus scored into
-target / non-target histograms, the per-rank counts summed with one all-reduce.  Without ``torch.distributed.run`` it runs
-as a single rank.
+target / non-target histograms, the per-rank counts summed with one all-reduce.  ``--all-pairs-norm s|as`` adds the same for
+s-normalised (``as``: adaptive, the ``--norm-topk`` best cohort scores) scores, the reference's "norm EER" at a size where no
+score matrix fits: the last ``--norm-cohort`` rows of the corpus (PLDA training rows) are the cohort, every pair ``i != j`` of the rows
+before them is counted (``score_normalization.normalised_histograms``, row shards and the all-reduce as above).  Without
+``torch.distributed.run`` it runs as a single rank.
 
 The corpus: speaker s is a fixed set of sinusoids (``RandomState(0)``), an utterance adds per-utterance phases, amplitude
 jitter and white noise (a batch is generated on the device with seed ``1000 + index of its first utterance``) -- enough
@@ -113,6 +116,12 @@ def main(argv=None, model=None, scoring=None, keep=None):
                     help="score range of the all-pairs histograms; default: derived from a sample of THIS run's x-vectors.  Two runs that are to be "
                          "compared (fp32 against bf16, tests/test_gpu_eer_dtype.py) must be binned on the same edges: pass the first run's range to the second")
     ap.add_argument("--hist-bins", type=int, default=None, help="bins of the all-pairs histograms: 8192 (default, one pass) or a multiple of 8190 (that many passes / 8190)")
+    ap.add_argument("--all-pairs-norm", default=None, choices=["s", "as"],
+                    help="with --all-pairs: also the histograms of s-normalised (s) or adaptive s-normalised (as) scores against a cohort taken from the corpus")
+    ap.add_argument("--norm-cohort", type=int, default=2000, metavar="M", help="cohort of --all-pairs-norm: the last M rows of the corpus (at most utterances - 2 * trials)")
+    ap.add_argument("--norm-topk", type=int, default=200, metavar="K", help="--all-pairs-norm as: statistics of each row's K best cohort scores")
+    ap.add_argument("--norm-hist-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="range of the normalised histograms; default: from a sample of this run's normalised scores (as --hist-range: runs to be compared share it)")
     ap.add_argument("--seed", type=int, default=0, help="corpus seed: another draw of speaker labels, phases, amplitude jitter and noise for the same speaker table")
     ap.add_argument("--plda", default=None, help="PLDA (mu, F, Sigma): SIDEKIT HDF5 or .npz; default: moment estimate from the corpus")
     ap.add_argument("--plda-train", default="moments", choices=["moments", "em"],
@@ -122,6 +131,17 @@ def main(argv=None, model=None, scoring=None, keep=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL over xGMI; gloo for CPU rehearsals")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu only with an injected model / scoring module")
     args = ap.parse_args(argv)
+    if args.all_pairs_norm:
+        if not args.all_pairs:
+            ap.error("--all-pairs-norm requires --all-pairs")
+        if not 0 < args.norm_cohort <= args.utterances - 2 * args.trials:
+            ap.error(f"--norm-cohort {args.norm_cohort}: the cohort comes out of the {args.utterances - 2 * args.trials} PLDA training rows")
+        if args.utterances - args.norm_cohort < 2:
+            ap.error("--norm-cohort leaves no pair to score")
+        if args.all_pairs_norm == "as" and not 1 < args.norm_topk <= args.norm_cohort:
+            ap.error(f"--norm-topk {args.norm_topk}: need 1 < K <= --norm-cohort ({args.norm_cohort})")
+        if args.device != "cuda":
+            ap.error("--all-pairs-norm runs on the GPU (sidekit_amd.score_normalization has no CPU fallback)")
     scoring = iv_scoring if scoring is None else scoring
     assert args.utterances >= 2 * args.trials + 2 * args.speakers, "need utterances for enrolment, test and PLDA training"
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -242,12 +262,31 @@ def main(argv=None, model=None, scoring=None, keep=None):
         out["all_pairs_hist_range"] = [lo, hi]
         out["all_pairs_hist_bins"] = int(ht.shape[0])
         sync()
-        counts = torch.as_tensor(numpy.stack([ht, hn]).astype(numpy.int64), device=dev)
+        parts, t_norm = [ht, hn], 0.0
+        if args.all_pairs_norm:
+            # the same again for s-normalised scores: cohort = the last M rows, trials = every pair of the rows before them; a rank
+            # computes the statistics of the rows it needs (its enrolment shard, every test row) and its counts join the one all-reduce
+            from .. import score_normalization
+            t1 = time.perf_counter()
+            M = args.norm_cohort
+            corpus, cohort = xv[:N - M], xv[N - M:]
+            topk = args.norm_topk if args.all_pairs_norm == "as" else None
+            nlo, nhi = args.norm_hist_range if args.norm_hist_range else score_normalization.normalised_range_from_sample(corpus, corpus, cohort, "s", topk)
+            a2, b2 = shard_range(N - M, rank, world)
+            rows = corpus if (a2, b2) == (0, N - M) else corpus[a2:b2]          # one rank: the statistics are computed once
+            parts += score_normalization.normalised_histograms(rows, corpus, lab_d[a2:b2], lab_d[:N - M], cohort, "s", topk, self_offset=a2, lo=nlo, hi=nhi,
+                                                               bins=int(ht.shape[0]))
+            sync()
+            t_norm = time.perf_counter() - t1
+        counts = torch.as_tensor(numpy.stack(parts).astype(numpy.int64), device=dev)
         if dist.is_initialized():
             dist.all_reduce(counts)
-        t_hist = time.perf_counter() - t0
+        t_hist = time.perf_counter() - t0 - t_norm
         counts = counts.cpu().numpy()
-        out.update(all_pairs=int(counts.sum()), all_pairs_s=t_hist, all_pairs_eer=float(eer_from_histograms(counts[0], counts[1])))
+        out.update(all_pairs=int(counts[:2].sum()), all_pairs_s=t_hist, all_pairs_eer=float(eer_from_histograms(counts[0], counts[1])))
+        if args.all_pairs_norm:
+            out.update(all_pairs_norm=int(counts[2:].sum()), all_pairs_norm_kind=args.all_pairs_norm, all_pairs_norm_cohort=M,
+                       all_pairs_norm_hist_range=[nlo, nhi], all_pairs_norm_s=t_norm, all_pairs_norm_eer=float(eer_from_histograms(counts[2], counts[3])))
     if keep is not None:
         keep.update(xv=xv, labels=labels, tar=tar, plda=(mu, F, Sigma))
         if transforms is not None:

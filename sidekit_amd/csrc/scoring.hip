@@ -127,13 +127,27 @@ constexpr int HB = 8192;   // bins per histogram: 2 x 32 KB of LDS per workgroup
 // (64 x 64 tiles with load-then-compute kept the pipes 26 % busy, 128 x 128 with four waves 33 %).
 constexpr int HT = 256, HLD = 36, HTHREADS = 1024;
 
+// NORM: what stands between an accumulator and its bin.  HN_NONE: nothing (sc_cosine_hist).  The others (sc_cosine_hist_norm) apply a
+// cohort normalisation with per-row statistics, in the expressions of the kernels that normalise a score matrix that exists
+// (norm_apply_kernel<true>, norm_apply_kernel<false>, snorm_apply_kernel): the same accumulator through the same IEEE operations (the
+// library is built with -ffp-contract=off) is the same bits, so the counts are those of sc_cosine + sc_norm_apply + binning.  A tile's
+// 256 enrolment-side and 256 test-side (mean, std) go through 4 KB of LDS, once per tile; HN_NONE declares none of it.
+enum { HN_NONE = 0, HN_ENROL = 1, HN_TEST = 2, HN_BOTH = 3 };
+struct HistNorm { const float *me, *se, *mt, *st; };   // Ne, Ne, Nt, Nt entries; a side a mode does not use is never read
+
+template <int NORM>
 __global__ __launch_bounds__(HTHREADS) void cosine_hist_kernel(const float* __restrict__ E, int Ne, const float* __restrict__ T, int Nt, int D,
                                                                const int* __restrict__ le, const int* __restrict__ lt, int self_offset,
                                                                float lo, float inv_width, unsigned long long* __restrict__ hist_tar,
-                                                               unsigned long long* __restrict__ hist_non) {
+                                                               unsigned long long* __restrict__ hist_non, HistNorm nrm) {
   __shared__ unsigned hist[2 * HB];
   __shared__ __attribute__((aligned(16))) float Es[HT * HLD];
   __shared__ __attribute__((aligned(16))) float Ts[HT * HLD];
+  float* stat = nullptr;   // [0, HT): enrolment means, [HT, 2 HT): test means, then the two stds in the same order
+  if constexpr (NORM != HN_NONE) {
+    __shared__ float stat_lds[4 * HT];
+    stat = stat_lds;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5, wm = wave >> 2, wn = wave & 3;
   for (int i = tid; i < 2 * HB; i += HTHREADS) hist[i] = 0u;
@@ -172,6 +186,14 @@ __global__ __launch_bounds__(HTHREADS) void cosine_hist_kernel(const float* __re
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
     fetch(0);
+    float smean = 0.f, sstd = 1.f;   // thread t < 256: enrolment row m0 + t; 256 <= t < 512: test row n0 + t - 256 (rows past the end are never binned)
+    if constexpr (NORM != HN_NONE) {
+      if (tid < HT) {
+        if ((NORM & HN_ENROL) && m0 + tid < Ne) { smean = nrm.me[m0 + tid]; sstd = nrm.se[m0 + tid]; }
+      } else if (tid < 2 * HT) {
+        if ((NORM & HN_TEST) && n0 + tid - HT < Nt) { smean = nrm.mt[n0 + tid - HT]; sstd = nrm.st[n0 + tid - HT]; }
+      }
+    }
     for (int kt = 0; kt < nk; ++kt) {
       __syncthreads();            // every wave is done reading the previous k-tile
 #pragma unroll
@@ -207,18 +229,28 @@ __global__ __launch_bounds__(HTHREADS) void cosine_hist_kernel(const float* __re
           for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
       }
     }
+    if constexpr (NORM != HN_NONE) {   // the k loop's barriers lie between the previous tile's last read of `stat` and this write
+      if (tid < 2 * HT) { stat[tid] = smean; stat[2 * HT + tid] = sstd; }
+      __syncthreads();
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int n = n0 + wn * 64 + j * 32 + r;
       if (n >= Nt) continue;
       const int ln = lt[n];
+      float mtn = 0.f, stn = 1.f;
+      if constexpr ((NORM & HN_TEST) != 0) { mtn = stat[HT + wn * 64 + j * 32 + r]; stn = stat[3 * HT + wn * 64 + j * 32 + r]; }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int m = m0 + wm * 64 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+          const int lm = wm * 64 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * h, m = m0 + lm;
           if (m >= Ne || (self_offset >= 0 && m + self_offset == n)) continue;
-          int bin = (int)floorf((acc[i][j][q] - lo) * inv_width);
+          float v = acc[i][j][q];
+          if constexpr (NORM == HN_ENROL) v = (v - stat[lm]) / stat[2 * HT + lm];
+          if constexpr (NORM == HN_TEST) v = (v - mtn) / stn;
+          if constexpr (NORM == HN_BOTH) v = 0.5f * ((v - stat[lm]) / stat[2 * HT + lm]) + 0.5f * ((v - mtn) / stn);
+          int bin = (int)floorf((v - lo) * inv_width);
           bin = bin < 0 ? 0 : (bin >= HB ? HB - 1 : bin);
           atomicAdd(&hist[(le[m] == ln ? 0 : HB) + bin], 1u);
         }
@@ -348,6 +380,27 @@ int plda_workspace_locked(hipStream_t st, size_t bytes, void** out) {
   return SK_OK;
 }
 
+// the persistent launch of both histogram entry points: counters zeroed on the stream, one workgroup per CU (at most one per tile)
+template <int NORM>
+static int launch_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, const int32_t* d_labels_e,
+                              const int32_t* d_labels_t, int32_t self_offset, HistNorm nrm, float lo, float hi, uint64_t* d_hist_tar,
+                              uint64_t* d_hist_non, hipStream_t st) {
+  SK_HIP(hipMemsetAsync(d_hist_tar, 0, (size_t)HB * 8, st));
+  SK_HIP(hipMemsetAsync(d_hist_non, 0, (size_t)HB * 8, st));
+  int dev = 0, cus = 256;   // the CU count of the device the stream belongs to (the NULL stream: the current device)
+  hipDevice_t sdev;
+  if (st && hipStreamGetDevice(st, &sdev) == hipSuccess) dev = (int)sdev;
+  else (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (cus <= 0) cus = 256;
+  const long ntiles = (long)cdiv(Ne, HT) * cdiv(Nt, HT);
+  const int grid = (int)(ntiles < (long)cus ? ntiles : (long)cus);   // persistent: one workgroup per CU (64 KB of histograms + 74 KB of operand tiles)
+  hipLaunchKernelGGL(cosine_hist_kernel<NORM>, dim3(grid), dim3(HTHREADS), 0, st, d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, lo,
+                     (float)HB / (hi - lo), (unsigned long long*)d_hist_tar, (unsigned long long*)d_hist_non, nrm);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
 }  // namespace sk
 
 using namespace sk;
@@ -425,21 +478,25 @@ int sc_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, i
   SK_CHECK(d_E && d_T && d_labels_e && d_labels_t && d_hist_tar && d_hist_non && Ne > 0 && Nt > 0 && D > 0 && D % 4 == 0, SK_EARG,
            "sc_cosine_hist: bad arguments (D must be a multiple of 4)");
   SK_CHECK(nbins == HB && hi > lo, SK_EARG, "sc_cosine_hist: nbins must be %d and hi > lo", HB);
+  return launch_cosine_hist<HN_NONE>(d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, HistNorm{nullptr, nullptr, nullptr, nullptr}, lo, hi,
+                                     d_hist_tar, d_hist_non, (hipStream_t)stream);
+}
+
+int sc_cosine_hist_norm(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, const int32_t* d_labels_e, const int32_t* d_labels_t,
+                        int32_t self_offset, const float* d_mean_e, const float* d_std_e, const float* d_mean_t, const float* d_std_t, float lo,
+                        float hi, int32_t nbins, uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream) {
+  SK_CHECK(d_E && d_T && d_labels_e && d_labels_t && d_hist_tar && d_hist_non && Ne > 0 && Nt > 0 && D > 0 && D % 4 == 0, SK_EARG,
+           "sc_cosine_hist_norm: bad arguments (D must be a multiple of 4)");
+  SK_CHECK(nbins == HB && hi > lo, SK_EARG, "sc_cosine_hist_norm: nbins must be %d and hi > lo", HB);
+  const bool e = d_mean_e && d_std_e, t = d_mean_t && d_std_t;   // sc_norm_apply's rules
+  SK_CHECK((d_mean_e == nullptr) == (d_std_e == nullptr) && (d_mean_t == nullptr) == (d_std_t == nullptr), SK_EARG,
+           "sc_cosine_hist_norm: a mean and its std come together");
+  SK_CHECK(e || t, SK_EARG, "sc_cosine_hist_norm: need at least one (mean, std) pair");
+  const HistNorm nrm{d_mean_e, d_std_e, d_mean_t, d_std_t};
   hipStream_t st = (hipStream_t)stream;
-  SK_HIP(hipMemsetAsync(d_hist_tar, 0, (size_t)HB * 8, st));
-  SK_HIP(hipMemsetAsync(d_hist_non, 0, (size_t)HB * 8, st));
-  int dev = 0, cus = 256;   // the CU count of the device the stream belongs to (the NULL stream: the current device)
-  hipDevice_t sdev;
-  if (st && hipStreamGetDevice(st, &sdev) == hipSuccess) dev = (int)sdev;
-  else (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (cus <= 0) cus = 256;
-  const long ntiles = (long)cdiv(Ne, HT) * cdiv(Nt, HT);
-  const int grid = (int)(ntiles < (long)cus ? ntiles : (long)cus);   // persistent: one workgroup per CU (64 KB of histograms + 74 KB of operand tiles)
-  hipLaunchKernelGGL(cosine_hist_kernel, dim3(grid), dim3(HTHREADS), 0, st, d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, lo,
-                     (float)HB / (hi - lo), (unsigned long long*)d_hist_tar, (unsigned long long*)d_hist_non);
-  SK_HIP(hipGetLastError());
-  return SK_OK;
+  if (e && t) return launch_cosine_hist<HN_BOTH>(d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, nrm, lo, hi, d_hist_tar, d_hist_non, st);
+  if (e) return launch_cosine_hist<HN_ENROL>(d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, nrm, lo, hi, d_hist_tar, d_hist_non, st);
+  return launch_cosine_hist<HN_TEST>(d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, nrm, lo, hi, d_hist_tar, d_hist_non, st);
 }
 
 int sc_cosine_trials(const float* d_E, const float* d_T, int32_t D, const int32_t* d_enr_idx, const int32_t* d_tst_idx, int64_t n_trials,

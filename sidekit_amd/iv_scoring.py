@@ -106,14 +106,39 @@ def plda_matrix(enroll_vectors, test_vectors, Phi, Psi, cst, scaling_factor=1., 
 HIST_BINS = 8192
 
 
-def cosine_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, self_offset=None, lo=-1.0, hi=1.0, device=None, bins=None):
+def _norm_pair(pair, n, side):
+    """A ``(mean, std)`` pair of ``cosine_histograms``: ``None``, or two vectors of ``n`` entries (checked without a device)."""
+    if pair is None:
+        return None
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] is None or pair[1] is None:
+        raise ValueError(f"{side}_norm is a (mean, std) pair: a mean comes with its std")
+    for name, v in zip(("mean", "std"), pair):
+        if tuple(v.shape) != (n,):
+            raise ValueError(f"{side}_norm: the {name} has shape {tuple(v.shape)}, the {side} side has {n} rows")
+    return pair
+
+
+def cosine_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, self_offset=None, lo=-1.0, hi=1.0, device=None, bins=None,
+                      enroll_norm=None, test_norm=None):
     """Target / non-target score histograms of ALL (enrol, test) pairs without materialising the (Ne, Nt) score matrix
     (SURVEY 8d: 100k x 100k cosine trials are 40 GB).  A trial is a target when the two integer labels are equal;
     ``self_offset=k`` drops the self-trials ``j == i + k`` when the enrolment side is rows ``[k, k + Ne)`` of the test side (``0`` for
     a set scored against itself, a shard's first row for one rank's block of it); ``None`` keeps every pair.  Returns two uint64 arrays of
     ``bins`` equal bins over ``[lo, hi)`` (scores outside land in the end bins); ``bosaris.detplot.eer_from_histograms`` turns them into the
     ROCCH EER.  ``bins``: ``HIST_BINS`` (8192, the kernel's LDS histograms: one pass over the pairs) or a multiple of ``HIST_BINS - 2``: that
-    many finer bins from ``bins / (HIST_BINS - 2)`` passes, each over a slice of the range with one guard bin either side."""
+    many finer bins from ``bins / (HIST_BINS - 2)`` passes, each over a slice of the range with one guard bin either side.
+
+    ``enroll_norm`` / ``test_norm``: ``(mean, std)`` float32 vectors, one entry per enrolment / test row (device tensors are used as
+    given; ``score_normalization.cohort_stats_device`` makes them).  The scores are then normalised before they are binned
+    (``sc_cosine_hist_norm``): ``enroll_norm`` alone is z-norm, ``test_norm`` alone t-norm, both s-norm -- the bits of ``sc_cosine``
+    followed by ``sc_norm_apply``.  A pair of the wrong length, a mean without its std, or a std that is not finite and positive (a NaN
+    score has no bin, and counting it somewhere would hide a broken cohort) raise ``ValueError`` before any launch; ``lo`` / ``hi`` are then
+    the range of the NORMALISED scores (``score_normalization.normalised_range_from_sample``).  Both ``None``: the raw scores, as before."""
+    if enroll_norm is not None or test_norm is not None:                              # what needs no device is said before one is touched
+        if len(enroll_vectors.shape) != 2 or len(test_vectors.shape) != 2 or enroll_vectors.shape[1] != test_vectors.shape[1] or enroll_vectors.shape[1] % 4:
+            raise ValueError("x-vector dimensions must match and be a multiple of 4")
+        enroll_norm = _norm_pair(enroll_norm, enroll_vectors.shape[0], "enroll")
+        test_norm = _norm_pair(test_norm, test_vectors.shape[0], "test")
     device = _device(device if device is not None else (enroll_vectors.device if torch.is_tensor(enroll_vectors) and enroll_vectors.is_cuda else None))
     e, t = _to_device(enroll_vectors, torch.float32, device), _to_device(test_vectors, torch.float32, device)
     if e.shape[1] % 4 or e.shape[1] != t.shape[1]:
@@ -127,14 +152,24 @@ def cosine_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, 
         raise AssertionError(f"bins must be {HIST_BINS} or a multiple of {inner}")
     if not float(hi) > float(lo):
         raise AssertionError("histogram range: hi must exceed lo")
+    normalised = enroll_norm is not None or test_norm is not None
+    if normalised:
+        stats = [None if pair is None else tuple(_to_device(v, torch.float32, device) for v in pair) for pair in (enroll_norm, test_norm)]
+        stds = torch.cat([pair[1] for pair in stats if pair is not None])
+        if not bool((torch.isfinite(stds) & (stds > 0)).all()):                     # one reduction, one scalar back
+            raise ValueError("cosine_histograms: every std of enroll_norm / test_norm must be finite and > 0")
+        norm_ptrs = tuple(None if pair is None else v.data_ptr() for pair in stats for v in (pair if pair is not None else (None, None)))
 
     def one_pass(a, b):
         ht = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
         hn = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
+        head = (e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], le.data_ptr(), lt.data_ptr(), -1 if self_offset is None else int(self_offset))
+        tail = (float(a), float(b), HIST_BINS, ht.data_ptr(), hn.data_ptr(), _stream(device))
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().sc_cosine_hist(e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], le.data_ptr(), lt.data_ptr(),
-                                                 -1 if self_offset is None else int(self_offset), float(a), float(b), HIST_BINS, ht.data_ptr(), hn.data_ptr(),
-                                                 _stream(device)), AssertionError)
+            if normalised:
+                _lib.check(_lib.lib().sc_cosine_hist_norm(*head, *norm_ptrs, *tail), AssertionError)
+            else:
+                _lib.check(_lib.lib().sc_cosine_hist(*head, *tail), AssertionError)
         return ht.cpu().numpy().astype(numpy.uint64), hn.cpu().numpy().astype(numpy.uint64)
 
     if bins == HIST_BINS:

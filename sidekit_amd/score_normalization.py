@@ -15,6 +15,12 @@ Two stated deviations from the reference's ``znorm`` ("Scor
 along rows (the reference's line 70 broadcasts them along the segment axis: it raises unless the matrix is square, and then normalises
 columns), and with ``sym=True`` the std is the square root of the variance of the ``n - 1`` off-diagonal values (lines 64-66 omit the
 root and centre along the wrong axis).
+
+``normalised_histograms`` is the form for trial sets whose (Ne, Nt) matrix does not fit: the z-, t-, s- or adaptive s-normalised scores of
+every pair counted into target / non-target histograms (``iv_scoring.cosine_histograms`` with the statistics of ``cohort_stats_device``;
+``sc_cosine_hist_norm`` normalises each score between the GEMM's accumulator and its bin, in ``sc_norm_apply``'s expressions, so the counts
+are those of the materialised path).  ``normalised_range_from_sample`` proposes its ``lo`` / ``hi``.  zt-norm is not offered there: it is a
+t-norm against a z-normalised cohort, a different chain of expressions from the three ``sc_norm_apply`` has.
 """
 import copy
 import ctypes
@@ -214,6 +220,85 @@ def asnorm_trials(enroll_xv, test_xv, cohort_xv, topk=200, normalize=True, max_w
     with torch.cuda.device(device):
         _lib.check(_lib.lib().sc_cosine(e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], scores.data_ptr(), _stream(device)))
     return snorm_device(scores, e, t, cohort_xv, topk=topk, normalize=normalize, max_workspace_bytes=max_workspace_bytes)
+
+
+def _check_kind(kind, topk, m):
+    if kind not in ("z", "t", "s"):
+        raise ValueError(f"kind is 'z', 't' or 's' (zt-norm has no histogram form), got {kind!r}")
+    if topk is not None:
+        if kind != "s":
+            raise ValueError("topk (adaptive statistics) goes with kind='s' only")
+        if not 1 < int(topk) <= m:
+            raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={m})")
+
+
+def _side_stats(kind, enroll_xv, test_xv, cohort, topk, max_workspace_bytes):
+    """(enrolment pair, test pair) of ``kind``: the side a kind does not use is ``None``; ``test_xv is enroll_xv`` computes once."""
+    e = cohort_stats_device(enroll_xv, cohort, topk=topk, max_workspace_bytes=max_workspace_bytes) if kind in ("z", "s") else None
+    if kind == "z":
+        return e, None
+    if kind == "s" and test_xv is enroll_xv:
+        return e, e
+    return e, cohort_stats_device(test_xv, cohort, topk=topk, max_workspace_bytes=max_workspace_bytes)
+
+
+def _cohort_on(device, cohort_xv, normalize):
+    if normalize:
+        from .iv_scoring import normalize_rows_device
+        return normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), device)
+    return _f32(cohort_xv, device)
+
+
+def normalised_histograms(enroll_xv, test_xv, enroll_labels, test_labels, cohort_xv, kind="s", topk=None, normalize=False, self_offset=None, *,
+                          lo=None, hi=None, bins=None, max_workspace_bytes=1 << 30):
+    """Target / non-target histograms ``(hist_tar, hist_non)`` of the cohort-normalised cosine scores of ALL (enrol, test) pairs; neither
+    the (Ne, Nt) score matrix nor (with ``topk=None``) a cohort score matrix is formed.  ``kind``: ``"z"`` (``znorm_device``'s
+    expression), ``"t"`` (``tnorm_device``'s) or ``"s"`` (``snorm_device``'s); ``topk=k``, with ``"s"`` only, is adaptive s-norm with
+    ``asnorm``'s unbiased std.  ``normalize=True`` L2-normalises the cohort first.  ``test_xv is enroll_xv`` computes the statistics once.
+    ``self_offset``, ``bins`` and the labels are ``iv_scoring.cosine_histograms``'s.  ``lo`` / ``hi`` are required keywords: normalised scores have
+    no natural range (``normalised_range_from_sample`` estimates one).  zt-norm is not offered (see the module docstring)."""
+    _, m, _ = _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
+    _check_xv(test_xv, cohort_xv, "test x-vectors")
+    _check_kind(kind, topk, m)
+    if lo is None or hi is None:
+        raise ValueError("lo and hi are required keywords: normalised scores have no default range (normalised_range_from_sample estimates one)")
+    if not float(hi) > float(lo):
+        raise ValueError("histogram range: hi must exceed lo")
+    from .iv_scoring import cosine_histograms
+    device = _device_of(enroll_xv, test_xv, cohort_xv)
+    e = _f32(enroll_xv, device)
+    t = e if test_xv is enroll_xv else _f32(test_xv, device)
+    en, tn = _side_stats(kind, e, t, _cohort_on(device, cohort_xv, normalize), topk, max_workspace_bytes)
+    return cosine_histograms(e, t, enroll_labels, test_labels, self_offset=self_offset, lo=lo, hi=hi, device=device, bins=bins,
+                             enroll_norm=en, test_norm=tn)
+
+
+def normalised_range_from_sample(enroll_xv, test_xv, cohort_xv, kind="s", topk=None, normalize=False):
+    """``(lo, hi)`` for ``normalised_histograms``: a strided sample of at most 2 048 rows per side, its materialised score matrix
+    normalised by ``znorm_device`` / ``tnorm_device`` / ``snorm_device`` against the whole cohort, and the sample's smallest and largest
+    normalised score, each widened by a quarter of the sampled range (what still falls outside is counted in the end bins)."""
+    _, m, _ = _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
+    _check_xv(test_xv, cohort_xv, "test x-vectors")
+    _check_kind(kind, topk, m)
+    device = _device_of(enroll_xv, test_xv, cohort_xv)
+    e = _f32(enroll_xv, device)
+    t = e if test_xv is enroll_xv else _f32(test_xv, device)
+    es = e[:: max(1, e.shape[0] // 2048)][:2048].contiguous()
+    ts = es if t is e else t[:: max(1, t.shape[0] // 2048)][:2048].contiguous()
+    cohort = _cohort_on(device, cohort_xv, normalize)
+    from .iv_scoring import cosine_matrix_device
+    z = cosine_matrix_device(es, ts, device)
+    if kind == "z":
+        znorm_device(z, es, cohort)
+    elif kind == "t":
+        tnorm_device(z, ts, cohort)
+    else:
+        snorm_device(z, es, ts, cohort, topk=topk)
+    if es is ts:
+        z = z[~torch.eye(z.shape[0], dtype=torch.bool, device=device)]               # a set against itself: the self-trials are not trials
+    zmin, zmax = float(z.min()), float(z.max())
+    pad = 0.25 * (zmax - zmin)
+    return zmin - pad, zmax + pad
 
 
 def matrix_moments_device(scoremat, axis, skip_diag=False):
