@@ -224,7 +224,7 @@ int sc_plda_fast(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, i
  * cosine scoring (sidekit/score_normalization.py:128, sidekit/nnet/xvector.py:243,258-259).  d_out may alias d_X. */
 int sc_normalize_rows(const float* d_X, int32_t N, int32_t D, float* d_out, void* stream);
 
-/* sc_plda_fast keeps its intermediate buffer (E.Psi and the quadratic-form partials) cached per (device, stream) so that a call
+/* sc_plda_fast (and sc_plda_hist) keeps its intermediate buffer (E.Psi and the quadratic-form partials) cached per (device, stream) so that a call
  * allocates nothing; this frees every cached buffer (after a device synchronise).  The Python shim calls it at interpreter exit;
  * a long-lived host that creates and destroys many streams may call it whenever no sc_plda_fast call is in flight.  The reference
  * has no counterpart (its temporaries are numpy arrays, sidekit/iv_scoring.py:449-460). */
@@ -252,6 +252,20 @@ int sc_cosine_hist_norm(const float* d_E, int32_t Ne, const float* d_T, int32_t 
                         const int32_t* d_labels_t, int32_t self_offset, const float* d_mean_e, const float* d_std_e,
                         const float* d_mean_t, const float* d_std_t, float lo, float hi, int32_t nbins, uint64_t* d_hist_tar,
                         uint64_t* d_hist_non, void* stream);
+
+/* All-pairs PLDA scoring without the score matrix (100k x 100k float64 trials = 80 GB): the log-likelihood ratios of
+ * sidekit/iv_scoring.py:448-462, each the double sc_plda_fast would have stored for the pair (the same preparation launch, the same
+ * f64 MFMA chain over ascending k, the same epilogue expression from left to right), are classified and counted as sc_cosine_hist
+ * counts cosine scores: the counts are those of sc_plda_fast + binning the matrix, which is never formed.  E, T, Phi, Psi, cst and
+ * scaling are sc_plda_fast's.  The bin of a score v is taken in float64, x = (v - lo) * (nbins / (hi - lo)), and clamped before the
+ * conversion to an integer: x < 0 is bin 0, x >= nbins the last bin, so +-inf lands in an end bin; a NaN score is counted nowhere and
+ * shows as a missing trial in the total.  Log-likelihood ratios have no natural range: lo and hi are finite, hi > lo, nbins = 8192,
+ * anything else (or a null pointer, or a size <= 0) is SK_EARG before anything is enqueued.  Only integer atomics are used: the
+ * counts are a function of the arguments alone.  Labels, self_offset, the zeroing of the counters on the stream and the stream
+ * contract are sc_cosine_hist's; the intermediate buffer is sc_plda_fast's (sc_release_workspace). */
+int sc_plda_hist(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
+                 double cst, double scaling, const int32_t* d_labels_e, const int32_t* d_labels_t, int32_t self_offset, double lo,
+                 double hi, int32_t nbins, uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream);
 
 /* Speaker-mean enrolment + cosine over a listed trial set, sidekit/bin/compute_spk_cosine.py:18-26:
  * out[k] = <E[enr_idx[k]], T[tst_idx[k]]> / (|E| |T|), float32 in, float64 maths. */

@@ -25,6 +25,7 @@ _LAZY = {
     "StatServer": "statserver",
     "cosine_scoring": "iv_scoring", "PLDA_scoring": "iv_scoring", "fast_PLDA_scoring": "iv_scoring", "full_PLDA_scoring": "iv_scoring",
     "mahalanobis_scoring": "iv_scoring", "two_covariance_scoring": "iv_scoring",
+    "plda_histograms": "iv_scoring", "plda_range_from_sample": "iv_scoring",
     "FactorAnalyser": "factor_analyser",
     "asnorm": "score_normalization", "znorm": "score_normalization", "tnorm": "score_normalization", "ztnorm": "score_normalization",
     "asnorm_trials": "score_normalization", "cohort_stats_device": "score_normalization", "znorm_device": "score_normalization",

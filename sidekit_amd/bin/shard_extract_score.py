@@ -12,8 +12,10 @@ prints EERs and timings as one JSON line.  ``--all-pairs`` adds the matrix-free 
 target / non-target histograms, the per-rank counts summed with one all-reduce.  ``--all-pairs-norm s|as`` adds the same for
 s-normalised (``as``: adaptive, the ``--norm-topk`` best cohort scores) scores, the reference's "norm EER" at a size where no
 score matrix fits: the last ``--norm-cohort`` rows of the corpus (PLDA training rows) are the cohort, every pair ``i != j`` of the rows
-before them is counted (``score_normalization.normalised_histograms``, row shards and the all-reduce as above).  Without
-``torch.distributed.run`` it runs as a single rank.
+before them is counted (``score_normalization.normalised_histograms``, row shards and the all-reduce as above).
+``--all-pairs-plda`` (on its own: it implies no other flag) counts the PLDA log-likelihood ratios of every pair ``i != j`` of the corpus
+the same way (``plda_histograms``: the back-end-normalised rows, the run's own ``(mu, F, Sigma)``, row shards, one all-reduce) and reports
+``plda_all_pairs_eer``.  Without ``torch.distributed.run`` it runs as a single rank.
 
 The corpus: speaker s is a fixed set of sinusoids (``RandomState(0)``), an utterance adds per-utterance phases, amplitude
 jitter and white noise (a batch is generated on the device with seed ``1000 + index of its first utterance``) -- enough
@@ -29,7 +31,8 @@ the device before PLDA training and PLDA scoring (cosine scoring keeps the raw x
 
 ``main(argv, model=None, scoring=None, keep=None)``: ``keep`` (a dict) receives the gathered x-vectors (``"xv"``, device tensor), the labels and
 rank 0's two score matrices -- for tests that compare two runs; the model and the module that scores (``cosine_matrix_device``, ``plda_matrix_device``,
-``cosine_histograms``) default to the GPU ones; ``--backend gloo --device cpu`` with injected stand-ins runs this driver's real
+``cosine_histograms``, and under ``--all-pairs-plda`` alone ``plda_histograms`` and, without ``--plda-hist-range``, ``plda_range_from_sample``) default
+to the GPU ones; ``--backend gloo --device cpu`` with injected stand-ins runs this driver's real
 control flow (ragged gather, row shards, ``self_offset``, the counter all-reduce) on CPU ranks (``tests/test_sharding_cpu.py``).
 """
 import argparse
@@ -122,6 +125,10 @@ def main(argv=None, model=None, scoring=None, keep=None):
     ap.add_argument("--norm-topk", type=int, default=200, metavar="K", help="--all-pairs-norm as: statistics of each row's K best cohort scores")
     ap.add_argument("--norm-hist-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="range of the normalised histograms; default: from a sample of this run's normalised scores (as --hist-range: runs to be compared share it)")
+    ap.add_argument("--all-pairs-plda", action="store_true",
+                    help="also count the PLDA scores of every pair of the corpus into histograms (no N x N float64 matrix); needs no other flag")
+    ap.add_argument("--plda-hist-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="range of the PLDA all-pairs histograms; default: from a sample of this run's PLDA scores (as --hist-range: runs to be compared share it)")
     ap.add_argument("--seed", type=int, default=0, help="corpus seed: another draw of speaker labels, phases, amplitude jitter and noise for the same speaker table")
     ap.add_argument("--plda", default=None, help="PLDA (mu, F, Sigma): SIDEKIT HDF5 or .npz; default: moment estimate from the corpus")
     ap.add_argument("--plda-train", default="moments", choices=["moments", "em"],
@@ -131,6 +138,8 @@ def main(argv=None, model=None, scoring=None, keep=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL over xGMI; gloo for CPU rehearsals")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu only with an injected model / scoring module")
     args = ap.parse_args(argv)
+    if args.plda_hist_range and not args.plda_hist_range[1] > args.plda_hist_range[0]:
+        ap.error("--plda-hist-range: HI must exceed LO")
     if args.all_pairs_norm:
         if not args.all_pairs:
             ap.error("--all-pairs-norm requires --all-pairs")
@@ -287,6 +296,32 @@ def main(argv=None, model=None, scoring=None, keep=None):
         if args.all_pairs_norm:
             out.update(all_pairs_norm=int(counts[2:].sum()), all_pairs_norm_kind=args.all_pairs_norm, all_pairs_norm_cohort=M,
                        all_pairs_norm_hist_range=[nlo, nhi], all_pairs_norm_s=t_norm, all_pairs_norm_eer=float(eer_from_histograms(counts[2], counts[3])))
+    if args.all_pairs_plda:
+        # the same for PLDA: rank r counts the log-likelihood ratios of the rows of its shard against every row of the corpus (the
+        # back-end-normalised rows where --lda / --sphnorm are given; plda_histograms centres them); the range comes from a sample scored
+        # on rank 0 and is broadcast, so that every rank bins on the same edges
+        a, b = shard_range(N, rank, world)
+        rows_all = xv if transforms is None else pv
+        lab_d = torch.as_tensor(labels, device=dev)
+        t0 = time.perf_counter()
+        edges = torch.zeros(2, dtype=torch.float64, device=dev)
+        if args.plda_hist_range:
+            edges = torch.as_tensor(args.plda_hist_range, dtype=torch.float64, device=dev)
+        else:
+            if rank == 0:
+                edges = torch.as_tensor(scoring.plda_range_from_sample(rows_all, rows_all, mu, F, Sigma, device=dev), dtype=torch.float64, device=dev)
+            if dist.is_initialized():
+                dist.broadcast(edges, src=0)
+        plo, phi = (float(v) for v in edges.cpu())
+        pht, phn = scoring.plda_histograms(rows_all[a:b], rows_all, lab_d[a:b], lab_d, mu, F, Sigma, self_offset=a, lo=plo, hi=phi, device=dev,
+                                           **({"bins": args.hist_bins} if args.hist_bins else {}))
+        pcounts = torch.as_tensor(numpy.stack([pht, phn]).astype(numpy.int64), device=dev)
+        if dist.is_initialized():
+            dist.all_reduce(pcounts)
+        sync()
+        pcounts = pcounts.cpu().numpy()
+        out.update(plda_all_pairs=int(pcounts.sum()), plda_all_pairs_s=time.perf_counter() - t0, plda_all_pairs_hist_range=[plo, phi],
+                   plda_all_pairs_hist_bins=int(pcounts.shape[1]), plda_all_pairs_eer=float(eer_from_histograms(pcounts[0], pcounts[1])))
     if keep is not None:
         keep.update(xv=xv, labels=labels, tar=tar, plda=(mu, F, Sigma))
         if transforms is not None:

@@ -6,8 +6,9 @@
 // launch forms E.Psi and the two quadratic forms, and the N^2 part runs as an f64 MFMA GEMM
 // (C = A . B^T, v_mfma_f64_16x16x4_f64) whose epilogue adds the quadratic terms and the constant, so
 // the (Ne x Nt) matrix is written exactly once.  For
-// trial sets too large to materialise, sc_cosine_hist counts target / non-target scores into
+// trial sets too large to materialise, sc_cosine_hist (cosine) and sc_plda_hist (PLDA) count target / non-target scores into
 // histograms straight from the accumulators.
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -260,6 +261,78 @@ __global__ __launch_bounds__(HTHREADS) void cosine_hist_kernel(const float* __re
   flush();
 }
 
+// ---- all-pairs PLDA scoring WITHOUT the score matrix (100k x 100k float64 log-likelihood ratios are 80 GB) ------------------------
+// The scores of sidekit/iv_scoring.py:448-462 as sc_plda_fast computes them, counted instead of stored: the counts are those of
+// sc_plda_fast + binning.  Persistent workgroups walk the 128 x 128 tiles of (E Psi) . T^T with dgemm_tile<4, false>, the tile of
+// dgemm_nt_kernel<4>; an accumulator element is the same chain of v_mfma_f64_16x16x4_f64 over ascending k whatever the tile edge, so
+// dgemm_nt_kernel<2>'s value for the pair is the same double.  The epilogue is dgemm_nt_kernel's expression,
+// alpha * (acc + rowterm + colterm + cst) from left to right (the library is built with -ffp-contract=off), with the two terms summed
+// over the partials in ascending p -- once per tile: thread t < 128 sums row m0 + t's, thread 128 + t column n0 + t's, during the k
+// loop, and 2 KB of LDS hand them to the epilogue.  The bin is taken in float64 and clamped BEFORE the conversion to int, so +-inf
+// lands in an end bin; a NaN score is counted nowhere and the caller sees it missing from the total.  Histograms, flush and launch
+// follow cosine_hist_kernel: 2 x 32 KB of 32-bit LDS counters beside the 34 KB of operand tiles, so one workgroup (four waves) per CU.
+constexpr int PT = 128, PTHREADS = 256;
+
+__global__ __launch_bounds__(PTHREADS) void plda_hist_kernel(const double* __restrict__ EPsi, int Ne, const double* __restrict__ T, int Nt, int D,
+                                                             const double* __restrict__ rowpart, const double* __restrict__ colpart, int nparts,
+                                                             double cst, double alpha, const int* __restrict__ le, const int* __restrict__ lt,
+                                                             int self_offset, double lo, double inv_width,
+                                                             unsigned long long* __restrict__ hist_tar, unsigned long long* __restrict__ hist_non) {
+  constexpr int WT = PT / 32;
+  __shared__ unsigned hist[2 * HB];
+  __shared__ __attribute__((aligned(16))) double As[PT * DLD];
+  __shared__ __attribute__((aligned(16))) double Bs[PT * DLD];
+  __shared__ double term[2 * PT];   // [0, PT): the tile's row terms, [PT, 2 PT): its column terms
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  for (int i = tid; i < 2 * HB; i += PTHREADS) hist[i] = 0u;
+  const long tiles_n = (Nt + PT - 1) / PT, ntiles = (long)((Ne + PT - 1) / PT) * tiles_n;
+  auto flush = [&]() {   // LDS counts -> the global 64-bit counters
+    for (int i = tid; i < 2 * HB; i += PTHREADS) {
+      const unsigned c = hist[i];
+      if (c) atomicAdd((i < HB ? hist_tar : hist_non) + (i & (HB - 1)), (unsigned long long)c);
+      hist[i] = 0u;
+    }
+  };
+  int since_flush = 0;
+  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    // a tile adds at most 128 x 128 = 2^14 counts to one 32-bit LDS bin: flushing before the 2^17-th tile keeps a bin below 2^31
+    if (++since_flush == (1 << 17)) { __syncthreads(); flush(); since_flush = 0; __syncthreads(); }
+    const int m0 = (int)(tile / tiles_n) * PT, n0 = (int)(tile % tiles_n) * PT;
+    double tsum = 0.0;   // rows and columns past the end are never binned
+    if (tid < PT) {
+      if (m0 + tid < Ne) for (int p = 0; p < nparts; ++p) tsum += rowpart[(long)p * Ne + m0 + tid];
+    } else if (n0 + tid - PT < Nt) {
+      for (int p = 0; p < nparts; ++p) tsum += colpart[(long)p * Nt + n0 + tid - PT];
+    }
+    f64x4 acc[WT][WT];
+    dgemm_tile<WT, false>(EPsi, T, Ne, Nt, D, m0, n0, As, Bs, acc);
+    term[tid] = tsum;   // the k loop's barriers lie between the previous tile's last read of `term` and this write
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < WT; ++j) {
+      const int ln_ = wn * 16 * WT + j * 16 + lr, n = n0 + ln_;
+      if (n >= Nt) continue;
+      const int labn = lt[n];
+      const double ct = term[PT + ln_];
+#pragma unroll
+      for (int i = 0; i < WT; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int lm = wm * 16 * WT + i * 16 + lk + 4 * q, m = m0 + lm;
+          if (m >= Ne || (self_offset >= 0 && m + self_offset == n)) continue;
+          const double v = alpha * (acc[i][j][q] + term[lm] + ct + cst);
+          const double x = (v - lo) * inv_width;
+          if (x != x) continue;
+          const int bin = x < 0.0 ? 0 : (x >= (double)HB ? HB - 1 : (int)x);
+          atomicAdd(&hist[(le[m] == labn ? 0 : HB) + bin], 1u);
+        }
+    }
+  }
+  __syncthreads();
+  flush();
+}
+
 __global__ void cosine_trials_kernel(const float* __restrict__ E, const float* __restrict__ T, int D, const int* __restrict__ ei,
                                      const int* __restrict__ ti, long n, double* __restrict__ out) {
   const long k = blockIdx.x * 4L + (threadIdx.x >> 6);
@@ -355,7 +428,7 @@ __global__ void snorm_apply_kernel(float* __restrict__ S, int ne, int nt, const 
   S[i] = 0.5f * ((v - me[r]) / se[r]) + 0.5f * ((v - mt[c]) / st[c]);
 }
 
-// ---- workspace of sc_plda_fast (E . Psi (Ne x D) and the partial quadratic forms) and of the PLDA training calls (plda_train.hip), cached per (device, stream) so that a call
+// ---- workspace of sc_plda_fast and sc_plda_hist (E . Psi (Ne x D) and the partial quadratic forms) and of the PLDA training calls (plda_train.hip), cached per (device, stream) so that a call
 // allocates nothing in the steady state (three hipMallocAsync / hipFreeAsync pairs per call were most of a 1000 x 1000 scoring).  A
 // stream's calls are ordered, so reuse needs no further synchronisation; growth waits for that stream's earlier calls first.  The
 // caller holds g_plda_mu from the lookup until its two kernels are enqueued (with the lock dropped in between, a second host
@@ -380,6 +453,36 @@ int plda_workspace_locked(hipStream_t st, size_t bytes, void** out) {
   return SK_OK;
 }
 
+// the CU count of the device the stream belongs to (the NULL stream: the current device)
+static int stream_cus(hipStream_t st) {
+  int dev = 0, cus = 256;
+  hipDevice_t sdev;
+  if (st && hipStreamGetDevice(st, &sdev) == hipSuccess) dev = (int)sdev;
+  else (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return cus > 0 ? cus : 256;
+}
+
+// What sc_plda_fast and sc_plda_hist share: the stream's workspace cut into E . Psi and the partial quadratic forms, and the ONE launch
+// that fills them.  The caller holds g_plda_mu, and keeps it until its own N^2 kernel is enqueued (see plda_workspace_locked).
+struct PldaPrep { double *epsi, *qe, *qt; int nparts; };
+static int plda_prep_locked(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
+                            hipStream_t st, PldaPrep* out) {
+  const int ctiles = cdiv(D, 64);
+  const size_t n_epsi = ((size_t)Ne * D + 1) & ~(size_t)1, n_qe = (size_t)ctiles * Ne, n_qt = (size_t)ctiles * Nt;
+  void* ws = nullptr;
+  SK_TRY(plda_workspace_locked(st, (n_epsi + n_qe + n_qt) * 8, &ws));
+  out->epsi = (double*)ws;
+  out->qe = out->epsi + n_epsi;
+  out->qt = out->qe + n_qe;
+  out->nparts = ctiles;
+  // model_part / seg_part = 0.5 * diag(X Phi X') as per-column-tile partials, and E . Psi   (iv_scoring.py:449-450,458)
+  hipLaunchKernelGGL(plda_prep_kernel, dim3(2 * ctiles, cdiv(Ne, 64) + cdiv(Nt, 64)), dim3(256), 0, st, d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, out->qe, out->qt,
+                     out->epsi);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
 // the persistent launch of both histogram entry points: counters zeroed on the stream, one workgroup per CU (at most one per tile)
 template <int NORM>
 static int launch_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, const int32_t* d_labels_e,
@@ -387,12 +490,7 @@ static int launch_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, in
                               uint64_t* d_hist_non, hipStream_t st) {
   SK_HIP(hipMemsetAsync(d_hist_tar, 0, (size_t)HB * 8, st));
   SK_HIP(hipMemsetAsync(d_hist_non, 0, (size_t)HB * 8, st));
-  int dev = 0, cus = 256;   // the CU count of the device the stream belongs to (the NULL stream: the current device)
-  hipDevice_t sdev;
-  if (st && hipStreamGetDevice(st, &sdev) == hipSuccess) dev = (int)sdev;
-  else (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (cus <= 0) cus = 256;
+  const int cus = stream_cus(st);
   const long ntiles = (long)cdiv(Ne, HT) * cdiv(Nt, HT);
   const int grid = (int)(ntiles < (long)cus ? ntiles : (long)cus);   // persistent: one workgroup per CU (64 KB of histograms + 74 KB of operand tiles)
   hipLaunchKernelGGL(cosine_hist_kernel<NORM>, dim3(grid), dim3(HTHREADS), 0, st, d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, lo,
@@ -418,21 +516,36 @@ int sc_plda_fast(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, i
                  double cst, double scaling, double* d_out, void* stream) {
   SK_CHECK(d_E && d_T && d_Phi && d_Psi && d_out && Ne > 0 && Nt > 0 && D > 0, SK_EARG, "sc_plda_fast: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  const int ctiles = cdiv(D, 64);
-  const size_t n_epsi = ((size_t)Ne * D + 1) & ~(size_t)1, n_qe = (size_t)ctiles * Ne, n_qt = (size_t)ctiles * Nt;
-  void* ws = nullptr;
+  PldaPrep w;
   std::lock_guard<std::mutex> lock(g_plda_mu);   // held until both launches are enqueued (see plda_workspace_locked)
-  SK_TRY(plda_workspace_locked(st, (n_epsi + n_qe + n_qt) * 8, &ws));
-  double* epsi = (double*)ws;
-  double* qe = epsi + n_epsi;
-  double* qt = qe + n_qe;
-  // 1) model_part / seg_part = 0.5 * diag(X Phi X') as per-column-tile partials, and E . Psi   (iv_scoring.py:449-450,458)
-  hipLaunchKernelGGL(plda_prep_kernel, dim3(2 * ctiles, cdiv(Ne, 64) + cdiv(Nt, 64)), dim3(256), 0, st, d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, qe, qt, epsi);
-  SK_HIP(hipGetLastError());
+  // 1) the workspace, E . Psi and the partial quadratic forms
+  SK_TRY(plda_prep_locked(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, st, &w));
   // 2) scoremat = (model_part[:, None] + seg_part + cst + (E Psi) T') * scaling   (:458-460)
   const bool big = (long)cdiv(Ne, 128) * cdiv(Nt, 128) >= 512;   // two 128 x 128 workgroups per CU and still two rounds of them
-  if (big) hipLaunchKernelGGL(dgemm_nt_kernel<4>, dim3(cdiv(Nt, 128), cdiv(Ne, 128)), dim3(256), 0, st, epsi, d_T, d_out, Ne, Nt, D, qe, qt, ctiles, cst, scaling);
-  else hipLaunchKernelGGL(dgemm_nt_kernel<2>, dim3(cdiv(Nt, 64), cdiv(Ne, 64)), dim3(256), 0, st, epsi, d_T, d_out, Ne, Nt, D, qe, qt, ctiles, cst, scaling);
+  if (big) hipLaunchKernelGGL(dgemm_nt_kernel<4>, dim3(cdiv(Nt, 128), cdiv(Ne, 128)), dim3(256), 0, st, w.epsi, d_T, d_out, Ne, Nt, D, w.qe, w.qt, w.nparts, cst, scaling);
+  else hipLaunchKernelGGL(dgemm_nt_kernel<2>, dim3(cdiv(Nt, 64), cdiv(Ne, 64)), dim3(256), 0, st, w.epsi, d_T, d_out, Ne, Nt, D, w.qe, w.qt, w.nparts, cst, scaling);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
+int sc_plda_hist(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi, double cst,
+                 double scaling, const int32_t* d_labels_e, const int32_t* d_labels_t, int32_t self_offset, double lo, double hi, int32_t nbins,
+                 uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream) {
+  SK_CHECK(d_E && d_T && d_Phi && d_Psi && d_labels_e && d_labels_t && d_hist_tar && d_hist_non && Ne > 0 && Nt > 0 && D > 0, SK_EARG,
+           "sc_plda_hist: bad arguments (a null pointer or a size that is not positive)");
+  SK_CHECK(nbins == HB, SK_EARG, "sc_plda_hist: nbins must be %d", HB);
+  SK_CHECK(std::isfinite(lo) && std::isfinite(hi) && hi > lo, SK_EARG, "sc_plda_hist: lo and hi must be finite and hi > lo");
+  hipStream_t st = (hipStream_t)stream;
+  PldaPrep w;
+  std::lock_guard<std::mutex> lock(g_plda_mu);   // held until everything is enqueued (see plda_workspace_locked)
+  SK_TRY(plda_prep_locked(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, st, &w));
+  SK_HIP(hipMemsetAsync(d_hist_tar, 0, (size_t)HB * 8, st));
+  SK_HIP(hipMemsetAsync(d_hist_non, 0, (size_t)HB * 8, st));
+  const long ntiles = (long)cdiv(Ne, PT) * cdiv(Nt, PT);
+  const int cus = stream_cus(st);
+  const int grid = (int)(ntiles < (long)cus ? ntiles : (long)cus);   // persistent: one workgroup per CU (64 KB of histograms + 36 KB of tiles and terms)
+  hipLaunchKernelGGL(plda_hist_kernel, dim3(grid), dim3(PTHREADS), 0, st, w.epsi, Ne, d_T, Nt, D, w.qe, w.qt, w.nparts, cst, scaling, d_labels_e,
+                     d_labels_t, self_offset, lo, (double)HB / (hi - lo), (unsigned long long*)d_hist_tar, (unsigned long long*)d_hist_non);
   SK_HIP(hipGetLastError());
   return SK_OK;
 }

@@ -1,5 +1,6 @@
 """Trial scoring -- mirror of ``sidekit/iv_scoring.py``: ``cosine_scoring`` (:63-113), ``PLDA_scoring``
-(:215-269), ``full_PLDA_scoring`` (:272-368), ``fast_PLDA_scoring`` (:370-477), and -- beyond SURVEY 8's rows, because they are
+(:215-269), ``full_PLDA_scoring`` (:272-368), ``fast_PLDA_scoring`` (:370-477), ``plda_histograms`` / ``plda_range_from_sample`` (the scores of
+:448-462 for every pair of a corpus, counted instead of stored), and -- beyond SURVEY 8's rows, because they are
 the same device entry point with other matrices -- ``mahalanobis_scoring`` (:116-156) and ``two_covariance_scoring`` (:159-213).
 
 The trial matrix is computed on the GPU through the C ABI (``sc_cosine``: f32 MFMA GEMM;
@@ -118,6 +119,28 @@ def _norm_pair(pair, n, side):
     return pair
 
 
+def _histogram_passes(one_pass, lo, hi, bins):
+    """``bins`` bins over ``[lo, hi)`` from ``one_pass(a, b)``, which counts every pair into ``HIST_BINS`` bins over ``[a, b)``: one pass for
+    ``HIST_BINS`` itself, else ``bins / (HIST_BINS - 2)`` passes, each over a slice of the range with one guard bin either side (bins 0 and
+    ``HIST_BINS - 1`` of a pass hold everything below / above its slice)."""
+    if bins == HIST_BINS:
+        return one_pass(lo, hi)
+    inner = HIST_BINS - 2
+    w = (float(hi) - float(lo)) / bins
+    out_t, out_n = numpy.zeros(bins, dtype=numpy.uint64), numpy.zeros(bins, dtype=numpy.uint64)
+    passes = bins // inner
+    for k in range(passes):
+        a = float(lo) + k * inner * w
+        ht, hn = one_pass(a - w, a + (inner + 1) * w)
+        for full, part in ((out_t, ht), (out_n, hn)):
+            full[k * inner:(k + 1) * inner] = part[1:-1]
+            if k == 0:
+                full[0] += part[0]
+            if k == passes - 1:
+                full[-1] += part[-1]
+    return out_t, out_n
+
+
 def cosine_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, self_offset=None, lo=-1.0, hi=1.0, device=None, bins=None,
                       enroll_norm=None, test_norm=None):
     """Target / non-target score histograms of ALL (enrol, test) pairs without materialising the (Ne, Nt) score matrix
@@ -172,21 +195,7 @@ def cosine_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, 
                 _lib.check(_lib.lib().sc_cosine_hist(*head, *tail), AssertionError)
         return ht.cpu().numpy().astype(numpy.uint64), hn.cpu().numpy().astype(numpy.uint64)
 
-    if bins == HIST_BINS:
-        return one_pass(lo, hi)
-    w = (float(hi) - float(lo)) / bins
-    out_t, out_n = numpy.zeros(bins, dtype=numpy.uint64), numpy.zeros(bins, dtype=numpy.uint64)
-    passes = bins // inner
-    for k in range(passes):
-        a = float(lo) + k * inner * w
-        ht, hn = one_pass(a - w, a + (inner + 1) * w)          # bins 0 and HIST_BINS - 1 of a pass: everything below / above its slice
-        for full, part in ((out_t, ht), (out_n, hn)):
-            full[k * inner:(k + 1) * inner] = part[1:-1]
-            if k == 0:
-                full[0] += part[0]
-            if k == passes - 1:
-                full[-1] += part[-1]
-    return out_t, out_n
+    return _histogram_passes(one_pass, lo, hi, bins)
 
 
 def _speaker_posterior_terms(K):
@@ -230,6 +239,115 @@ def full_plda_parameters(F, G, Sigma, scaling_factor=1.):
     B = F.T @ prec_marg
     K1, K2, constant = _speaker_posterior_terms(B @ F)
     return B, K2 - K1, 0.5 * (K2 + K2.T), constant
+
+
+def _plda_hist_operands(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor):
+    """The host half of ``plda_histograms`` / ``plda_range_from_sample``: every check that needs no device, then the D x D algebra.
+    Returns ``(mu, B, Phi, Psi, cst)``; ``B`` is ``None`` without a channel sub-space, else the projection both sides go through."""
+    if len(enroll_vectors.shape) != 2 or len(test_vectors.shape) != 2 or enroll_vectors.shape[1] != test_vectors.shape[1]:
+        raise ValueError("enrolment and test vectors are matrices of one width")
+    if enroll_vectors.shape[0] == 0 or test_vectors.shape[0] == 0:
+        raise ValueError("empty enrolment or test side")
+    D = enroll_vectors.shape[1]
+    mu, F, Sigma = (numpy.asarray(v, dtype=numpy.float64) for v in (mu, F, Sigma))
+    G = None if G is None else numpy.asarray(G, dtype=numpy.float64)
+    if mu.shape != (D,) or F.ndim != 2 or F.shape[0] != D or Sigma.shape != (D, D) or (G is not None and (G.ndim != 2 or G.shape[0] != D)):
+        raise ValueError(f"the vectors are {D} wide: mu must be ({D},), F ({D}, rank), Sigma ({D}, {D}) and G ({D}, rank); got "
+                         f"{mu.shape}, {F.shape}, {Sigma.shape}" + ("" if G is None else f", {G.shape}"))
+    for side, labels, n in (("enrolment", enroll_labels, enroll_vectors.shape[0]), ("test", test_labels, test_vectors.shape[0])):
+        if labels is not None and tuple(labels.shape) != (n,):
+            raise ValueError(f"one label per row: the {side} side has {n} rows and labels of shape {tuple(labels.shape)}")
+    for name, v in (("mu", mu), ("F", F), ("Sigma", Sigma), ("G", G)):
+        if v is not None and not numpy.isfinite(v).all():
+            raise ValueError(f"{name} is not finite")
+    if G is None:
+        return (mu, None) + tuple(plda_parameters(mu, F, Sigma, scaling_factor))
+    return (mu,) + tuple(full_plda_parameters(F, G, Sigma, scaling_factor))
+
+
+def _plda_hist_vectors(enroll_vectors, test_vectors, mu, B, device):
+    """Both sides on the device in float64, centred by ``mu`` and, with a channel sub-space, projected by ``B`` (the route of
+    ``full_PLDA_scoring``); one object for both sides when the caller passed one.  One reduction checks that they are finite."""
+    mu_d = torch.as_tensor(mu, device=device)
+    prep = lambda x: _to_device(x, torch.float64, device) - mu_d
+    e = prep(enroll_vectors)
+    t = e if test_vectors is enroll_vectors else prep(test_vectors)
+    if not bool(torch.isfinite(e).all() & torch.isfinite(t).all()):                  # one scalar back
+        raise ValueError("the centred vectors are not finite")
+    if B is not None:
+        from .backend import whiten_rows_device
+        R = numpy.ascontiguousarray(B.T)
+        pe = whiten_rows_device(e.contiguous(), None, R)
+        e, t = pe, (pe if t is e else whiten_rows_device(t.contiguous(), None, R))
+    return e.contiguous(), t.contiguous()
+
+
+def _hist_device(device, *tensors):
+    return _device(device if device is not None else next((x.device for x in tensors if torch.is_tensor(x) and x.is_cuda), None))
+
+
+def _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, lo, hi, device):
+    """One ``sc_plda_hist`` call on resident operands: the two ``HIST_BINS``-bin uint64 histograms over ``[lo, hi)``."""
+    ht = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
+    hn = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().sc_plda_hist(e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], phi.data_ptr(), psi.data_ptr(),
+                                           float(cst), float(scaling_factor), le.data_ptr(), lt.data_ptr(),
+                                           -1 if self_offset is None else int(self_offset), float(lo), float(hi), HIST_BINS, ht.data_ptr(),
+                                           hn.data_ptr(), _stream(device)))
+    return ht.cpu().numpy().astype(numpy.uint64), hn.cpu().numpy().astype(numpy.uint64)
+
+
+def plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G=None, scaling_factor=1., self_offset=None, *,
+                    lo=None, hi=None, bins=None, device=None):
+    """Target / non-target histograms of the PLDA log-likelihood ratios of ALL (enrol, test) pairs without the (Ne, Nt) float64 score
+    matrix (100k x 100k trials are 80 GB): what ``cosine_histograms`` is to ``cosine_scoring``, for ``fast_PLDA_scoring`` (``G is None``:
+    ``plda_parameters``) and ``full_PLDA_scoring`` (``G`` given: ``full_plda_parameters``, both sides projected by ``B``, so the kernel sees
+    rank-dimensional vectors).  The vectors are centred by ``mu`` on the device in float64; every score is the double ``plda_matrix_device``
+    would have stored (``sc_plda_hist``), so the counts are those of binning that matrix.  Labels, ``self_offset`` and the two uint64 arrays
+    returned are ``cosine_histograms``'; so is ``bins`` (``HIST_BINS`` or a multiple of ``HIST_BINS - 2``: that many finer bins from several
+    passes).  Log-likelihood ratios have no natural range: ``lo`` / ``hi`` are required keywords (``plda_range_from_sample``).  Scores outside
+    land in the end bins; a NaN score is in no bin.
+
+    What needs no device raises ``ValueError`` before one is touched: missing ``lo`` / ``hi`` or ``hi <= lo``, vectors that are not matrices
+    of one width, a width other than ``len(mu)``, ``F.shape[0]`` or ``Sigma.shape``, labels that are not one per row, ``bins``, and non-finite
+    ``mu`` / ``F`` / ``Sigma`` / ``G``; centred vectors that are not finite raise it after one device reduction."""
+    if lo is None or hi is None:
+        raise ValueError("plda_histograms: lo and hi are required (log-likelihood ratios have no natural range: plda_range_from_sample)")
+    if not (numpy.isfinite(lo) and numpy.isfinite(hi) and float(hi) > float(lo)):
+        raise ValueError("plda_histograms: lo and hi must be finite and hi must exceed lo")
+    bins = HIST_BINS if bins is None else int(bins)
+    if bins != HIST_BINS and (bins <= 0 or bins % (HIST_BINS - 2)):
+        raise ValueError(f"bins must be {HIST_BINS} or a multiple of {HIST_BINS - 2}")
+    enroll_labels = enroll_labels if torch.is_tensor(enroll_labels) else numpy.asarray(enroll_labels)
+    test_labels = test_labels if torch.is_tensor(test_labels) else numpy.asarray(test_labels)
+    mu, B, Phi, Psi, cst = _plda_hist_operands(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor)
+    device = _hist_device(device, enroll_vectors, test_vectors)
+    e, t = _plda_hist_vectors(enroll_vectors, test_vectors, mu, B, device)
+    phi, psi = _to_device(Phi, torch.float64, device), _to_device(Psi, torch.float64, device)
+    le = torch.as_tensor(enroll_labels).to(device=device, dtype=torch.int32).contiguous()
+    lt = torch.as_tensor(test_labels).to(device=device, dtype=torch.int32).contiguous()
+
+    one_pass = lambda a, b: _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, a, b, device)
+    return _histogram_passes(one_pass, lo, hi, bins)
+
+
+def plda_range_from_sample(enroll_vectors, test_vectors, mu, F, Sigma, G=None, scaling_factor=1., device=None):
+    """``(lo, hi)`` for ``plda_histograms``, as ``score_normalization.normalised_range_from_sample`` finds it: a strided sample of at most
+    2 048 rows per side, its score matrix from ``plda_matrix_device`` (without the self-trials when the two sides are the same object), and
+    the sample's smallest and largest score, each widened by a quarter of the sampled range."""
+    mu, B, Phi, Psi, cst = _plda_hist_operands(enroll_vectors, test_vectors, None, None, mu, F, Sigma, G, scaling_factor)
+    device = _hist_device(device, enroll_vectors, test_vectors)
+    sample = lambda x: x[:: max(1, x.shape[0] // 2048)][:2048]
+    es = sample(enroll_vectors)
+    ts = es if test_vectors is enroll_vectors else sample(test_vectors)
+    e, t = _plda_hist_vectors(es, ts, mu, B, device)
+    z = plda_matrix_device(e, t, Phi, Psi, cst, scaling_factor, device)
+    if es is ts:
+        z = z[~torch.eye(z.shape[0], dtype=torch.bool, device=device)]               # a set against itself: the self-trials are not trials
+    zmin, zmax = float(z.min()), float(z.max())
+    pad = 0.25 * (zmax - zmin)
+    return zmin - pad, zmax + pad
 
 
 def _open_set(scoremat, p_known):
