@@ -7,8 +7,10 @@
 //   cosine trial scoring (iv_scoring.py:108-109).
 // Tile: 64x64x32 per 256-thread workgroup, four waves each owning a 32x32 accumulator;
 // global->register prefetch of tile k+1 overlaps the MFMAs of tile k; LDS rows padded to 36
-// floats so the ds_read_b128 fragment reads are bank-conflict free.
+// floats so the ds_read_b128 fragment reads are bank-conflict free.  The wave's k-tile step and the
+// accumulator map are sgemm_tile.h's, shared with score_norm.hip (gemm128_kernel keeps the step written out, see there).
 #include "kernels.h"
+#include "sgemm_tile.h"
 
 namespace sk {
 
@@ -71,15 +73,13 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
   // K is cut into g.kslices slices of whole k-tiles and a result is ALWAYS 0 + slice 0 + slice 1 + ... (each slice an FMA chain
   // from zero), whether the slices run as blockIdx.z (small M: parallelism; gemm_splitk_epilogue_kernel adds them) or one after the
   // other in this workgroup (large M) -- an utterance's embedding does not depend on how many others share its batch.
-  f32x16 acc, tot;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) tot[q] = 0.f;
+  f32x16 acc[1][1], tot[1][1];
+  sgemm_zero(tot);
   const int nk_all = (g.K + BK - 1) / BK;
   const int per = (nk_all + g.kslices - 1) / g.kslices;
   const int z0 = g.ksplit > 1 ? (int)blockIdx.z : 0, z1 = g.ksplit > 1 ? z0 + 1 : g.kslices;
   for (int z = z0; z < z1; ++z) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    sgemm_zero(acc);
     const int kt0 = z * per, kt1 = (kt0 + per < nk_all) ? kt0 + per : nk_all;
     if (kt0 < kt1) fetch(kt0 * BK);
     for (int kt = kt0; kt < kt1; ++kt) {
@@ -90,45 +90,38 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
       }
       __syncthreads();
       if (kt + 1 < kt1) fetch((kt + 1) * BK);
-#pragma unroll
-      for (int kk = 0; kk < BK; kk += 8) {
-        const float4 a = *reinterpret_cast<const float4*>(&As[(wm * 32 + r) * LDT + kk + 4 * h]);
-        const float4 b = *reinterpret_cast<const float4*>(&Ws[(wn * 32 + r) * LDT + kk + 4 * h]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-      }
+      sgemm_wave_step<1>(As, Ws, LDT, wm * 32 + r, wn * 32 + r, h, acc);
       __syncthreads();
     }
     if (g.ksplit == 1 && g.kslices > 1) {
 #pragma unroll
-      for (int q = 0; q < 16; ++q) tot[q] += acc[q];
+      for (int q = 0; q < 16; ++q) tot[0][0][q] += acc[0][0][q];
     }
   }
-  if (g.ksplit == 1 && g.kslices > 1) acc = tot;
-  // epilogue: D[row = (q&3) + 8*(q>>2) + 4*h][col = r]
+  if (g.ksplit == 1 && g.kslices > 1) acc[0][0] = tot[0][0];
+  // epilogue: D[row = sgemm_acc_row(q, h)][col = r]
   const int n = n0 + wn * 32 + r;
   if (n >= g.N) return;
   if (g.ksplit > 1) {  // raw partial sums; gemm_splitk_epilogue_kernel adds them in slice order and applies the epilogue
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int m = m0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-      if (m < g.M) g.splitk_ws[((long)blockIdx.z * g.M + m) * g.N + n] = acc[q];
+      const int m = m0 + wm * 32 + sgemm_acc_row(q, h);
+      if (m < g.M) g.splitk_ws[((long)blockIdx.z * g.M + m) * g.N + n] = acc[0][0][q];
     }
     return;
   }
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
-    const int m = m0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-    if (m < g.M) g.C[(long)m * g.ldc + n] = gemm_epilogue(g, acc[q], m, n);
+    const int m = m0 + wm * 32 + sgemm_acc_row(q, h);
+    if (m < g.M) g.C[(long)m * g.ldc + n] = gemm_epilogue(g, acc[0][0][q], m, n);
   }
 }
 
 // ---- 128 x 128 tile for the large problems (TDNN layers: 96k rows x 512..1536; 16k x 16k cosine trial matrices) -------------
 // With 64 x 64 tiles every k-tile moves 16 KB of operands for 262 kFLOP: 16 FLOP/B, i.e. 6 TB/s of L2 traffic at the 96 TFLOP/s
 // the kernel reached (61 % of the f32 MFMA peak).  Four waves of 64 x 64 (2 x 2 accumulator tiles, 64 registers) halve that.
-// Each output element sees the same k-ordered FMA chain as in the 64 x 64 kernel: results are bit-identical.
+// Each output element sees the same k-ordered FMA chain as in the 64 x 64 kernel: results are bit-identical.  The k-tile step below is
+// sgemm_wave_step<2> written out, and stays so: through the helper the compiler schedules this kernel 0.7 % slower at 16 384^2 x 256.
 constexpr int BM2 = 128, BN2 = 128;
 
 template <bool SLICED>
@@ -348,7 +341,7 @@ __global__ __launch_bounds__(128) void gemm_bf16_kernel(GemmArgs g) {
   if (n >= g.N) return;
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
-    const int m = m0 + (q & 3) + 8 * (q >> 2) + 4 * h;
+    const int m = m0 + sgemm_acc_row(q, h);
     if (m >= g.M) continue;
     if (g.ksplit > 1) g.splitk_ws[((long)blockIdx.y * g.M + m) * g.N + n] = tot[q];      // this slice's sum (0 + s_z); the epilogue kernel adds the slices in order
     else g.C[(long)m * g.ldc + n] = gemm_epilogue(g, g.kslices > 1 ? tot[q] : acc[q], m, n);

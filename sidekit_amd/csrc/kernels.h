@@ -163,8 +163,9 @@ int launch_l2norm(const float* x, float* out, int D, int B, hipStream_t s);
 int launch_normalize_rows(const float* x, float* out, int D, int B, float eps, hipStream_t s);
 
 // ---- scoring.hip --------------------------------------------------------------------------
-// The sc_* workspace: one buffer per (device, stream), grown on demand, freed by sc_release_workspace().  The caller holds
-// g_plda_mu from the lookup until the kernels that use the buffer are enqueued.
+// The sc_* workspace (also score_norm.hip's, plda_train.hip's and backend.hip's): one buffer per (device, stream), grown on demand, freed
+// by sc_release_workspace().  The caller holds g_plda_mu from the lookup until the kernels that use the buffer are enqueued.
+// (The f32 / f64 MFMA tiles shared between files are headers of their own: sgemm_tile.h, dgemm_tile.h.)
 extern std::mutex g_plda_mu;
 int plda_workspace_locked(hipStream_t st, size_t bytes, void** out);
 

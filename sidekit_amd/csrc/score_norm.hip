@@ -3,16 +3,18 @@
 //
 // What a normalisation needs from an impostor cohort is two numbers per enrolment (or test) vector: the mean and the standard
 // deviation of its scores against the cohort.  sc_cohort_moments forms them straight from the accumulators of the cosine GEMM
-// (f32 MFMA, the arithmetic of sc_cosine), so the (N x M) cohort score matrix is never written; sc_matrix_moments does the same for
-// a score matrix that already exists (the Scores-level mirrors); sc_norm_apply is the elementwise pass.  Sums are float64, partial
-// sums go through the sc_* workspace and are added in a fixed order: no floating-point atomics.
+// (f32 MFMA through sgemm_wave_step, the k-ordered FMA chain of sc_cosine's kernels: the same bits), so the (N x M) cohort score matrix is never written;
+// sc_matrix_moments does the same for a score matrix that already exists (the Scores-level mirrors); sc_topk_stats gives the adaptive
+// statistics (the k best scores of a row); sc_norm_apply / sc_snorm_apply are the elementwise pass, one kernel with three modes.  Sums
+// are float64, partial sums go through the sc_* workspace and are added in a fixed order: no floating-point atomics.
 #include "../../include/sidekit_amd.h"
 #include "kernels.h"
+#include "sgemm_tile.h"
 
 namespace sk {
 
 // Tile: 128 cohort rows x 128 X rows per 256-thread workgroup, four waves of 64 x 64 (2 x 2 accumulator tiles), k-tiles of 32 through
-// LDS with the next k-tile prefetched into registers: the loop of gemm128_kernel.  The COHORT is the MFMA's row operand, so a lane's
+// LDS with the next k-tile prefetched into registers: gemm128_kernel's loop with sgemm_wave_step as the k-tile step.  The COHORT is the MFMA's row operand, so a lane's
 // 32 accumulator values per 32 x 32 tile are 32 cohort scores of ONE X row: its running sum and sum of squares are two doubles per
 // column tile (8 registers), not two per accumulator row (128).  a * b is commutative, so every score is the k-ordered FMA chain
 // sc_cosine computes.  A workgroup walks the `tiles_per_slab` cohort tiles of slab blockIdx.y; the slab size depends on M alone, so a
@@ -48,12 +50,7 @@ __global__ __launch_bounds__(256, 2) void cohort_moments_kernel(const float* __r
   for (int t = t0; t < t1; ++t) {
     const int c0 = t * CT;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+    sgemm_zero(acc);
     for (int kt = 0; kt < nk; ++kt) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -63,34 +60,10 @@ __global__ __launch_bounds__(256, 2) void cohort_moments_kernel(const float* __r
       __syncthreads();
       const bool wrap = kt + 1 == nk;           // then: the next cohort tile's first k-tile
       if (!wrap || t + 1 < t1) fetch(wrap ? c0 + CT : c0, wrap ? 0 : (kt + 1) * 32);
-#pragma unroll
-      for (int kk = 0; kk < 32; kk += 8) {
-        float4 a[2], b[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          a[i] = *reinterpret_cast<const float4*>(&Cs[(wm * 64 + i * 32 + r) * CLD + kk + 4 * h]);
-          b[i] = *reinterpret_cast<const float4*>(&Xs[(wn * 64 + i * 32 + r) * CLD + kk + 4 * h]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
-      }
+      sgemm_wave_step<2>(Cs, Xs, CLD, wm * 64 + r, wn * 64 + r, h, acc);
       __syncthreads();
     }
-    // acc[i][j][q] = <C[c0 + wm*64 + i*32 + (q&3) + 8*(q>>2) + 4*h], X[n0 + wn*64 + j*32 + r]>
+    // acc[i][j][q] = <C[c0 + wm*64 + i*32 + sgemm_acc_row(q, h)], X[n0 + wn*64 + j*32 + r]>
     // (a dropped value enters the sums as an exact zero: the kept values' additions are unchanged by it)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -99,7 +72,7 @@ __global__ __launch_bounds__(256, 2) void cohort_moments_kernel(const float* __r
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int m = c0 + wm * 64 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+          const int m = c0 + wm * 64 + i * 32 + sgemm_acc_row(q, h);
           double v = (double)acc[i][j][q];
           if constexpr (AFFINE) {
             const int mc = m < M ? m : M - 1;
@@ -200,13 +173,96 @@ __global__ __launch_bounds__(256) void col_moments_kernel(const float* __restric
   }
 }
 
-// S[i][j] <- (S[i][j] - m[k]) / s[k],  k = i (z-norm) or j (t-norm)
-template <bool BY_ROW>
-__global__ void norm_apply_kernel(float* __restrict__ S, int ne, int nt, const float* __restrict__ m, const float* __restrict__ s) {
+// ---- adaptive s-norm support (sidekit/score_normalization.py:120-140) -----------------------------------------
+// Mean and unbiased std of the k largest values of every row: an exact radix select on the order-preserving
+// integer image of the floats (four 8-bit passes narrow the k-th largest key), then one pass of sums.  Ties at the
+// threshold contribute exactly the copies torch.topk would keep, so the statistics equal those of any valid top-k.
+__device__ inline unsigned fkey(float f) {
+  const unsigned u = __builtin_bit_cast(unsigned, f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // larger float <=> larger key
+}
+
+__global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict__ x, int ncols, int k, float* __restrict__ mean,
+                                                         float* __restrict__ stdv) {
+  __shared__ unsigned hist[256];
+  __shared__ unsigned s_prefix, s_remaining;
+  __shared__ double red[2 * 256];
+  const float* row = x + (size_t)blockIdx.x * ncols;
+  const int tid = threadIdx.x;
+  unsigned prefix = 0, mask = 0;
+  unsigned remaining = (unsigned)k;   // how many of the still-undecided keys belong to the top-k
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < ncols; i += 256) {
+      const unsigned key = fkey(row[i]);
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      unsigned acc = 0;
+      int b = 255;
+      for (; b > 0; --b) {
+        if (acc + hist[b] >= remaining) break;
+        acc += hist[b];
+      }
+      s_prefix = prefix | ((unsigned)b << shift);
+      s_remaining = remaining - acc;
+    }
+    __syncthreads();
+    prefix = s_prefix;
+    remaining = s_remaining;
+    mask |= 255u << shift;
+    __syncthreads();
+  }
+  // prefix == key of the k-th largest value; `remaining` copies of it are inside the top-k
+  double s1 = 0.0, s2 = 0.0;
+  float tval = 0.f;
+  for (int i = tid; i < ncols; i += 256) {
+    const float v = row[i];
+    const unsigned key = fkey(v);
+    if (key > prefix) { s1 += (double)v; s2 += (double)v * (double)v; }
+    if (key == prefix) tval = v;
+  }
+  red[tid] = s1; red[256 + tid] = s2;
+  __shared__ float s_tval;
+  if (fkey(tval) == prefix) s_tval = tval;   // every writer holds the same value
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0, b = 0.0;
+    for (int q = 0; q < 256; ++q) { a += red[q]; b += red[256 + q]; }
+    const double tv = (double)s_tval;
+    a += tv * (double)remaining;
+    b += tv * tv * (double)remaining;
+    const double m = a / (double)k;
+    mean[blockIdx.x] = (float)m;
+    const double var = (b - (double)k * m * m) / (double)(k - 1);
+    stdv[blockIdx.x] = (float)sqrt(var > 0.0 ? var : 0.0);
+  }
+}
+
+// S[i][j] <- (S[i][j] - me[i]) / se[i] (NA_ENROL: z-norm), (S[i][j] - mt[j]) / st[j] (NA_TEST: t-norm), or half the one plus half the
+// other (NA_BOTH: s-norm); a pair a mode does not use is never read
+enum { NA_ENROL = 1, NA_TEST = 2, NA_BOTH = 3 };
+template <int MODE>
+__global__ void norm_apply_kernel(float* __restrict__ S, int ne, int nt, const float* __restrict__ me, const float* __restrict__ se,
+                                  const float* __restrict__ mt, const float* __restrict__ st) {
   const long i = blockIdx.x * 256L + threadIdx.x;
   if (i >= (long)ne * nt) return;
-  const int k = BY_ROW ? (int)(i / nt) : (int)(i % nt);
-  S[i] = (S[i] - m[k]) / s[k];
+  const int r = (int)(i / nt), c = (int)(i % nt);
+  const float v = S[i];
+  if constexpr (MODE == NA_ENROL) S[i] = (v - me[r]) / se[r];
+  if constexpr (MODE == NA_TEST) S[i] = (v - mt[c]) / st[c];
+  if constexpr (MODE == NA_BOTH) S[i] = 0.5f * ((v - me[r]) / se[r]) + 0.5f * ((v - mt[c]) / st[c]);
+}
+
+template <int MODE>
+static int launch_norm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t,
+                             const float* d_std_t, void* stream) {
+  hipLaunchKernelGGL(norm_apply_kernel<MODE>, dim3((unsigned)(((long)Ne * Nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_S, Ne, Nt,
+                     d_mean_e, d_std_e, d_mean_t, d_std_t);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
 }
 
 }  // namespace sk
@@ -261,12 +317,22 @@ int sc_norm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, con
   SK_CHECK(d_S && Ne > 0 && Nt > 0 && (e || t), SK_EARG, "sc_norm_apply: need the matrix and at least one (mean, std) pair");
   SK_CHECK((d_mean_e == nullptr) == (d_std_e == nullptr) && (d_mean_t == nullptr) == (d_std_t == nullptr), SK_EARG,
            "sc_norm_apply: a mean and its std come together");
-  if (e && t) return sc_snorm_apply(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);   // the same kernel: the same bits
-  const dim3 grid((unsigned)(((long)Ne * Nt + 255) / 256));
-  if (e) hipLaunchKernelGGL(norm_apply_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d_S, Ne, Nt, d_mean_e, d_std_e);
-  else hipLaunchKernelGGL(norm_apply_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d_S, Ne, Nt, d_mean_t, d_std_t);
+  if (e && t) return launch_norm_apply<NA_BOTH>(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);   // sc_snorm_apply's kernel
+  if (e) return launch_norm_apply<NA_ENROL>(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);
+  return launch_norm_apply<NA_TEST>(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);
+}
+
+int sc_topk_stats(const float* d_scores, int32_t n_rows, int32_t n_cols, int32_t k, float* d_mean, float* d_std, void* stream) {
+  SK_CHECK(d_scores && d_mean && d_std && n_rows > 0 && k > 1 && k <= n_cols, SK_EARG, "sc_topk_stats: need 1 < k <= n_cols (k=%d, n_cols=%d)", k, n_cols);
+  hipLaunchKernelGGL(topk_stats_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, d_scores, n_cols, k, d_mean, d_std);
   SK_HIP(hipGetLastError());
   return SK_OK;
+}
+
+int sc_snorm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t,
+                   const float* d_std_t, void* stream) {
+  SK_CHECK(d_S && d_mean_e && d_std_e && d_mean_t && d_std_t && Ne > 0 && Nt > 0, SK_EARG, "sc_snorm_apply: bad arguments");
+  return launch_norm_apply<NA_BOTH>(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);
 }
 
 }  // extern "C"

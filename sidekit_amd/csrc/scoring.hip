@@ -1,13 +1,15 @@
 // Trial-matrix scoring: cosine (sidekit/iv_scoring.py:98-109), fast PLDA (:448-462) and the
 // per-trial cosine of sidekit/bin/compute_spk_cosine.py:18-26.
 //
+// This file holds the scores and their histograms; everything that normalises a score is score_norm.hip.
 // cosine is one f32 MFMA GEMM over the already normalised rows.  PLDA keeps the reference's
 // float64 arithmetic end to end: the 256x256 algebra (Phi, Psi, constant) stays on the host; here ONE
 // launch forms E.Psi and the two quadratic forms, and the N^2 part runs as an f64 MFMA GEMM
 // (C = A . B^T, v_mfma_f64_16x16x4_f64) whose epilogue adds the quadratic terms and the constant, so
 // the (Ne x Nt) matrix is written exactly once.  For
-// trial sets too large to materialise, sc_cosine_hist (cosine) and sc_plda_hist (PLDA) count target / non-target scores into
-// histograms straight from the accumulators.
+// trial sets too large to materialise, sc_cosine_hist (cosine) and sc_plda_hist (PLDA; f64 tile of dgemm_tile.h)
+// count target / non-target scores into histograms straight from the accumulators; the entry points share one host prologue (hist_args_ok,
+// hist_begin).  The two kernels keep their own k-tile step and LDS histogram code: through shared helpers both measured slower.
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void plda_prep_kernel(const double* __restrict
 }
 
 // ---- all-pairs cosine scoring WITHOUT the score matrix (100k x 100k trials are 40 GB of float32) ---------------------
-// Persistent workgroups walk the 256 x 256 tiles of E . T^T (f32 MFMA, the arithmetic of sc_cosine), classify every score as
+// Persistent workgroups walk the 256 x 256 tiles of E . T^T (f32 MFMA, the arithmetic of sc_cosine: sgemm_wave_step<2> of sgemm_tile.h written out), classify every score as
 // target / non-target from the two label vectors and count it into a private LDS histogram pair; the histograms are added to
 // the global 64-bit counters once, at the end.  EER / ROCCH then come from the counts (bosaris.detplot.eer_from_histograms).
 constexpr int HB = 8192;   // bins per histogram: 2 x 32 KB of LDS per workgroup, one persistent workgroup per CU
@@ -130,7 +132,7 @@ constexpr int HT = 256, HLD = 36, HTHREADS = 1024;
 
 // NORM: what stands between an accumulator and its bin.  HN_NONE: nothing (sc_cosine_hist).  The others (sc_cosine_hist_norm) apply a
 // cohort normalisation with per-row statistics, in the expressions of the kernels that normalise a score matrix that exists
-// (norm_apply_kernel<true>, norm_apply_kernel<false>, snorm_apply_kernel): the same accumulator through the same IEEE operations (the
+// (norm_apply_kernel<NA_ENROL>, <NA_TEST>, <NA_BOTH> of score_norm.hip): the same accumulator through the same IEEE operations (the
 // library is built with -ffp-contract=off) is the same bits, so the counts are those of sc_cosine + sc_norm_apply + binning.  A tile's
 // 256 enrolment-side and 256 test-side (mean, std) go through 4 KB of LDS, once per tile; HN_NONE declares none of it.
 enum { HN_NONE = 0, HN_ENROL = 1, HN_TEST = 2, HN_BOTH = 3 };
@@ -350,84 +352,6 @@ __global__ void cosine_trials_kernel(const float* __restrict__ E, const float* _
   if (lane == 0) out[k] = uv / (sqrt(uu) * sqrt(vv));  // 1 - scipy.spatial.distance.cosine
 }
 
-// ---- adaptive s-norm support (sidekit/score_normalization.py:120-140) -----------------------------------------
-// Mean and unbiased std of the k largest values of every row: an exact radix select on the order-preserving
-// integer image of the floats (four 8-bit passes narrow the k-th largest key), then one pass of sums.  Ties at the
-// threshold contribute exactly the copies torch.topk would keep, so the statistics equal those of any valid top-k.
-__device__ inline unsigned fkey(float f) {
-  const unsigned u = __builtin_bit_cast(unsigned, f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // larger float <=> larger key
-}
-
-__global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict__ x, int ncols, int k, float* __restrict__ mean,
-                                                         float* __restrict__ stdv) {
-  __shared__ unsigned hist[256];
-  __shared__ unsigned s_prefix, s_remaining;
-  __shared__ double red[2 * 256];
-  const float* row = x + (size_t)blockIdx.x * ncols;
-  const int tid = threadIdx.x;
-  unsigned prefix = 0, mask = 0;
-  unsigned remaining = (unsigned)k;   // how many of the still-undecided keys belong to the top-k
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < ncols; i += 256) {
-      const unsigned key = fkey(row[i]);
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      unsigned acc = 0;
-      int b = 255;
-      for (; b > 0; --b) {
-        if (acc + hist[b] >= remaining) break;
-        acc += hist[b];
-      }
-      s_prefix = prefix | ((unsigned)b << shift);
-      s_remaining = remaining - acc;
-    }
-    __syncthreads();
-    prefix = s_prefix;
-    remaining = s_remaining;
-    mask |= 255u << shift;
-    __syncthreads();
-  }
-  // prefix == key of the k-th largest value; `remaining` copies of it are inside the top-k
-  double s1 = 0.0, s2 = 0.0;
-  float tval = 0.f;
-  for (int i = tid; i < ncols; i += 256) {
-    const float v = row[i];
-    const unsigned key = fkey(v);
-    if (key > prefix) { s1 += (double)v; s2 += (double)v * (double)v; }
-    if (key == prefix) tval = v;
-  }
-  red[tid] = s1; red[256 + tid] = s2;
-  __shared__ float s_tval;
-  if (fkey(tval) == prefix) s_tval = tval;   // every writer holds the same value
-  __syncthreads();
-  if (tid == 0) {
-    double a = 0.0, b = 0.0;
-    for (int q = 0; q < 256; ++q) { a += red[q]; b += red[256 + q]; }
-    const double tv = (double)s_tval;
-    a += tv * (double)remaining;
-    b += tv * tv * (double)remaining;
-    const double m = a / (double)k;
-    mean[blockIdx.x] = (float)m;
-    const double var = (b - (double)k * m * m) / (double)(k - 1);
-    stdv[blockIdx.x] = (float)sqrt(var > 0.0 ? var : 0.0);
-  }
-}
-
-// S[i][j] <- 0.5 * ((S[i][j] - me[i]) / se[i] + (S[i][j] - mt[j]) / st[j])
-__global__ void snorm_apply_kernel(float* __restrict__ S, int ne, int nt, const float* __restrict__ me, const float* __restrict__ se,
-                                   const float* __restrict__ mt, const float* __restrict__ st) {
-  const long i = blockIdx.x * 256L + threadIdx.x;
-  if (i >= (long)ne * nt) return;
-  const int r = (int)(i / nt), c = (int)(i % nt);
-  const float v = S[i];
-  S[i] = 0.5f * ((v - me[r]) / se[r]) + 0.5f * ((v - mt[c]) / st[c]);
-}
-
 // ---- workspace of sc_plda_fast and sc_plda_hist (E . Psi (Ne x D) and the partial quadratic forms) and of the PLDA training calls (plda_train.hip), cached per (device, stream) so that a call
 // allocates nothing in the steady state (three hipMallocAsync / hipFreeAsync pairs per call were most of a 1000 x 1000 scoring).  A
 // stream's calls are ordered, so reuse needs no further synchronisation; growth waits for that stream's earlier calls first.  The
@@ -483,16 +407,29 @@ static int plda_prep_locked(const double* d_E, int32_t Ne, const double* d_T, in
   return SK_OK;
 }
 
-// the persistent launch of both histogram entry points: counters zeroed on the stream, one workgroup per CU (at most one per tile)
+// What the histogram entry points do before their persistent launch: the counters zeroed on the stream, and the grid: one workgroup
+// per CU (the caller's LDS budget allows no second one), at most one per tile.
+static int hist_begin(uint64_t* d_hist_tar, uint64_t* d_hist_non, long ntiles, hipStream_t st, int* grid) {
+  SK_HIP(hipMemsetAsync(d_hist_tar, 0, (size_t)HB * 8, st));
+  SK_HIP(hipMemsetAsync(d_hist_non, 0, (size_t)HB * 8, st));
+  const int cus = stream_cus(st);
+  *grid = (int)(ntiles < (long)cus ? ntiles : (long)cus);
+  return SK_OK;
+}
+
+// the condition on the arguments every histogram entry point takes: no null pointer, no size that is not positive
+static bool hist_args_ok(const void* d_E, const void* d_T, const int32_t* d_labels_e, const int32_t* d_labels_t, const uint64_t* d_hist_tar,
+                         const uint64_t* d_hist_non, int32_t Ne, int32_t Nt, int32_t D) {
+  return d_E && d_T && d_labels_e && d_labels_t && d_hist_tar && d_hist_non && Ne > 0 && Nt > 0 && D > 0;
+}
+
+// the persistent launch of both cosine histogram entry points
 template <int NORM>
 static int launch_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, const int32_t* d_labels_e,
                               const int32_t* d_labels_t, int32_t self_offset, HistNorm nrm, float lo, float hi, uint64_t* d_hist_tar,
                               uint64_t* d_hist_non, hipStream_t st) {
-  SK_HIP(hipMemsetAsync(d_hist_tar, 0, (size_t)HB * 8, st));
-  SK_HIP(hipMemsetAsync(d_hist_non, 0, (size_t)HB * 8, st));
-  const int cus = stream_cus(st);
-  const long ntiles = (long)cdiv(Ne, HT) * cdiv(Nt, HT);
-  const int grid = (int)(ntiles < (long)cus ? ntiles : (long)cus);   // persistent: one workgroup per CU (64 KB of histograms + 74 KB of operand tiles)
+  int grid = 0;
+  SK_TRY(hist_begin(d_hist_tar, d_hist_non, (long)cdiv(Ne, HT) * cdiv(Nt, HT), st, &grid));   // one workgroup per CU: 64 KB of histograms + 74 KB of operand tiles
   hipLaunchKernelGGL(cosine_hist_kernel<NORM>, dim3(grid), dim3(HTHREADS), 0, st, d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, lo,
                      (float)HB / (hi - lo), (unsigned long long*)d_hist_tar, (unsigned long long*)d_hist_non, nrm);
   SK_HIP(hipGetLastError());
@@ -531,7 +468,7 @@ int sc_plda_fast(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, i
 int sc_plda_hist(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi, double cst,
                  double scaling, const int32_t* d_labels_e, const int32_t* d_labels_t, int32_t self_offset, double lo, double hi, int32_t nbins,
                  uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream) {
-  SK_CHECK(d_E && d_T && d_Phi && d_Psi && d_labels_e && d_labels_t && d_hist_tar && d_hist_non && Ne > 0 && Nt > 0 && D > 0, SK_EARG,
+  SK_CHECK(hist_args_ok(d_E, d_T, d_labels_e, d_labels_t, d_hist_tar, d_hist_non, Ne, Nt, D) && d_Phi && d_Psi, SK_EARG,
            "sc_plda_hist: bad arguments (a null pointer or a size that is not positive)");
   SK_CHECK(nbins == HB, SK_EARG, "sc_plda_hist: nbins must be %d", HB);
   SK_CHECK(std::isfinite(lo) && std::isfinite(hi) && hi > lo, SK_EARG, "sc_plda_hist: lo and hi must be finite and hi > lo");
@@ -539,11 +476,8 @@ int sc_plda_hist(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, i
   PldaPrep w;
   std::lock_guard<std::mutex> lock(g_plda_mu);   // held until everything is enqueued (see plda_workspace_locked)
   SK_TRY(plda_prep_locked(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, st, &w));
-  SK_HIP(hipMemsetAsync(d_hist_tar, 0, (size_t)HB * 8, st));
-  SK_HIP(hipMemsetAsync(d_hist_non, 0, (size_t)HB * 8, st));
-  const long ntiles = (long)cdiv(Ne, PT) * cdiv(Nt, PT);
-  const int cus = stream_cus(st);
-  const int grid = (int)(ntiles < (long)cus ? ntiles : (long)cus);   // persistent: one workgroup per CU (64 KB of histograms + 36 KB of tiles and terms)
+  int grid = 0;
+  SK_TRY(hist_begin(d_hist_tar, d_hist_non, (long)cdiv(Ne, PT) * cdiv(Nt, PT), st, &grid));   // one workgroup per CU: 64 KB of histograms + 36 KB of tiles and terms
   hipLaunchKernelGGL(plda_hist_kernel, dim3(grid), dim3(PTHREADS), 0, st, w.epsi, Ne, d_T, Nt, D, w.qe, w.qt, w.nparts, cst, scaling, d_labels_e,
                      d_labels_t, self_offset, lo, (double)HB / (hi - lo), (unsigned long long*)d_hist_tar, (unsigned long long*)d_hist_non);
   SK_HIP(hipGetLastError());
@@ -570,25 +504,9 @@ int sc_release_workspace(void) {
   return SK_OK;
 }
 
-int sc_topk_stats(const float* d_scores, int32_t n_rows, int32_t n_cols, int32_t k, float* d_mean, float* d_std, void* stream) {
-  SK_CHECK(d_scores && d_mean && d_std && n_rows > 0 && k > 1 && k <= n_cols, SK_EARG, "sc_topk_stats: need 1 < k <= n_cols (k=%d, n_cols=%d)", k, n_cols);
-  hipLaunchKernelGGL(topk_stats_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, d_scores, n_cols, k, d_mean, d_std);
-  SK_HIP(hipGetLastError());
-  return SK_OK;
-}
-
-int sc_snorm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t,
-                   const float* d_std_t, void* stream) {
-  SK_CHECK(d_S && d_mean_e && d_std_e && d_mean_t && d_std_t && Ne > 0 && Nt > 0, SK_EARG, "sc_snorm_apply: bad arguments");
-  hipLaunchKernelGGL(snorm_apply_kernel, dim3((unsigned)(((long)Ne * Nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_S, Ne, Nt,
-                     d_mean_e, d_std_e, d_mean_t, d_std_t);
-  SK_HIP(hipGetLastError());
-  return SK_OK;
-}
-
 int sc_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, const int32_t* d_labels_e, const int32_t* d_labels_t,
                    int32_t self_offset, float lo, float hi, int32_t nbins, uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream) {
-  SK_CHECK(d_E && d_T && d_labels_e && d_labels_t && d_hist_tar && d_hist_non && Ne > 0 && Nt > 0 && D > 0 && D % 4 == 0, SK_EARG,
+  SK_CHECK(hist_args_ok(d_E, d_T, d_labels_e, d_labels_t, d_hist_tar, d_hist_non, Ne, Nt, D) && D % 4 == 0, SK_EARG,
            "sc_cosine_hist: bad arguments (D must be a multiple of 4)");
   SK_CHECK(nbins == HB && hi > lo, SK_EARG, "sc_cosine_hist: nbins must be %d and hi > lo", HB);
   return launch_cosine_hist<HN_NONE>(d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, HistNorm{nullptr, nullptr, nullptr, nullptr}, lo, hi,
@@ -598,7 +516,7 @@ int sc_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, i
 int sc_cosine_hist_norm(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, const int32_t* d_labels_e, const int32_t* d_labels_t,
                         int32_t self_offset, const float* d_mean_e, const float* d_std_e, const float* d_mean_t, const float* d_std_t, float lo,
                         float hi, int32_t nbins, uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream) {
-  SK_CHECK(d_E && d_T && d_labels_e && d_labels_t && d_hist_tar && d_hist_non && Ne > 0 && Nt > 0 && D > 0 && D % 4 == 0, SK_EARG,
+  SK_CHECK(hist_args_ok(d_E, d_T, d_labels_e, d_labels_t, d_hist_tar, d_hist_non, Ne, Nt, D) && D % 4 == 0, SK_EARG,
            "sc_cosine_hist_norm: bad arguments (D must be a multiple of 4)");
   SK_CHECK(nbins == HB && hi > lo, SK_EARG, "sc_cosine_hist_norm: nbins must be %d and hi > lo", HB);
   const bool e = d_mean_e && d_std_e, t = d_mean_t && d_std_t;   // sc_norm_apply's rules

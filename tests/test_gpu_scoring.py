@@ -250,6 +250,19 @@ def test_device_resident_scoring(gpu):
     assert numpy.array_equal(p.cpu().numpy(), iv_scoring.plda_matrix(e.double().cpu().numpy(), t.double().cpu().numpy(), Phi, Psi, 1.5, 1.0))
 
 
+def test_cosine_bits_do_not_depend_on_the_tile(gpu):
+    """sc_cosine's 128 x 128 kernel (2048 rows and up) and its 64 x 64 kernel run the same k-ordered FMA chain per element: scoring 2049
+    rows at once (a ragged seventeenth row tile) and in calls of at most 2047 rows gives the same bits.  129 columns: one full column
+    tile and a single-column one; D = 36: one full k-tile and a 4-wide tail."""
+    g = torch.Generator(device=gpu).manual_seed(36)
+    e = torch.nn.functional.normalize(torch.randn(2049, 36, device=gpu, generator=g), dim=1).contiguous()
+    t = torch.nn.functional.normalize(torch.randn(129, 36, device=gpu, generator=g), dim=1).contiguous()
+    whole = iv_scoring.cosine_matrix_device(e, t).cpu().numpy()
+    parts = torch.cat([iv_scoring.cosine_matrix_device(e[a:a + 2047].contiguous(), t) for a in (0, 2047)]).cpu().numpy()
+    assert whole.shape == parts.shape == (2049, 129) and numpy.isfinite(whole).all() and numpy.abs(whole).max() > 0.1
+    assert numpy.array_equal(whole.view(numpy.uint32), parts.view(numpy.uint32))
+
+
 def test_cosine_histograms_match_the_score_matrix(gpu):
     """The matrix-free path counts exactly the scores sc_cosine would have written (same MFMA arithmetic, same bins), drops the
     self-trials of a row shard, and its ROCCH EER is that of the binned scores -- within +-0.05 % absolute of the exact EER."""
