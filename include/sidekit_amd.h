@@ -267,6 +267,19 @@ int sc_plda_hist(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, i
                  double cst, double scaling, const int32_t* d_labels_e, const int32_t* d_labels_t, int32_t self_offset, double lo,
                  double hi, int32_t nbins, uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream);
 
+/* The same histograms of cohort-normalised PLDA scores: what sc_cosine_hist_norm is to sc_cosine_hist.  Every score is the double
+ * sc_plda_hist forms and goes through the expression of sc_norm_apply_f64 for the mode (the enrolment pair alone, the test pair alone,
+ * or both), with IEEE float64 operations in that order, before sc_plda_hist's float64 binning: the counts are exactly those of
+ * sc_plda_fast + sc_norm_apply_f64 + binning the matrix, which is never formed.  d_mean_e / d_std_e: Ne entries, d_mean_t / d_std_t: Nt
+ * entries (sc_plda_cohort_moments or sc_topk_stats_f64 produce them); a mean and its std come together and at least one pair is given,
+ * anything else is SK_EARG.  A normalised score that is not finite (a zero std gives +-inf or NaN) has no bin and shows as a missing
+ * trial in the total: callers check the stds first (sidekit_amd.iv_scoring.plda_histograms does).  Everything else is sc_plda_hist's.
+ * zt-norm is not here. */
+int sc_plda_hist_norm(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
+                      double cst, double scaling, const int32_t* d_labels_e, const int32_t* d_labels_t, int32_t self_offset,
+                      const double* d_mean_e, const double* d_std_e, const double* d_mean_t, const double* d_std_t, double lo, double hi,
+                      int32_t nbins, uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream);
+
 /* Speaker-mean enrolment + cosine over a listed trial set, sidekit/bin/compute_spk_cosine.py:18-26:
  * out[k] = <E[enr_idx[k]], T[tst_idx[k]]> / (|E| |T|), float32 in, float64 maths. */
 int sc_cosine_trials(const float* d_E, const float* d_T, int32_t D, const int32_t* d_enr_idx, const int32_t* d_tst_idx,
@@ -299,6 +312,33 @@ int sc_cohort_moments(const float* d_X, int32_t N, const float* d_C, int32_t M, 
  * as in the reference. */
 int sc_norm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t,
                   const float* d_std_t, void* stream);
+
+/* Cohort normalisation of PLDA log-likelihood ratios, float64 throughout (what score_normalization.py's znorm / tnorm / asnorm applied
+ * to fast_PLDA_scoring output amount to).
+ *
+ * sc_plda_cohort_moments: for every row i of X (N x D, centred as sc_plda_fast takes them) the mean and the population standard
+ * deviation of
+ *   v_ij = scaling * (0.5 x_i' Phi x_i + 0.5 c_j' Phi c_j + cst + x_i' Psi c_j)    over the M cohort rows j,
+ * each the double sc_plda_fast(X, C) would store at [i][j] (the same preparation launch, the same f64 MFMA chain over ascending k, the
+ * same epilogue expression); the N x M matrix is never written.  self_offset is sc_cohort_moments': >= 0 drops the pair
+ * j == i + self_offset (divisor M - 1 for such a row), < 0 keeps every pair.  The sums are float64 (s1 += v, s2 = fma(v, v, s2)), added
+ * in an order that depends on M alone (partials through the sc_* workspace, no floating-point atomics); the variance is clamped at 0.
+ * The statistics of the TEST side of a trial, s(c_j, t_i) with cross term t_i' Psi' c_j, are this call with the transpose of Psi.
+ * N == 0 does nothing; M <= 0, D <= 0, a null pointer with N > 0, or a row that keeps no pair is SK_EARG before anything is enqueued.
+ * The stream contract and the intermediate buffer are sc_plda_fast's. */
+int sc_plda_cohort_moments(const double* d_X, int32_t N, const double* d_C, int32_t M, int32_t D, const double* d_Phi,
+                           const double* d_Psi, double cst, double scaling, int32_t self_offset, double* d_mean, double* d_std,
+                           void* stream);
+
+/* sc_topk_stats for float64 rows: an exact radix select on the order-preserving 64-bit integer image of the doubles (eight 8-bit
+ * passes), then the mean and the unbiased std of the k largest; ties at the threshold contribute exactly the copies any valid top-k
+ * keeps.  1 < k <= n_cols, else SK_EARG. */
+int sc_topk_stats_f64(const double* d_scores, int32_t n_rows, int32_t n_cols, int32_t k, double* d_mean, double* d_std, void* stream);
+
+/* sc_norm_apply on a float64 matrix, in place: the same three modes, the same expressions in the same order.  A mean without its std,
+ * or neither pair, is SK_EARG; a zero std gives what IEEE division gives. */
+int sc_norm_apply_f64(double* d_S, int32_t Ne, int32_t Nt, const double* d_mean_e, const double* d_std_e, const double* d_mean_t,
+                      const double* d_std_t, void* stream);
 
 /* Mean and population std of the rows (axis = 1: scoremat.mean(1) / .std(1), :68-69) or the columns (axis = 0: :89-90) of a
  * rows x cols float32 score matrix; float64 sums in a fixed order.  skip_diag != 0 (square matrices only) leaves S[i][i] out and

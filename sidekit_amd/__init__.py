@@ -25,12 +25,15 @@ _LAZY = {
     "StatServer": "statserver",
     "cosine_scoring": "iv_scoring", "PLDA_scoring": "iv_scoring", "fast_PLDA_scoring": "iv_scoring", "full_PLDA_scoring": "iv_scoring",
     "mahalanobis_scoring": "iv_scoring", "two_covariance_scoring": "iv_scoring",
-    "plda_histograms": "iv_scoring", "plda_range_from_sample": "iv_scoring",
+    "plda_histograms": "iv_scoring", "plda_range_from_sample": "iv_scoring", "plda_norm_histograms": "iv_scoring",
     "FactorAnalyser": "factor_analyser",
     "asnorm": "score_normalization", "znorm": "score_normalization", "tnorm": "score_normalization", "ztnorm": "score_normalization",
     "asnorm_trials": "score_normalization", "cohort_stats_device": "score_normalization", "znorm_device": "score_normalization",
     "tnorm_device": "score_normalization", "snorm_device": "score_normalization", "ztnorm_device": "score_normalization",
     "normalised_histograms": "score_normalization", "normalised_range_from_sample": "score_normalization",
+    "plda_cohort_stats_device": "score_normalization", "plda_znorm_device": "score_normalization", "plda_tnorm_device": "score_normalization",
+    "plda_snorm_device": "score_normalization", "plda_normalised_histograms": "score_normalization",
+    "plda_normalised_range_from_sample": "score_normalization",
     "vad_energy": "frontend.vad",
     "write_matrix_hdf5": "sidekit_io", "read_plda_hdf5": "sidekit_io", "write_plda_hdf5": "sidekit_io",
 }

@@ -74,11 +74,15 @@ SIGNATURES = {
     "sc_cosine_hist": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _I32, ctypes.c_float, ctypes.c_float, _I32, _P, _P, _P]),
     "sc_cosine_hist_norm": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I32, _P, _P, _P]),
     "sc_plda_hist": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _F64, _F64, _P, _P, _I32, _F64, _F64, _I32, _P, _P, _P]),
+    "sc_plda_hist_norm": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _F64, _F64, _P, _P, _I32, _P, _P, _P, _P, _F64, _F64, _I32, _P, _P, _P]),
     "sc_cosine_trials": (ctypes.c_int, [_P, _P, _I32, _P, _P, _I64, _P, _P]),
     "sc_topk_stats": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
     "sc_snorm_apply": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
     "sc_cohort_moments": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _I32, _P, _P, _P]),
     "sc_norm_apply": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "sc_plda_cohort_moments": (ctypes.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _F64, _F64, _I32, _P, _P, _P]),
+    "sc_topk_stats_f64": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
+    "sc_norm_apply_f64": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
     "sc_matrix_moments": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "sc_class_sums": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P]),
     "sc_gemm_tn": (ctypes.c_int, [_P, _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P]),

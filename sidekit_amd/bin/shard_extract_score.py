@@ -15,7 +15,10 @@ score matrix fits: the last ``--norm-cohort`` rows of the corpus (PLDA training 
 before them is counted (``score_normalization.normalised_histograms``, row shards and the all-reduce as above).
 ``--all-pairs-plda`` (on its own: it implies no other flag) counts the PLDA log-likelihood ratios of every pair ``i != j`` of the corpus
 the same way (``plda_histograms``: the back-end-normalised rows, the run's own ``(mu, F, Sigma)``, row shards, one all-reduce) and reports
-``plda_all_pairs_eer``.  Without ``torch.distributed.run`` it runs as a single rank.
+``plda_all_pairs_eer``.  ``--all-pairs-plda-norm s|as`` (with ``--all-pairs-plda``) adds the s- or adaptive s-normalised PLDA scores:
+cohort and trials as for ``--all-pairs-norm`` (the last ``--norm-cohort`` back-end-normalised rows; every pair ``i != j`` of the rows before
+them), ``score_normalization.plda_normalised_histograms`` on row shards, the same all-reduce; it reports ``plda_all_pairs_norm_eer``.
+Without ``torch.distributed.run`` it runs as a single rank.
 
 The corpus: speaker s is a fixed set of sinusoids (``RandomState(0)``), an utterance adds per-utterance phases, amplitude
 jitter and white noise (a batch is generated on the device with seed ``1000 + index of its first utterance``) -- enough
@@ -129,6 +132,10 @@ def main(argv=None, model=None, scoring=None, keep=None):
                     help="also count the PLDA scores of every pair of the corpus into histograms (no N x N float64 matrix); needs no other flag")
     ap.add_argument("--plda-hist-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="range of the PLDA all-pairs histograms; default: from a sample of this run's PLDA scores (as --hist-range: runs to be compared share it)")
+    ap.add_argument("--all-pairs-plda-norm", default=None, choices=["s", "as"],
+                    help="with --all-pairs-plda: also the histograms of s-normalised (s) or adaptive s-normalised (as) PLDA scores; cohort and K are --norm-cohort / --norm-topk")
+    ap.add_argument("--plda-norm-hist-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="range of the normalised PLDA histograms; default: from a sample of this run's normalised PLDA scores (as --hist-range: runs to be compared share it)")
     ap.add_argument("--seed", type=int, default=0, help="corpus seed: another draw of speaker labels, phases, amplitude jitter and noise for the same speaker table")
     ap.add_argument("--plda", default=None, help="PLDA (mu, F, Sigma): SIDEKIT HDF5 or .npz; default: moment estimate from the corpus")
     ap.add_argument("--plda-train", default="moments", choices=["moments", "em"],
@@ -140,17 +147,23 @@ def main(argv=None, model=None, scoring=None, keep=None):
     args = ap.parse_args(argv)
     if args.plda_hist_range and not args.plda_hist_range[1] > args.plda_hist_range[0]:
         ap.error("--plda-hist-range: HI must exceed LO")
-    if args.all_pairs_norm:
-        if not args.all_pairs:
-            ap.error("--all-pairs-norm requires --all-pairs")
+    if args.plda_norm_hist_range and not args.plda_norm_hist_range[1] > args.plda_norm_hist_range[0]:
+        ap.error("--plda-norm-hist-range: HI must exceed LO")
+    if args.all_pairs_norm and not args.all_pairs:
+        ap.error("--all-pairs-norm requires --all-pairs")
+    if args.all_pairs_plda_norm and not args.all_pairs_plda:
+        ap.error("--all-pairs-plda-norm requires --all-pairs-plda")
+    for flag, kind in (("--all-pairs-norm", args.all_pairs_norm), ("--all-pairs-plda-norm", args.all_pairs_plda_norm)):
+        if not kind:
+            continue
         if not 0 < args.norm_cohort <= args.utterances - 2 * args.trials:
             ap.error(f"--norm-cohort {args.norm_cohort}: the cohort comes out of the {args.utterances - 2 * args.trials} PLDA training rows")
         if args.utterances - args.norm_cohort < 2:
             ap.error("--norm-cohort leaves no pair to score")
-        if args.all_pairs_norm == "as" and not 1 < args.norm_topk <= args.norm_cohort:
+        if kind == "as" and not 1 < args.norm_topk <= args.norm_cohort:
             ap.error(f"--norm-topk {args.norm_topk}: need 1 < K <= --norm-cohort ({args.norm_cohort})")
         if args.device != "cuda":
-            ap.error("--all-pairs-norm runs on the GPU (sidekit_amd.score_normalization has no CPU fallback)")
+            ap.error(f"{flag} runs on the GPU (sidekit_amd.score_normalization has no CPU fallback)")
     scoring = iv_scoring if scoring is None else scoring
     assert args.utterances >= 2 * args.trials + 2 * args.speakers, "need utterances for enrolment, test and PLDA training"
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -315,13 +328,35 @@ def main(argv=None, model=None, scoring=None, keep=None):
         plo, phi = (float(v) for v in edges.cpu())
         pht, phn = scoring.plda_histograms(rows_all[a:b], rows_all, lab_d[a:b], lab_d, mu, F, Sigma, self_offset=a, lo=plo, hi=phi, device=dev,
                                            **({"bins": args.hist_bins} if args.hist_bins else {}))
-        pcounts = torch.as_tensor(numpy.stack([pht, phn]).astype(numpy.int64), device=dev)
+        pparts, t_pnorm = [pht, phn], 0.0
+        if args.all_pairs_plda_norm:
+            # the same again for s-normalised PLDA scores: cohort = the last M (back-end-normalised) rows, trials = every pair of the rows
+            # before them; the range comes from the same gathered rows on every rank, and the counts join the one all-reduce
+            from .. import score_normalization
+            sync()
+            t1 = time.perf_counter()
+            M = args.norm_cohort
+            corpus, cohort = rows_all[:N - M], rows_all[N - M:]
+            topk = args.norm_topk if args.all_pairs_plda_norm == "as" else None
+            qlo, qhi = args.plda_norm_hist_range if args.plda_norm_hist_range else score_normalization.plda_normalised_range_from_sample(
+                corpus, corpus, cohort, mu, F, Sigma, kind="s", topk=topk)
+            a2, b2 = shard_range(N - M, rank, world)
+            rows = corpus if (a2, b2) == (0, N - M) else corpus[a2:b2]
+            pparts += score_normalization.plda_normalised_histograms(rows, corpus, lab_d[a2:b2], lab_d[:N - M], cohort, mu, F, Sigma, kind="s", topk=topk,
+                                                                     self_offset=a2, lo=qlo, hi=qhi, bins=int(pht.shape[0]))
+            sync()
+            t_pnorm = time.perf_counter() - t1
+        pcounts = torch.as_tensor(numpy.stack(pparts).astype(numpy.int64), device=dev)
         if dist.is_initialized():
             dist.all_reduce(pcounts)
         sync()
         pcounts = pcounts.cpu().numpy()
-        out.update(plda_all_pairs=int(pcounts.sum()), plda_all_pairs_s=time.perf_counter() - t0, plda_all_pairs_hist_range=[plo, phi],
+        out.update(plda_all_pairs=int(pcounts[:2].sum()), plda_all_pairs_s=time.perf_counter() - t0 - t_pnorm, plda_all_pairs_hist_range=[plo, phi],
                    plda_all_pairs_hist_bins=int(pcounts.shape[1]), plda_all_pairs_eer=float(eer_from_histograms(pcounts[0], pcounts[1])))
+        if args.all_pairs_plda_norm:
+            out.update(plda_all_pairs_norm=int(pcounts[2:].sum()), plda_all_pairs_norm_kind=args.all_pairs_plda_norm, plda_all_pairs_norm_cohort=M,
+                       plda_all_pairs_norm_hist_range=[qlo, qhi], plda_all_pairs_norm_s=t_pnorm,
+                       plda_all_pairs_norm_eer=float(eer_from_histograms(pcounts[2], pcounts[3])))
     if keep is not None:
         keep.update(xv=xv, labels=labels, tar=tar, plda=(mu, F, Sigma))
         if transforms is not None:

@@ -168,5 +168,12 @@ int launch_normalize_rows(const float* x, float* out, int D, int B, float eps, h
 // (The f32 / f64 MFMA tiles shared between files are headers of their own: sgemm_tile.h, dgemm_tile.h.)
 extern std::mutex g_plda_mu;
 int plda_workspace_locked(hipStream_t st, size_t bytes, void** out);
+// What the PLDA entry points share: the stream's workspace cut into E . Psi (Ne x D), the partial quadratic forms of both sides
+// (nparts x Ne, nparts x Nt; a term is the sum of its partials in ascending p) and `extra_doubles` more for the caller (the buffer is ONE
+// request: a second one could free the first), and the ONE plda_prep_kernel launch that fills the first three.  The caller holds
+// g_plda_mu and keeps it until its own kernels are enqueued.
+struct PldaPrep { double *epsi, *qe, *qt, *extra; int nparts; };
+int plda_prep_locked(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
+                     hipStream_t st, PldaPrep* out, size_t extra_doubles = 0);
 
 }  // namespace sk

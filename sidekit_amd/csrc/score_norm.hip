@@ -7,7 +7,10 @@
 // sc_matrix_moments does the same for a score matrix that already exists (the Scores-level mirrors); sc_topk_stats gives the adaptive
 // statistics (the k best scores of a row); sc_norm_apply / sc_snorm_apply are the elementwise pass, one kernel with three modes.  Sums
 // are float64, partial sums go through the sc_* workspace and are added in a fixed order: no floating-point atomics.
+// PLDA log-likelihood ratios get the same in float64 throughout: sc_plda_cohort_moments (the f64 MFMA tile of dgemm_tile.h, the scores
+// of sc_plda_fast never written), sc_topk_stats_f64 and sc_norm_apply_f64 (the float32 kernels' templates at double).
 #include "../../include/sidekit_amd.h"
+#include "dgemm_tile.h"
 #include "kernels.h"
 #include "sgemm_tile.h"
 
@@ -105,8 +108,9 @@ __global__ __launch_bounds__(256, 2) void cohort_moments_kernel(const float* __r
 }
 
 // mean and population std of the values a row kept: the slabs' partials in slab order, variance clamped at 0
+template <typename T>
 __global__ __launch_bounds__(256) void cohort_moments_final_kernel(const double* __restrict__ part, int N, int slabs, int M, long self_off,
-                                                                   float* __restrict__ mean, float* __restrict__ stdv) {
+                                                                   T* __restrict__ mean, T* __restrict__ stdv) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   double a = 0.0, b = 0.0;
@@ -117,8 +121,92 @@ __global__ __launch_bounds__(256) void cohort_moments_final_kernel(const double*
   const long d = self_off >= 0 ? (long)i + self_off : -1L;
   const double cnt = (double)(M - ((d >= 0 && d < (long)M) ? 1 : 0));
   const double m = a / cnt, var = b / cnt - m * m;
-  mean[i] = (float)m;
-  stdv[i] = (float)sqrt(var > 0.0 ? var : 0.0);
+  mean[i] = (T)m;
+  stdv[i] = (T)sqrt(var > 0.0 ? var : 0.0);
+}
+
+// ---- the same statistics of PLDA log-likelihood ratios (sc_plda_cohort_moments) ----------------------------------------------------
+// v_ij = alpha * (x_i' Psi c_j + xterm(i) + cterm(j) + cst): dgemm_nt_kernel's value for sc_plda_fast(X, C), never written.  Tile:
+// 128 cohort rows x 128 X rows per 256-thread workgroup through dgemm_tile<4, false>, the COHORT as the tile's row operand and X . Psi
+// (plda_prep_kernel's) as its column operand: a * b is commutative, so an accumulator is the chain of v_mfma_f64_16x16x4_f64 over
+// ascending k that sc_plda_fast computes for the pair.  In the f64 accumulator map a lane's acc[i][j][q] is then cohort row
+// wm * 64 + i * 16 + lk + 4 q against X row wn * 64 + j * 16 + lr: sixteen cohort scores of ONE X row per j, so a lane carries two
+// running doubles per j (8 registers).  The two terms are summed over the partials in ascending p, X's once per workgroup, the cohort's
+// once per tile, and reach the epilogue through 2 KB of LDS as in plda_hist_kernel.  Slabs as in cohort_moments_kernel: a row's additions
+// -- lane (i, q) order inside a tile, tiles in order, the four lane groups (lk), the two cohort-side waves, then the slabs in
+// cohort_moments_final_kernel<double> -- do not depend on N, on the row's place in its tile or on the launch.
+constexpr int PCT = 128;
+
+__global__ __launch_bounds__(256, 2) void plda_cohort_moments_kernel(const double* __restrict__ XPsi, int N, const double* __restrict__ C, int M, int D,
+                                                                     const double* __restrict__ xpart, long x_stride, const double* __restrict__ cpart,
+                                                                     int nparts, double cst, double alpha, long self_off, int tiles_per_slab,
+                                                                     double* __restrict__ part) {
+  constexpr int WT = PCT / 32;
+  __shared__ __attribute__((aligned(16))) double As[PCT * DLD];
+  __shared__ __attribute__((aligned(16))) double Bs[PCT * DLD];
+  __shared__ double term[2 * PCT];   // [0, PCT): the tile's cohort terms, [PCT, 2 PCT): the workgroup's X terms
+  __shared__ double red[PCT][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;   // wm: cohort side, wn: X side
+  const int n0 = blockIdx.x * PCT;
+  const int tiles_m = (M + PCT - 1) / PCT, t0 = blockIdx.y * tiles_per_slab, t1 = t0 + tiles_per_slab < tiles_m ? t0 + tiles_per_slab : tiles_m;
+  if (tid >= PCT) {   // rows past the end are never written
+    double t = 0.0;
+    if (n0 + tid - PCT < N) for (int p = 0; p < nparts; ++p) t += xpart[(long)p * x_stride + n0 + tid - PCT];
+    term[tid] = t;    // read after the first tile's barriers
+  }
+  double s1[WT], s2[WT];
+#pragma unroll
+  for (int j = 0; j < WT; ++j) { s1[j] = 0.0; s2[j] = 0.0; }
+  for (int t = t0; t < t1; ++t) {
+    const int c0 = t * PCT;
+    f64x4 acc[WT][WT];
+    dgemm_tile<WT, false>(C, XPsi, M, N, D, c0, n0, As, Bs, acc);
+    if (tid < PCT) {   // the k loop's barriers lie between the previous tile's last read of `term` and this write
+      double tsum = 0.0;   // (summed here, not across the k loop: the kernel sits at its 256 registers)
+      if (c0 + tid < M) for (int p = 0; p < nparts; ++p) tsum += cpart[(long)p * M + c0 + tid];
+      term[tid] = tsum;
+    }
+    __syncthreads();
+    // (a dropped value enters the sums as an exact zero: the kept values' additions are unchanged by it)
+#pragma unroll
+    for (int j = 0; j < WT; ++j) {
+      const int ln_ = wn * 16 * WT + j * 16 + lr;
+      const long drop = self_off >= 0 ? (long)(n0 + ln_) + self_off : -1L;
+      const double xt = term[PCT + ln_];
+#pragma unroll
+      for (int i = 0; i < WT; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int lm = wm * 16 * WT + i * 16 + lk + 4 * q, m = c0 + lm;
+          double v = alpha * (acc[i][j][q] + xt + term[lm] + cst);   // dgemm_nt_kernel's expression: X is sc_plda_fast's row side
+          v = (m < M && (long)m != drop) ? v : 0.0;
+          s1[j] += v;
+          s2[j] = fma(v, v, s2[j]);
+        }
+    }
+  }
+  // the four lane groups hold the four interleaved quarters of a 16-row block, the two wm waves a tile's two 64-row halves
+#pragma unroll
+  for (int j = 0; j < WT; ++j) {
+    s1[j] += __shfl_xor(s1[j], 16);
+    s2[j] += __shfl_xor(s2[j], 16);
+    s1[j] += __shfl_xor(s1[j], 32);
+    s2[j] += __shfl_xor(s2[j], 32);
+    const int row = wn * 16 * WT + j * 16 + lr;
+    if (wm == 1 && lk == 0) { red[row][0] = s1[j]; red[row][1] = s2[j]; }
+  }
+  __syncthreads();
+  if (wm == 0 && lk == 0) {
+#pragma unroll
+    for (int j = 0; j < WT; ++j) {
+      const int row = wn * 16 * WT + j * 16 + lr, n = n0 + row;
+      if (n >= N) continue;
+      double* o = part + ((long)blockIdx.y * N + n) * 2;
+      o[0] = s1[j] + red[row][0];
+      o[1] = s2[j] + red[row][1];
+    }
+  }
 }
 
 // ---- moments of a score matrix that exists (the Scores-level mirrors) ------------------------------------------------------------
@@ -177,26 +265,37 @@ __global__ __launch_bounds__(256) void col_moments_kernel(const float* __restric
 // Mean and unbiased std of the k largest values of every row: an exact radix select on the order-preserving
 // integer image of the floats (four 8-bit passes narrow the k-th largest key), then one pass of sums.  Ties at the
 // threshold contribute exactly the copies torch.topk would keep, so the statistics equal those of any valid top-k.
+// sc_topk_stats_f64 is the same kernel at double: eight 8-bit passes over the 64-bit image.
 __device__ inline unsigned fkey(float f) {
   const unsigned u = __builtin_bit_cast(unsigned, f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // larger float <=> larger key
 }
+__device__ inline unsigned long long fkey(double f) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, f);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+template <typename T> struct key_of;
+template <> struct key_of<float> { typedef unsigned type; };
+template <> struct key_of<double> { typedef unsigned long long type; };
 
-__global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict__ x, int ncols, int k, float* __restrict__ mean,
-                                                         float* __restrict__ stdv) {
+template <typename T>
+__global__ __launch_bounds__(256) void topk_stats_kernel(const T* __restrict__ x, int ncols, int k, T* __restrict__ mean,
+                                                         T* __restrict__ stdv) {
+  typedef typename key_of<T>::type K;
   __shared__ unsigned hist[256];
-  __shared__ unsigned s_prefix, s_remaining;
+  __shared__ K s_prefix;
+  __shared__ unsigned s_remaining;
   __shared__ double red[2 * 256];
-  const float* row = x + (size_t)blockIdx.x * ncols;
+  const T* row = x + (size_t)blockIdx.x * ncols;
   const int tid = threadIdx.x;
-  unsigned prefix = 0, mask = 0;
+  K prefix = 0, mask = 0;
   unsigned remaining = (unsigned)k;   // how many of the still-undecided keys belong to the top-k
-  for (int shift = 24; shift >= 0; shift -= 8) {
+  for (int shift = 8 * (int)sizeof(K) - 8; shift >= 0; shift -= 8) {
     hist[tid] = 0;
     __syncthreads();
     for (int i = tid; i < ncols; i += 256) {
-      const unsigned key = fkey(row[i]);
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+      const K key = fkey(row[i]);
+      if ((key & mask) == prefix) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
     }
     __syncthreads();
     if (tid == 0) {
@@ -206,26 +305,26 @@ __global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict
         if (acc + hist[b] >= remaining) break;
         acc += hist[b];
       }
-      s_prefix = prefix | ((unsigned)b << shift);
+      s_prefix = prefix | ((K)b << shift);
       s_remaining = remaining - acc;
     }
     __syncthreads();
     prefix = s_prefix;
     remaining = s_remaining;
-    mask |= 255u << shift;
+    mask |= (K)255u << shift;
     __syncthreads();
   }
   // prefix == key of the k-th largest value; `remaining` copies of it are inside the top-k
   double s1 = 0.0, s2 = 0.0;
-  float tval = 0.f;
+  T tval = 0;
   for (int i = tid; i < ncols; i += 256) {
-    const float v = row[i];
-    const unsigned key = fkey(v);
+    const T v = row[i];
+    const K key = fkey(v);
     if (key > prefix) { s1 += (double)v; s2 += (double)v * (double)v; }
     if (key == prefix) tval = v;
   }
   red[tid] = s1; red[256 + tid] = s2;
-  __shared__ float s_tval;
+  __shared__ T s_tval;
   if (fkey(tval) == prefix) s_tval = tval;   // every writer holds the same value
   __syncthreads();
   if (tid == 0) {
@@ -235,31 +334,31 @@ __global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict
     a += tv * (double)remaining;
     b += tv * tv * (double)remaining;
     const double m = a / (double)k;
-    mean[blockIdx.x] = (float)m;
+    mean[blockIdx.x] = (T)m;
     const double var = (b - (double)k * m * m) / (double)(k - 1);
-    stdv[blockIdx.x] = (float)sqrt(var > 0.0 ? var : 0.0);
+    stdv[blockIdx.x] = (T)sqrt(var > 0.0 ? var : 0.0);
   }
 }
 
 // S[i][j] <- (S[i][j] - me[i]) / se[i] (NA_ENROL: z-norm), (S[i][j] - mt[j]) / st[j] (NA_TEST: t-norm), or half the one plus half the
 // other (NA_BOTH: s-norm); a pair a mode does not use is never read
 enum { NA_ENROL = 1, NA_TEST = 2, NA_BOTH = 3 };
-template <int MODE>
-__global__ void norm_apply_kernel(float* __restrict__ S, int ne, int nt, const float* __restrict__ me, const float* __restrict__ se,
-                                  const float* __restrict__ mt, const float* __restrict__ st) {
+template <int MODE, typename T>
+__global__ void norm_apply_kernel(T* __restrict__ S, int ne, int nt, const T* __restrict__ me, const T* __restrict__ se,
+                                  const T* __restrict__ mt, const T* __restrict__ st) {
   const long i = blockIdx.x * 256L + threadIdx.x;
   if (i >= (long)ne * nt) return;
   const int r = (int)(i / nt), c = (int)(i % nt);
-  const float v = S[i];
+  const T v = S[i];
   if constexpr (MODE == NA_ENROL) S[i] = (v - me[r]) / se[r];
   if constexpr (MODE == NA_TEST) S[i] = (v - mt[c]) / st[c];
-  if constexpr (MODE == NA_BOTH) S[i] = 0.5f * ((v - me[r]) / se[r]) + 0.5f * ((v - mt[c]) / st[c]);
+  if constexpr (MODE == NA_BOTH) S[i] = (T)0.5 * ((v - me[r]) / se[r]) + (T)0.5 * ((v - mt[c]) / st[c]);
 }
 
-template <int MODE>
-static int launch_norm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, const float* d_std_e, const float* d_mean_t,
-                             const float* d_std_t, void* stream) {
-  hipLaunchKernelGGL(norm_apply_kernel<MODE>, dim3((unsigned)(((long)Ne * Nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_S, Ne, Nt,
+template <int MODE, typename T>
+static int launch_norm_apply(T* d_S, int32_t Ne, int32_t Nt, const T* d_mean_e, const T* d_std_e, const T* d_mean_t, const T* d_std_t,
+                             void* stream) {
+  hipLaunchKernelGGL((norm_apply_kernel<MODE, T>), dim3((unsigned)(((long)Ne * Nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_S, Ne, Nt,
                      d_mean_e, d_std_e, d_mean_t, d_std_t);
   SK_HIP(hipGetLastError());
   return SK_OK;
@@ -295,7 +394,35 @@ int sc_cohort_moments(const float* d_X, int32_t N, const float* d_C, int32_t M, 
     if (d_col_shift) hipLaunchKernelGGL(cohort_moments_kernel<true>, grid, dim3(256), 0, st, x, n, d_C, M, D, d_col_shift, d_col_scale, self_off, per, (double*)ws);
     else hipLaunchKernelGGL(cohort_moments_kernel<false>, grid, dim3(256), 0, st, x, n, d_C, M, D, d_col_shift, d_col_scale, self_off, per, (double*)ws);
     SK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cohort_moments_final_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const double*)ws, n, slabs, M, self_off, d_mean + r0, d_std + r0);
+    hipLaunchKernelGGL(cohort_moments_final_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const double*)ws, n, slabs, M, self_off, d_mean + r0, d_std + r0);
+    SK_HIP(hipGetLastError());
+  }
+  return SK_OK;
+}
+
+int sc_plda_cohort_moments(const double* d_X, int32_t N, const double* d_C, int32_t M, int32_t D, const double* d_Phi, const double* d_Psi, double cst,
+                           double scaling, int32_t self_offset, double* d_mean, double* d_std, void* stream) {
+  SK_CHECK(N >= 0 && M > 0 && D > 0, SK_EARG, "sc_plda_cohort_moments: need N >= 0, M > 0 and D > 0 (N=%d, M=%d, D=%d)", N, M, D);
+  SK_CHECK(!(M == 1 && self_offset == 0 && N > 0), SK_EARG, "sc_plda_cohort_moments: row 0 keeps no pair (M = 1 and self_offset = 0)");
+  if (N == 0) return SK_OK;
+  SK_CHECK(d_X && d_C && d_Phi && d_Psi && d_mean && d_std, SK_EARG, "sc_plda_cohort_moments: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  // slabs as in sc_cohort_moments: a function of M alone (at most 64, at least two cohort tiles each)
+  const int tiles_m = cdiv(M, PCT), per = tiles_m > 128 ? cdiv(tiles_m, 64) : 2, slabs = cdiv(tiles_m, per);
+  constexpr int ROWS = 32768;   // rows per launch: bounds the partials at slabs x 32768 x 16 B (32 MB at 64 slabs)
+  const int rows_max = N < ROWS ? N : ROWS;
+  PldaPrep w;
+  std::lock_guard<std::mutex> lock(g_plda_mu);   // held until every launch is enqueued (see plda_workspace_locked)
+  // ONE workspace request: X . Psi, the quadratic-form partials of X (as E) and of the cohort (as T), and the moment partials
+  SK_TRY(plda_prep_locked(d_X, N, d_C, M, D, d_Phi, d_Psi, st, &w, (size_t)slabs * rows_max * 2));
+  for (int r0 = 0; r0 < N; r0 += ROWS) {
+    const int n = N - r0 < ROWS ? N - r0 : ROWS;
+    const long self_off = self_offset >= 0 ? (long)self_offset + r0 : -1L;
+    hipLaunchKernelGGL(plda_cohort_moments_kernel, dim3(cdiv(n, PCT), slabs), dim3(256), 0, st, w.epsi + (long)r0 * D, n, d_C, M, D, w.qe + r0, (long)N,
+                       w.qt, w.nparts, cst, scaling, self_off, per, w.extra);
+    SK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cohort_moments_final_kernel<double>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const double*)w.extra, n, slabs, M, self_off,
+                       d_mean + r0, d_std + r0);
     SK_HIP(hipGetLastError());
   }
   return SK_OK;
@@ -324,7 +451,25 @@ int sc_norm_apply(float* d_S, int32_t Ne, int32_t Nt, const float* d_mean_e, con
 
 int sc_topk_stats(const float* d_scores, int32_t n_rows, int32_t n_cols, int32_t k, float* d_mean, float* d_std, void* stream) {
   SK_CHECK(d_scores && d_mean && d_std && n_rows > 0 && k > 1 && k <= n_cols, SK_EARG, "sc_topk_stats: need 1 < k <= n_cols (k=%d, n_cols=%d)", k, n_cols);
-  hipLaunchKernelGGL(topk_stats_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, d_scores, n_cols, k, d_mean, d_std);
+  hipLaunchKernelGGL(topk_stats_kernel<float>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, d_scores, n_cols, k, d_mean, d_std);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
+int sc_norm_apply_f64(double* d_S, int32_t Ne, int32_t Nt, const double* d_mean_e, const double* d_std_e, const double* d_mean_t,
+                      const double* d_std_t, void* stream) {
+  const bool e = d_mean_e && d_std_e, t = d_mean_t && d_std_t;
+  SK_CHECK(d_S && Ne > 0 && Nt > 0 && (e || t), SK_EARG, "sc_norm_apply_f64: need the matrix and at least one (mean, std) pair");
+  SK_CHECK((d_mean_e == nullptr) == (d_std_e == nullptr) && (d_mean_t == nullptr) == (d_std_t == nullptr), SK_EARG,
+           "sc_norm_apply_f64: a mean and its std come together");
+  if (e && t) return launch_norm_apply<NA_BOTH>(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);
+  if (e) return launch_norm_apply<NA_ENROL>(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);
+  return launch_norm_apply<NA_TEST>(d_S, Ne, Nt, d_mean_e, d_std_e, d_mean_t, d_std_t, stream);
+}
+
+int sc_topk_stats_f64(const double* d_scores, int32_t n_rows, int32_t n_cols, int32_t k, double* d_mean, double* d_std, void* stream) {
+  SK_CHECK(d_scores && d_mean && d_std && n_rows > 0 && k > 1 && k <= n_cols, SK_EARG, "sc_topk_stats_f64: need 1 < k <= n_cols (k=%d, n_cols=%d)", k, n_cols);
+  hipLaunchKernelGGL(topk_stats_kernel<double>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, d_scores, n_cols, k, d_mean, d_std);
   SK_HIP(hipGetLastError());
   return SK_OK;
 }

@@ -8,7 +8,7 @@
 // (C = A . B^T, v_mfma_f64_16x16x4_f64) whose epilogue adds the quadratic terms and the constant, so
 // the (Ne x Nt) matrix is written exactly once.  For
 // trial sets too large to materialise, sc_cosine_hist (cosine) and sc_plda_hist (PLDA; f64 tile of dgemm_tile.h)
-// count target / non-target scores into histograms straight from the accumulators; the entry points share one host prologue (hist_args_ok,
+// count target / non-target scores into histograms straight from the accumulators (sc_cosine_hist_norm / sc_plda_hist_norm: cohort-normalised first); the entry points share one host prologue (hist_args_ok,
 // hist_begin).  The two kernels keep their own k-tile step and LDS histogram code: through shared helpers both measured slower.
 #include <cmath>
 #include <map>
@@ -273,18 +273,31 @@ __global__ __launch_bounds__(HTHREADS) void cosine_hist_kernel(const float* __re
 // loop, and 2 KB of LDS hand them to the epilogue.  The bin is taken in float64 and clamped BEFORE the conversion to int, so +-inf
 // lands in an end bin; a NaN score is counted nowhere and the caller sees it missing from the total.  Histograms, flush and launch
 // follow cosine_hist_kernel: 2 x 32 KB of 32-bit LDS counters beside the 34 KB of operand tiles, so one workgroup (four waves) per CU.
+//
+// NORM (sc_plda_hist_norm), as in cosine_hist_kernel: HN_NONE is sc_plda_hist's kernel; the others put the score through the float64
+// expression of norm_apply_kernel<NA_ENROL | NA_TEST | NA_BOTH, double> (score_norm.hip) between the epilogue and the bin, so the counts
+// are those of sc_plda_fast + sc_norm_apply_f64 + binning.  A tile's 128 enrolment-side and 128 test-side (mean, std) go through 4 KB of
+// LDS once per tile (256 threads: one row each); HN_NONE declares none of it and reads no field of `nrm`.
 constexpr int PT = 128, PTHREADS = 256;
+struct PldaHistNorm { const double *me, *se, *mt, *st; };   // Ne, Ne, Nt, Nt entries; a side a mode does not use is never read
 
+template <int NORM>
 __global__ __launch_bounds__(PTHREADS) void plda_hist_kernel(const double* __restrict__ EPsi, int Ne, const double* __restrict__ T, int Nt, int D,
                                                              const double* __restrict__ rowpart, const double* __restrict__ colpart, int nparts,
                                                              double cst, double alpha, const int* __restrict__ le, const int* __restrict__ lt,
                                                              int self_offset, double lo, double inv_width,
-                                                             unsigned long long* __restrict__ hist_tar, unsigned long long* __restrict__ hist_non) {
+                                                             unsigned long long* __restrict__ hist_tar, unsigned long long* __restrict__ hist_non,
+                                                             PldaHistNorm nrm) {
   constexpr int WT = PT / 32;
   __shared__ unsigned hist[2 * HB];
   __shared__ __attribute__((aligned(16))) double As[PT * DLD];
   __shared__ __attribute__((aligned(16))) double Bs[PT * DLD];
   __shared__ double term[2 * PT];   // [0, PT): the tile's row terms, [PT, 2 PT): its column terms
+  double* stat = nullptr;           // [0, PT): enrolment means, [PT, 2 PT): test means, then the two stds in the same order
+  if constexpr (NORM != HN_NONE) {
+    __shared__ double stat_lds[4 * PT];
+    stat = stat_lds;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
   for (int i = tid; i < 2 * HB; i += PTHREADS) hist[i] = 0u;
@@ -307,9 +320,18 @@ __global__ __launch_bounds__(PTHREADS) void plda_hist_kernel(const double* __res
     } else if (n0 + tid - PT < Nt) {
       for (int p = 0; p < nparts; ++p) tsum += colpart[(long)p * Nt + n0 + tid - PT];
     }
+    double smean = 0.0, sstd = 1.0;   // thread t < 128: enrolment row m0 + t; else test row n0 + t - 128 (rows past the end are never binned)
+    if constexpr (NORM != HN_NONE) {
+      if (tid < PT) {
+        if ((NORM & HN_ENROL) && m0 + tid < Ne) { smean = nrm.me[m0 + tid]; sstd = nrm.se[m0 + tid]; }
+      } else if ((NORM & HN_TEST) && n0 + tid - PT < Nt) {
+        smean = nrm.mt[n0 + tid - PT]; sstd = nrm.st[n0 + tid - PT];
+      }
+    }
     f64x4 acc[WT][WT];
     dgemm_tile<WT, false>(EPsi, T, Ne, Nt, D, m0, n0, As, Bs, acc);
     term[tid] = tsum;   // the k loop's barriers lie between the previous tile's last read of `term` and this write
+    if constexpr (NORM != HN_NONE) { stat[tid] = smean; stat[2 * PT + tid] = sstd; }   // (and of `stat`)
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < WT; ++j) {
@@ -317,15 +339,21 @@ __global__ __launch_bounds__(PTHREADS) void plda_hist_kernel(const double* __res
       if (n >= Nt) continue;
       const int labn = lt[n];
       const double ct = term[PT + ln_];
+      double mtn = 0.0, stn = 1.0;
+      if constexpr ((NORM & HN_TEST) != 0) { mtn = stat[PT + ln_]; stn = stat[3 * PT + ln_]; }
 #pragma unroll
       for (int i = 0; i < WT; ++i)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int lm = wm * 16 * WT + i * 16 + lk + 4 * q, m = m0 + lm;
           if (m >= Ne || (self_offset >= 0 && m + self_offset == n)) continue;
-          const double v = alpha * (acc[i][j][q] + term[lm] + ct + cst);
+          double v = alpha * (acc[i][j][q] + term[lm] + ct + cst);
+          if constexpr (NORM == HN_ENROL) v = (v - stat[lm]) / stat[2 * PT + lm];
+          if constexpr (NORM == HN_TEST) v = (v - mtn) / stn;
+          if constexpr (NORM == HN_BOTH) v = 0.5 * ((v - stat[lm]) / stat[2 * PT + lm]) + 0.5 * ((v - mtn) / stn);
           const double x = (v - lo) * inv_width;
-          if (x != x) continue;
+          if constexpr (NORM == HN_NONE) { if (x != x) continue; }
+          else { if (!(x - x == 0.0)) continue; }   // a normalised score that is not finite (a zero std: +-inf, or NaN) has no bin
           const int bin = x < 0.0 ? 0 : (x >= (double)HB ? HB - 1 : (int)x);
           atomicAdd(&hist[(le[m] == labn ? 0 : HB) + bin], 1u);
         }
@@ -387,18 +415,19 @@ static int stream_cus(hipStream_t st) {
   return cus > 0 ? cus : 256;
 }
 
-// What sc_plda_fast and sc_plda_hist share: the stream's workspace cut into E . Psi and the partial quadratic forms, and the ONE launch
-// that fills them.  The caller holds g_plda_mu, and keeps it until its own N^2 kernel is enqueued (see plda_workspace_locked).
-struct PldaPrep { double *epsi, *qe, *qt; int nparts; };
-static int plda_prep_locked(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
-                            hipStream_t st, PldaPrep* out) {
+// What sc_plda_fast, sc_plda_hist and sc_plda_cohort_moments share (kernels.h): the stream's workspace cut into E . Psi, the partial
+// quadratic forms and what the caller asked for beyond them, and the ONE launch that fills the first three.  The caller holds g_plda_mu,
+// and keeps it until its own N^2 kernel is enqueued (see plda_workspace_locked).
+int plda_prep_locked(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
+                     hipStream_t st, PldaPrep* out, size_t extra_doubles) {
   const int ctiles = cdiv(D, 64);
   const size_t n_epsi = ((size_t)Ne * D + 1) & ~(size_t)1, n_qe = (size_t)ctiles * Ne, n_qt = (size_t)ctiles * Nt;
   void* ws = nullptr;
-  SK_TRY(plda_workspace_locked(st, (n_epsi + n_qe + n_qt) * 8, &ws));
+  SK_TRY(plda_workspace_locked(st, (n_epsi + n_qe + n_qt + extra_doubles) * 8, &ws));
   out->epsi = (double*)ws;
   out->qe = out->epsi + n_epsi;
   out->qt = out->qe + n_qe;
+  out->extra = out->qt + n_qt;
   out->nparts = ctiles;
   // model_part / seg_part = 0.5 * diag(X Phi X') as per-column-tile partials, and E . Psi   (iv_scoring.py:449-450,458)
   hipLaunchKernelGGL(plda_prep_kernel, dim3(2 * ctiles, cdiv(Ne, 64) + cdiv(Nt, 64)), dim3(256), 0, st, d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, out->qe, out->qt,
@@ -432,6 +461,22 @@ static int launch_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, in
   SK_TRY(hist_begin(d_hist_tar, d_hist_non, (long)cdiv(Ne, HT) * cdiv(Nt, HT), st, &grid));   // one workgroup per CU: 64 KB of histograms + 74 KB of operand tiles
   hipLaunchKernelGGL(cosine_hist_kernel<NORM>, dim3(grid), dim3(HTHREADS), 0, st, d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, lo,
                      (float)HB / (hi - lo), (unsigned long long*)d_hist_tar, (unsigned long long*)d_hist_non, nrm);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
+// the preparation and the persistent launch of both PLDA histogram entry points
+template <int NORM>
+static int launch_plda_hist(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
+                            double cst, double scaling, const int32_t* d_labels_e, const int32_t* d_labels_t, int32_t self_offset, PldaHistNorm nrm,
+                            double lo, double hi, uint64_t* d_hist_tar, uint64_t* d_hist_non, hipStream_t st) {
+  PldaPrep w;
+  std::lock_guard<std::mutex> lock(g_plda_mu);   // held until everything is enqueued (see plda_workspace_locked)
+  SK_TRY(plda_prep_locked(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, st, &w));
+  int grid = 0;
+  SK_TRY(hist_begin(d_hist_tar, d_hist_non, (long)cdiv(Ne, PT) * cdiv(Nt, PT), st, &grid));   // one workgroup per CU: 64 KB of histograms + 36 KB of tiles and terms (+ 4 KB of statistics)
+  hipLaunchKernelGGL(plda_hist_kernel<NORM>, dim3(grid), dim3(PTHREADS), 0, st, w.epsi, Ne, d_T, Nt, D, w.qe, w.qt, w.nparts, cst, scaling, d_labels_e,
+                     d_labels_t, self_offset, lo, (double)HB / (hi - lo), (unsigned long long*)d_hist_tar, (unsigned long long*)d_hist_non, nrm);
   SK_HIP(hipGetLastError());
   return SK_OK;
 }
@@ -472,16 +517,27 @@ int sc_plda_hist(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, i
            "sc_plda_hist: bad arguments (a null pointer or a size that is not positive)");
   SK_CHECK(nbins == HB, SK_EARG, "sc_plda_hist: nbins must be %d", HB);
   SK_CHECK(std::isfinite(lo) && std::isfinite(hi) && hi > lo, SK_EARG, "sc_plda_hist: lo and hi must be finite and hi > lo");
+  return launch_plda_hist<HN_NONE>(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, cst, scaling, d_labels_e, d_labels_t, self_offset,
+                                   PldaHistNorm{nullptr, nullptr, nullptr, nullptr}, lo, hi, d_hist_tar, d_hist_non, (hipStream_t)stream);
+}
+
+int sc_plda_hist_norm(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi, double cst,
+                      double scaling, const int32_t* d_labels_e, const int32_t* d_labels_t, int32_t self_offset, const double* d_mean_e,
+                      const double* d_std_e, const double* d_mean_t, const double* d_std_t, double lo, double hi, int32_t nbins,
+                      uint64_t* d_hist_tar, uint64_t* d_hist_non, void* stream) {
+  SK_CHECK(hist_args_ok(d_E, d_T, d_labels_e, d_labels_t, d_hist_tar, d_hist_non, Ne, Nt, D) && d_Phi && d_Psi, SK_EARG,
+           "sc_plda_hist_norm: bad arguments (a null pointer or a size that is not positive)");
+  SK_CHECK(nbins == HB, SK_EARG, "sc_plda_hist_norm: nbins must be %d", HB);
+  SK_CHECK(std::isfinite(lo) && std::isfinite(hi) && hi > lo, SK_EARG, "sc_plda_hist_norm: lo and hi must be finite and hi > lo");
+  const bool e = d_mean_e && d_std_e, t = d_mean_t && d_std_t;   // sc_norm_apply_f64's rules
+  SK_CHECK((d_mean_e == nullptr) == (d_std_e == nullptr) && (d_mean_t == nullptr) == (d_std_t == nullptr), SK_EARG,
+           "sc_plda_hist_norm: a mean and its std come together");
+  SK_CHECK(e || t, SK_EARG, "sc_plda_hist_norm: need at least one (mean, std) pair");
+  const PldaHistNorm nrm{d_mean_e, d_std_e, d_mean_t, d_std_t};
   hipStream_t st = (hipStream_t)stream;
-  PldaPrep w;
-  std::lock_guard<std::mutex> lock(g_plda_mu);   // held until everything is enqueued (see plda_workspace_locked)
-  SK_TRY(plda_prep_locked(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, st, &w));
-  int grid = 0;
-  SK_TRY(hist_begin(d_hist_tar, d_hist_non, (long)cdiv(Ne, PT) * cdiv(Nt, PT), st, &grid));   // one workgroup per CU: 64 KB of histograms + 36 KB of tiles and terms
-  hipLaunchKernelGGL(plda_hist_kernel, dim3(grid), dim3(PTHREADS), 0, st, w.epsi, Ne, d_T, Nt, D, w.qe, w.qt, w.nparts, cst, scaling, d_labels_e,
-                     d_labels_t, self_offset, lo, (double)HB / (hi - lo), (unsigned long long*)d_hist_tar, (unsigned long long*)d_hist_non);
-  SK_HIP(hipGetLastError());
-  return SK_OK;
+  if (e && t) return launch_plda_hist<HN_BOTH>(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, cst, scaling, d_labels_e, d_labels_t, self_offset, nrm, lo, hi, d_hist_tar, d_hist_non, st);
+  if (e) return launch_plda_hist<HN_ENROL>(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, cst, scaling, d_labels_e, d_labels_t, self_offset, nrm, lo, hi, d_hist_tar, d_hist_non, st);
+  return launch_plda_hist<HN_TEST>(d_E, Ne, d_T, Nt, D, d_Phi, d_Psi, cst, scaling, d_labels_e, d_labels_t, self_offset, nrm, lo, hi, d_hist_tar, d_hist_non, st);
 }
 
 int sc_normalize_rows(const float* d_X, int32_t N, int32_t D, float* d_out, void* stream) {

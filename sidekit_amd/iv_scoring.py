@@ -1,6 +1,6 @@
 """Trial scoring -- mirror of ``sidekit/iv_scoring.py``: ``cosine_scoring`` (:63-113), ``PLDA_scoring``
 (:215-269), ``full_PLDA_scoring`` (:272-368), ``fast_PLDA_scoring`` (:370-477), ``plda_histograms`` / ``plda_range_from_sample`` (the scores of
-:448-462 for every pair of a corpus, counted instead of stored), and -- beyond SURVEY 8's rows, because they are
+:448-462 for every pair of a corpus, counted instead of stored; ``plda_norm_histograms``: cohort-normalised first), and -- beyond SURVEY 8's rows, because they are
 the same device entry point with other matrices -- ``mahalanobis_scoring`` (:116-156) and ``two_covariance_scoring`` (:159-213).
 
 The trial matrix is computed on the GPU through the C ABI (``sc_cosine``: f32 MFMA GEMM;
@@ -286,15 +286,19 @@ def _hist_device(device, *tensors):
     return _device(device if device is not None else next((x.device for x in tensors if torch.is_tensor(x) and x.is_cuda), None))
 
 
-def _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, lo, hi, device):
-    """One ``sc_plda_hist`` call on resident operands: the two ``HIST_BINS``-bin uint64 histograms over ``[lo, hi)``."""
+def _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, lo, hi, device, norm_ptrs=None):
+    """One ``sc_plda_hist`` call on resident operands (``sc_plda_hist_norm`` with the four statistics pointers ``norm_ptrs``): the two
+    ``HIST_BINS``-bin uint64 histograms over ``[lo, hi)``."""
     ht = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
     hn = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
+    head = (e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], phi.data_ptr(), psi.data_ptr(), float(cst), float(scaling_factor),
+            le.data_ptr(), lt.data_ptr(), -1 if self_offset is None else int(self_offset))
+    tail = (float(lo), float(hi), HIST_BINS, ht.data_ptr(), hn.data_ptr(), _stream(device))
     with torch.cuda.device(device):
-        _lib.check(_lib.lib().sc_plda_hist(e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], phi.data_ptr(), psi.data_ptr(),
-                                           float(cst), float(scaling_factor), le.data_ptr(), lt.data_ptr(),
-                                           -1 if self_offset is None else int(self_offset), float(lo), float(hi), HIST_BINS, ht.data_ptr(),
-                                           hn.data_ptr(), _stream(device)))
+        if norm_ptrs is None:
+            _lib.check(_lib.lib().sc_plda_hist(*head, *tail))
+        else:
+            _lib.check(_lib.lib().sc_plda_hist_norm(*head, *norm_ptrs, *tail))
     return ht.cpu().numpy().astype(numpy.uint64), hn.cpu().numpy().astype(numpy.uint64)
 
 
@@ -312,6 +316,27 @@ def plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu
     What needs no device raises ``ValueError`` before one is touched: missing ``lo`` / ``hi`` or ``hi <= lo``, vectors that are not matrices
     of one width, a width other than ``len(mu)``, ``F.shape[0]`` or ``Sigma.shape``, labels that are not one per row, ``bins``, and non-finite
     ``mu`` / ``F`` / ``Sigma`` / ``G``; centred vectors that are not finite raise it after one device reduction."""
+    return _plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor, self_offset, lo, hi, bins,
+                            device, None, None)
+
+
+def plda_norm_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G=None, scaling_factor=1., self_offset=None, *,
+                         enroll_norm=None, test_norm=None, lo=None, hi=None, bins=None, device=None):
+    """``plda_histograms`` of cohort-normalised scores: what ``cosine_histograms(enroll_norm=, test_norm=)`` is to cosine scores.
+
+    ``enroll_norm`` / ``test_norm``: ``(mean, std)`` float64 vectors, one entry per enrolment / test row (device tensors are used as given;
+    ``score_normalization.plda_cohort_stats_device`` makes them).  The scores are normalised before they are binned
+    (``sc_plda_hist_norm``): ``enroll_norm`` alone is z-norm, ``test_norm`` alone t-norm, both s-norm -- the bits of ``sc_plda_fast`` followed
+    by ``sc_norm_apply_f64``.  A pair of the wrong length, a mean without its std, or a std that is not finite and positive raise
+    ``ValueError`` before any launch; ``lo`` / ``hi`` are the range of the NORMALISED scores
+    (``score_normalization.plda_normalised_range_from_sample``).  Both ``None``: ``plda_histograms`` itself (``sc_plda_hist``).  Every other
+    argument and check is ``plda_histograms``'.  (The two keywords live here and not on ``plda_histograms``, whose parameter list is fixed.)"""
+    return _plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor, self_offset, lo, hi, bins,
+                            device, enroll_norm, test_norm)
+
+
+def _plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor, self_offset, lo, hi, bins, device,
+                     enroll_norm, test_norm):
     if lo is None or hi is None:
         raise ValueError("plda_histograms: lo and hi are required (log-likelihood ratios have no natural range: plda_range_from_sample)")
     if not (numpy.isfinite(lo) and numpy.isfinite(hi) and float(hi) > float(lo)):
@@ -322,13 +347,23 @@ def plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu
     enroll_labels = enroll_labels if torch.is_tensor(enroll_labels) else numpy.asarray(enroll_labels)
     test_labels = test_labels if torch.is_tensor(test_labels) else numpy.asarray(test_labels)
     mu, B, Phi, Psi, cst = _plda_hist_operands(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor)
+    enroll_norm = _norm_pair(enroll_norm, enroll_vectors.shape[0], "enroll")
+    test_norm = _norm_pair(test_norm, test_vectors.shape[0], "test")
     device = _hist_device(device, enroll_vectors, test_vectors)
     e, t = _plda_hist_vectors(enroll_vectors, test_vectors, mu, B, device)
     phi, psi = _to_device(Phi, torch.float64, device), _to_device(Psi, torch.float64, device)
     le = torch.as_tensor(enroll_labels).to(device=device, dtype=torch.int32).contiguous()
     lt = torch.as_tensor(test_labels).to(device=device, dtype=torch.int32).contiguous()
+    norm_ptrs = None
+    if enroll_norm is not None or test_norm is not None:
+        stats = [None if pair is None else tuple(_to_device(v, torch.float64, device) for v in pair) for pair in (enroll_norm, test_norm)]
+        stds = torch.cat([pair[1] for pair in stats if pair is not None])
+        if not bool((torch.isfinite(stds) & (stds > 0)).all()):                     # one reduction, one scalar back
+            raise ValueError("plda_histograms: every std of enroll_norm / test_norm must be finite and > 0")
+        norm_ptrs = tuple(None if pair is None else v.data_ptr() for pair in stats for v in (pair if pair is not None else (None, None)))
 
-    one_pass = lambda a, b: _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, a, b, device)
+    extra = () if norm_ptrs is None else (norm_ptrs,)
+    one_pass = lambda a, b: _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, a, b, device, *extra)
     return _histogram_passes(one_pass, lo, hi, bins)
 
 

@@ -16,6 +16,10 @@ along rows (the reference's line 70 broadcasts them along the segment axis: it r
 columns), and with ``sym=True`` the std is the square root of the variance of the ``n - 1`` off-diagonal values (lines 64-66 omit the
 root and centre along the wrong axis).
 
+PLDA log-likelihood ratios get the same in float64 (``plda_cohort_stats_device``, ``plda_znorm_device`` / ``plda_tnorm_device`` /
+``plda_snorm_device``, ``plda_normalised_histograms``, ``plda_normalised_range_from_sample``): what this module's reference functions
+applied to ``fast_PLDA_scoring`` output amount to, with the statistics from ``sc_plda_cohort_moments``.
+
 ``normalised_histograms`` is the form for trial sets whose (Ne, Nt) matrix does not fit: the z-, t-, s- or adaptive s-normalised scores of
 every pair counted into target / non-target histograms (``iv_scoring.cosine_histograms`` with the statistics of ``cohort_stats_device``;
 ``sc_cosine_hist_norm`` normalises each score between the GEMM's accumulator and its bin, in ``sc_norm_apply``'s expressions, so the counts
@@ -294,6 +298,183 @@ def normalised_range_from_sample(enroll_xv, test_xv, cohort_xv, kind="s", topk=N
         tnorm_device(z, ts, cohort)
     else:
         snorm_device(z, es, ts, cohort, topk=topk)
+    if es is ts:
+        z = z[~torch.eye(z.shape[0], dtype=torch.bool, device=device)]               # a set against itself: the self-trials are not trials
+    zmin, zmax = float(z.min()), float(z.max())
+    pad = 0.25 * (zmax - zmin)
+    return zmin - pad, zmax + pad
+
+
+# ---- PLDA log-likelihood ratios: the same normalisations in float64 -----------------------------------------------------------------
+def _plda_model(xv, cohort_xv, mu, F, Sigma, G, scaling_factor, what="x-vectors"):
+    """The host half (``iv_scoring._plda_hist_operands``: every check that needs no device, then the D x D algebra) for ``xv`` against the
+    cohort: ``(mu, B, Phi, Psi, cst)``."""
+    from .iv_scoring import _plda_hist_operands
+    _shape2(xv, what), _shape2(cohort_xv, "cohort")
+    if cohort_xv.shape[0] == 0:
+        raise ValueError("the cohort is empty")
+    return _plda_hist_operands(xv, cohort_xv, None, None, mu, F, Sigma, G, scaling_factor)
+
+
+def _check_plda_topk(topk, self_offset, m):
+    if topk is not None:
+        if self_offset is not None:
+            raise ValueError("self_offset applies to whole-cohort statistics (topk=None) only")
+        if not 1 < int(topk) <= m:
+            raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={m})")
+
+
+def _plda_stats_prepared(x, c, Phi, Psi, cst, scaling_factor, side, topk, self_offset, max_workspace_bytes):
+    """``plda_cohort_stats_device`` on operands that are centred (and projected), float64, contiguous and on the device."""
+    from .iv_scoring import _to_device
+    device = x.device
+    n, d = x.shape
+    m = c.shape[0]
+    phi = _to_device(Phi, torch.float64, device)
+    psi = _to_device(numpy.ascontiguousarray(Psi.T) if side == "test" else Psi, torch.float64, device)
+    mean = torch.empty(n, dtype=torch.float64, device=device)
+    std = torch.empty(n, dtype=torch.float64, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        st = _stream(device)
+        if topk is None:
+            _lib.check(lib.sc_plda_cohort_moments(x.data_ptr(), n, c.data_ptr(), m, d, phi.data_ptr(), psi.data_ptr(), float(cst), float(scaling_factor),
+                                                  -1 if self_offset is None else int(self_offset), mean.data_ptr(), std.data_ptr(), st))
+        elif n:
+            rows = max(1, min(n, int(max_workspace_bytes) // (8 * m)))
+            calib = torch.empty((rows, m), dtype=torch.float64, device=device)
+            for r0 in range(0, n, rows):
+                nr = min(rows, n - r0)
+                _lib.check(lib.sc_plda_fast(x[r0:].data_ptr(), nr, c.data_ptr(), m, d, phi.data_ptr(), psi.data_ptr(), float(cst), float(scaling_factor),
+                                            calib.data_ptr(), st))
+                _lib.check(lib.sc_topk_stats_f64(calib.data_ptr(), nr, m, int(topk), mean[r0:].data_ptr(), std[r0:].data_ptr(), st))
+    return mean, std
+
+
+def plda_cohort_stats_device(xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1., side="enrol", topk=None, self_offset=None,
+                             max_workspace_bytes=1 << 30):
+    """Per row of ``xv`` (N, D): ``(mean, std)`` of its PLDA log-likelihood ratios against the cohort (M, D), float64 **device tensors**.
+    The vectors are raw: they are centred by ``mu`` and, with ``G``, projected, as ``iv_scoring.plda_histograms`` does.
+
+    ``side="enrol"``: the scores ``s(x_i, c_j)`` of ``plda_matrix_device(x, cohort)``; ``side="test"``: ``s(c_j, x_i)``, the transposed
+    problem, whose cross term is ``x_i' Psi' c_j`` -- ``plda_parameters``' ``Psi`` is symmetric only up to rounding, so the test side
+    passes ``Psi.T``.  ``topk=None``: every cohort score counts, population std (``sc_plda_cohort_moments``; the (N, M) scores are never
+    stored); ``self_offset`` drops the pair ``j == i + self_offset``.  ``topk=k``: mean and unbiased std of the k best cohort scores
+    (``sc_plda_fast`` + ``sc_topk_stats_f64`` over row blocks whose (rows, M) float64 buffer fits in ``max_workspace_bytes``)."""
+    if side not in ("enrol", "test"):
+        raise ValueError(f"side is 'enrol' or 'test', got {side!r}")
+    mu, B, Phi, Psi, cst = _plda_model(xv, cohort_xv, mu, F, Sigma, G, scaling_factor)
+    _check_plda_topk(topk, self_offset, cohort_xv.shape[0])
+    from .iv_scoring import _plda_hist_vectors
+    device = _device_of(xv, cohort_xv)
+    x, c = _plda_hist_vectors(xv, cohort_xv, mu, B, device)
+    return _plda_stats_prepared(x, c, Phi, Psi, cst, scaling_factor, side, topk, self_offset, max_workspace_bytes)
+
+
+def _check_scores_f64(scores, ne, nt):
+    if not (torch.is_tensor(scores) and scores.is_cuda and scores.dtype == torch.float64 and scores.is_contiguous()):
+        raise ValueError("scores must be a contiguous float64 device tensor (it is normalised in place)")
+    if scores.dim() != 2 or (ne is not None and scores.shape[0] != ne) or (nt is not None and scores.shape[1] != nt):
+        raise ValueError(f"scores have shape {tuple(scores.shape)}, the x-vectors say ({ne if ne is not None else 'any'}, {nt if nt is not None else 'any'})")
+
+
+def _apply_f64(scores, enrol=None, test=None):
+    """``sc_norm_apply_f64`` in place: ``enrol`` / ``test`` are (mean, std) pairs or None."""
+    me, se = enrol if enrol is not None else (None, None)
+    mt, sd = test if test is not None else (None, None)
+    with torch.cuda.device(scores.device):
+        _lib.check(_lib.lib().sc_norm_apply_f64(scores.data_ptr(), scores.shape[0], scores.shape[1], _ptr(me), _ptr(se), _ptr(mt), _ptr(sd),
+                                                _stream(scores.device)))
+    return scores
+
+
+def plda_znorm_device(scores, enroll_xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1.):
+    """z-norm of a device (Ne, Nt) float64 PLDA score tensor (``iv_scoring.plda_matrix_device``'s), in place: ``(s_ij - m_i) / sd_i`` with
+    the statistics of enrolment i's cohort scores ``s(e_i, c)``."""
+    _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "enrolment x-vectors")
+    _check_scores_f64(scores, enroll_xv.shape[0], None)
+    return _apply_f64(scores, enrol=plda_cohort_stats_device(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, side="enrol"))
+
+
+def plda_tnorm_device(scores, test_xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1.):
+    """t-norm, in place: ``(s_ij - m_j) / sd_j`` with the statistics of the cohort's scores ``s(c, t_j)`` on test segment j."""
+    _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "test x-vectors")
+    _check_scores_f64(scores, None, test_xv.shape[0])
+    return _apply_f64(scores, test=plda_cohort_stats_device(test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, side="test"))
+
+
+def plda_snorm_device(scores, enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1., topk=None, max_workspace_bytes=1 << 30):
+    """s-norm, in place: ``0.5 ((s - m_i)/sd_i + (s - m_j)/sd_j)``; ``topk=k`` makes it adaptive (each side's k best cohort scores, unbiased
+    std).  ``test_xv is enroll_xv`` does NOT share statistics: the enrolment side's cohort scores are ``s(e, c)``, the test side's
+    ``s(c, t)``, which differ by ``Psi`` against ``Psi'`` (equal only up to rounding); both are computed."""
+    _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "enrolment x-vectors")
+    _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "test x-vectors")
+    _check_plda_topk(topk, None, cohort_xv.shape[0])
+    _check_scores_f64(scores, enroll_xv.shape[0], test_xv.shape[0])
+    e, t = _plda_side_stats("s", enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, topk, max_workspace_bytes)
+    return _apply_f64(scores, enrol=e, test=t)
+
+
+def _plda_side_stats(kind, enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, topk, max_workspace_bytes):
+    """(enrolment pair, test pair) of ``kind``; the side a kind does not use is ``None``.  The cohort is centred (and projected) once."""
+    from .iv_scoring import _plda_hist_vectors
+    mu, B, Phi, Psi, cst = _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor)
+    device = _device_of(enroll_xv, test_xv, cohort_xv)
+    e, c = _plda_hist_vectors(enroll_xv, cohort_xv, mu, B, device)
+    stats = lambda x, side: _plda_stats_prepared(x, c, Phi, Psi, cst, scaling_factor, side, topk, None, max_workspace_bytes)
+    en = stats(e, "enrol") if kind in ("z", "s") else None
+    if kind == "z":
+        return en, None
+    t = e if test_xv is enroll_xv else _plda_hist_vectors(test_xv, test_xv, mu, B, device)[0]
+    return en, stats(t, "test")
+
+
+def _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, kind, topk):
+    _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "enrolment x-vectors")
+    _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "test x-vectors")
+    _check_kind(kind, topk, cohort_xv.shape[0])
+
+
+def plda_normalised_histograms(enroll_xv, test_xv, enroll_labels, test_labels, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1., kind="s",
+                               topk=None, self_offset=None, *, lo=None, hi=None, bins=None, max_workspace_bytes=1 << 30):
+    """Target / non-target histograms ``(hist_tar, hist_non)`` of the cohort-normalised PLDA log-likelihood ratios of ALL (enrol, test)
+    pairs: ``normalised_histograms`` for PLDA.  Neither the (Ne, Nt) float64 score matrix nor (with ``topk=None``) a cohort score matrix is
+    formed.  ``kind``: ``"z"`` (``plda_znorm_device``'s expression), ``"t"`` (``plda_tnorm_device``'s) or ``"s"`` (``plda_snorm_device``'s);
+    ``topk=k``, with ``"s"`` only, is adaptive s-norm.  The vectors are raw and the model is ``(mu, F, Sigma, G, scaling_factor)`` as in
+    ``iv_scoring.plda_histograms``; ``iv_scoring.plda_norm_histograms`` does the counting with the statistics of ``plda_cohort_stats_device`` (``sc_plda_hist_norm``: the
+    counts are those of the materialised path).  ``self_offset`` (of the TRIALS: the cohort is a set of its own), ``bins`` and the labels are
+    ``plda_histograms``'.  ``lo`` / ``hi`` are required keywords (``plda_normalised_range_from_sample`` estimates them).  zt-norm is not offered."""
+    _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, kind, topk)
+    if lo is None or hi is None:
+        raise ValueError("lo and hi are required keywords: normalised scores have no default range (plda_normalised_range_from_sample estimates one)")
+    if not float(hi) > float(lo):
+        raise ValueError("histogram range: hi must exceed lo")
+    from .iv_scoring import plda_norm_histograms
+    en, tn = _plda_side_stats(kind, enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, topk, max_workspace_bytes)
+    return plda_norm_histograms(enroll_xv, test_xv, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor, self_offset, lo=lo, hi=hi, bins=bins,
+                                enroll_norm=en, test_norm=tn)
+
+
+def plda_normalised_range_from_sample(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1., kind="s", topk=None):
+    """``(lo, hi)`` for ``plda_normalised_histograms``, as ``normalised_range_from_sample`` finds it: a strided sample of at most 2 048 rows
+    per side, its materialised PLDA score matrix normalised by ``plda_znorm_device`` / ``plda_tnorm_device`` / ``plda_snorm_device`` against
+    the whole cohort (without the self-trials when the two sides are the same object), and the sample's smallest and largest normalised
+    score, each widened by a quarter of the sampled range."""
+    _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, kind, topk)
+    from .iv_scoring import _plda_hist_vectors, plda_matrix_device
+    device = _device_of(enroll_xv, test_xv, cohort_xv)
+    sample = lambda x: x[:: max(1, x.shape[0] // 2048)][:2048]
+    es = sample(enroll_xv)
+    ts = es if test_xv is enroll_xv else sample(test_xv)
+    pmu, B, Phi, Psi, cst = _plda_model(es, cohort_xv, mu, F, Sigma, G, scaling_factor)
+    e, t = _plda_hist_vectors(es, ts, pmu, B, device)
+    z = plda_matrix_device(e, t, Phi, Psi, cst, scaling_factor, device)
+    if kind == "z":
+        plda_znorm_device(z, es, cohort_xv, mu, F, Sigma, G, scaling_factor)
+    elif kind == "t":
+        plda_tnorm_device(z, ts, cohort_xv, mu, F, Sigma, G, scaling_factor)
+    else:
+        plda_snorm_device(z, es, ts, cohort_xv, mu, F, Sigma, G, scaling_factor, topk=topk)
     if es is ts:
         z = z[~torch.eye(z.shape[0], dtype=torch.bool, device=device)]               # a set against itself: the self-trials are not trials
     zmin, zmax = float(z.min()), float(z.max())
