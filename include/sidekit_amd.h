@@ -158,6 +158,18 @@ int xt_get_profile(xt_handle* h, double* ms /*[XT_PROF_SLOTS]*/, int64_t* launch
 int sk_bench_conv(int32_t shape, int32_t dtype, int32_t B, int32_t T, int32_t iters, int32_t variant, float* ms_out,
                   double* phase_cycles /* [8] mean shader cycles per kernel phase, or NULL */);
 
+/* One trunk block on caller-supplied input (diagnostic; not used by the product path): exactly the launches the forward makes for block
+ * `block` (0..15) of a finalised HalfResNet34 handle, with the handle's own packed weights -- conv1 in statistics form, the SE gate, conv2
+ * in residual form (first block of a layer: with the 1x1 shortcut in its epilogue).
+ *   d_x       block input, NHWC in the handle's compute type: [B][halve(T, lin)][W_in][C_in] (lin: stride-2 stages before the input)
+ *   h_frames  feature frames per utterance, NULL = all T
+ *   form      0 = batch tiling; 1 = small-grid tiling of conv2 (bf16 layers 3 and 4 only, SK_EARG elsewhere)
+ *   d_o1      relu(bn1(conv1(x))), [B][H_out][W_out][C] in the compute type;  d_gate  the SE gate, float32 [B][C];  d_out  the block output
+ * Rows past an utterance's length are not written: the caller pre-fills the outputs.  Scratch is allocated and released inside the call,
+ * which returns after the launches have completed. */
+int xt_debug_block(xt_handle* h, int32_t block, const void* d_x, const int32_t* h_frames, int32_t B, int32_t T, int32_t form, void* d_o1,
+                   float* d_gate, void* d_out, void* stream);
+
 const char* xt_last_error(void);
 
 /* Sample-rate conversion of one utterance on the device: `torchaudio.transforms.Resample(orig_freq, new_freq)` as

@@ -90,6 +90,7 @@ SIGNATURES = {
     "sc_scatter_within": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P]),
     "sc_whiten_rows": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _I32, _P]),
     "sk_bench_conv": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_F64)]),
+    "xt_debug_block": (ctypes.c_int, [_P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "sk_pavx": (ctypes.c_int, [_P, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
     "sk_rocch_vertices": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _P]),
     "sk_wav_probe": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P]),

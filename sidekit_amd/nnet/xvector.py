@@ -280,6 +280,53 @@ class Xtractor:
             out[n] = buf
         return out
 
+    @staticmethod
+    def block_geometry(block):
+        """Shapes of trunk block ``block`` (0..15): ``(layer index li, stride-2 stages before its input lin, C_in, W_in, C, W_out)``."""
+        if not 0 <= int(block) < 16:
+            raise ValueError(f"block {block} outside [0, 16)")
+        first = {0: 0, 3: 1, 7: 2, 13: 3}
+        li = max(l for s, l in first.items() if s <= block)
+        lin = max(li - 1, 0) if block in first else li
+        return li, lin, 32 << lin, 80 >> lin, 32 << li, 80 >> li
+
+    def debug_block(self, block, x, frames=None, form=0, fill=0.0):
+        """One trunk block on the caller's input (``xt_debug_block``; diagnostic, no product path uses it): conv1 + bn1 + ReLU, the SE gate and
+        conv2 + gate + shortcut + ReLU exactly as the forward launches them, with the handle's packed weights.
+
+        :param x: block input ``(B, H_in, W_in, C_in)`` (NHWC) on the device, in the compute type (float32 / bfloat16)
+        :param frames: feature frames per utterance (utterance b owns ``ceil(frames[b] / 2**lin)`` input rows); None: every row of ``x``
+        :param form: 0 the batch tiling, 1 the small-grid tiling of conv2 (bf16 layers 3 and 4)
+        :param fill: what the outputs hold where the kernels do not write (rows past an utterance's length)
+        :return: ``(o1 (B, H_out, W_out, C), gate (B, C) float32, out (B, H_out, W_out, C))``
+        """
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise TypeError("x must be a 4-D (B, H_in, W_in, C_in) tensor")
+        if x.device != self.device or self.device.type != "cuda":
+            raise RuntimeError(f"input is on {x.device} but the model is on {self.device}")
+        if self.model_archi != "halfresnet34":
+            raise NotImplementedError("debug_block: the HalfResNet34 trunk only")
+        key = self._dtype_key()
+        want = torch.bfloat16 if key == "bf16" else torch.float32
+        if x.dtype != want:
+            raise TypeError(f"x is {x.dtype} but the {key} trunk computes on {want}")
+        h = self._handle(key)
+        li, lin, cin, win, c, wout = self.block_geometry(block)
+        B, hin = int(x.shape[0]), int(x.shape[1])
+        if tuple(x.shape[2:]) != (win, cin) or B < 1 or hin < 1:
+            raise ValueError(f"block {block} takes (B, H_in, {win}, {cin}), got {tuple(x.shape)}")
+        x = x.contiguous()
+        T = hin << lin                                   # halve(T, lin) == H_in
+        hout = (hin + 1) // 2 if li != lin else hin
+        lens = self._lengths(frames, B, T)
+        o1 = torch.full((B, hout, wout, c), fill, dtype=want, device=x.device)
+        out = torch.full((B, hout, wout, c), fill, dtype=want, device=x.device)
+        gate = torch.full((B, c), fill, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().xt_debug_block(h, int(block), x.data_ptr(), _ptr(lens), B, T, int(form), o1.data_ptr(), gate.data_ptr(),
+                                                 out.data_ptr(), self._stream(x)))
+        return o1, gate, out
+
     def set_profile(self, on, dtype=None, slots=None):
         """Bracket the kernel launches of ``forward`` with HIP events on the launch stream (measurement only): all of
         them, or only the named classes (``slots``, names as returned by ``get_profile``) -- an event pair costs stream time."""

@@ -238,21 +238,22 @@ def test_bf16_row_tile_boundaries_and_per_utterance(model):
         model.compute_dtype = "fp32"
 
 
-def _pooling_in_float64(sd, l4, h, lens_rows, dtype):
+def _pooling_in_float64(sd, l4, h, lens_rows, dtype, prec=torch.float64):
     """attention.4 + softmax over time + weighted mean / std (pooling.py:161-168) in float64 on the kernel's own inputs: layer-4 rows
-    [B][T'][10][256] (columns d' = f*256 + c), attention.0 rows h [B*T'][128]; in bf16 the MFMA operands h and attention.4's weights are bf16."""
+    [B][T'][10][256] (columns d' = f*256 + c), attention.0 rows h [B*T'][128]; in bf16 the MFMA operands h and attention.4's weights are bf16.
+    (prec = torch.float32: the same formula as torch's float32 gives it, the yardstick of the fp32 test's tolerance.)"""
     B, T4 = l4.shape[0], l4.shape[1]
-    x = l4.reshape(B, T4, 2560).double()
+    x = l4.reshape(B, T4, 2560).to(prec)
     dp = torch.arange(2560)
     perm = (dp % 256) * 10 + dp // 256                                       # reference channel d = c*10 + f of trunk column d'
     w2 = sd["stat_pooling.attention.4.weight"].float().cpu().reshape(2560, 128)[perm]
-    b2 = sd["stat_pooling.attention.4.bias"].float().cpu()[perm].double()
+    b2 = sd["stat_pooling.attention.4.bias"].float().cpu()[perm].to(prec)
     hh = h.reshape(B, T4, 128)
     if dtype == "bf16":
         w2, hh = w2.bfloat16().float(), hh.bfloat16().float()
-    out = torch.zeros(B, 5120, dtype=torch.float64)
+    out = torch.zeros(B, 5120, dtype=prec)
     for b, n in enumerate(lens_rows):
-        e = hh[b, :n].double() @ w2.double().T + b2
+        e = hh[b, :n].to(prec) @ w2.to(prec).T + b2
         w = torch.softmax(e, dim=0)
         mu = (x[b, :n] * w).sum(0)
         out[b, :2560] = mu
@@ -285,6 +286,38 @@ def test_fused_attention_pooling_matches_float64(gpu):
             assert max(rows) == T4, (rows, T4)
             ref = _pooling_in_float64(sd, l4, h, rows, "bf16")
             assert rel(pooled, ref) < 2e-6, (lens, rel(pooled, ref))
+    finally:
+        m.set_debug(False)
+
+
+def test_fp32_attention_pooling_matches_float64(gpu, capsys):
+    """fp32 path: attention.4 as a GEMM, then the softmax over time and the weighted statistics (csrc/pool.hip, att_stats_kernel) against the same
+    arithmetic in float64 on the kernel's inputs (taps "layer4", "att_h", "pooled"), on the two ragged batches of the bf16 test.  Allowed: 8 x the
+    error torch's own float32 evaluation of the formula makes against float64 on the same inputs (the kernel's sums over time run in another order)."""
+    m = Xtractor(64, model_archi="halfresnet34", loss="aam", seed=5).to(gpu).eval()
+    m.compute_dtype = "fp32"
+    sd = m.state_dict()
+    torch.manual_seed(21)
+    wav = 0.1 * torch.randn(3, 30000).cuda()
+    cases = [(wav, [30000, 17000, 22222]), (0.1 * torch.randn(2, 200000).cuda(), [200000, 150001])]
+    m.set_debug(True)
+    try:
+        for x, lens in cases:
+            m(x, is_eval=True, lengths=lens)
+            raw = m.debug_taps(["layer4", "att_h", "pooled"])
+            B = len(lens)
+            l4 = torch.from_numpy(raw["layer4"].view(numpy.float32).copy())
+            T4 = l4.numel() // (B * 2560)
+            l4 = l4.reshape(B, T4, 10, 256)
+            h = torch.from_numpy(raw["att_h"].view(numpy.float32).copy()).reshape(B * T4, 128)
+            pooled = torch.from_numpy(raw["pooled"].view(numpy.float32).copy()).reshape(B, 5120)
+            rows = [_layer4_rows(n) for n in lens]
+            assert max(rows) == T4, (rows, T4)
+            ref = _pooling_in_float64(sd, l4, h, rows, "fp32")
+            err, err32 = rel(pooled, ref), rel(_pooling_in_float64(sd, l4, h, rows, "fp32", prec=torch.float32), ref)
+            with capsys.disabled():
+                print(f"  [fp32 pooling {lens}: {err:.2e} against float64, torch float32 {err32:.2e}]", end="")
+            assert err <= 8 * err32, (lens, err, err32)
     finally:
         m.set_debug(False)
 

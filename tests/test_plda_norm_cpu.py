@@ -40,7 +40,7 @@ def test_the_four_symbols_are_declared_exported_and_bound():
     for name, want in DECLARATIONS.items():
         assert want in text, name
         assert _lib.SIGNATURES[name] == (_lib.ctypes.c_int, ARGTYPES[name]) and getattr(lib, name).argtypes == ARGTYPES[name]
-    assert len(_lib.SIGNATURES) == 54                                                   # the 50 before them and these four
+    assert len(_lib.SIGNATURES) == 55                                                   # the 50 before them, these four and xt_debug_block
     for name in ("plda_cohort_stats_device", "plda_znorm_device", "plda_tnorm_device", "plda_snorm_device", "plda_normalised_histograms",
                  "plda_normalised_range_from_sample"):
         assert sidekit_amd._LAZY[name] == "score_normalization" and getattr(sidekit_amd, name) is getattr(sn, name)
