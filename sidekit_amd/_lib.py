@@ -146,3 +146,21 @@ def check(rc, arg_exc=ValueError):
     if rc == SK_EARG:
         raise arg_exc(msg)
     raise RuntimeError(msg)
+
+
+_torch = None   # imported at the first launch; lib() has imported it before anything can be launched
+
+
+def launch(name, device, *args, exc=ValueError):
+    """Call entry point ``name`` on ``device``: a tensor argument goes as its ``data_ptr()``, ``None`` as NULL, the device's current stream
+    is appended (its raw handle: no ``Stream`` object is built per call), and the return code goes through ``check(rc, exc)``.  The symbol
+    is looked up through ``lib()`` at call time."""
+    global _torch
+    if _torch is None:
+        import torch as _torch
+    fn, tensor = getattr(lib(), name), _torch.Tensor
+    index = device.index if device.index is not None else _torch.cuda.current_device()
+    with _torch.cuda.device(device):
+        rc = fn(*[a.data_ptr() if isinstance(a, tensor) else a for a in args], _torch._C._cuda_getCurrentRawStream(index))
+    if rc != SK_OK:
+        check(rc, exc)

@@ -9,9 +9,12 @@ epilogue).  As in the reference the 256x256 float64 algebra (inverses, slogdet) 
 ``full_PLDA_scoring`` maps onto the same device entry point: with e' = B e, t' = B t the reference's
 per-model loop is  0.5 (e'+t')' K2 (e'+t') - 0.5 t' K1 t - 0.5 e' K1 e  =  0.5 e'(K2-K1)e' +
 0.5 t'(K2-K1)t' + e' sym(K2) t'.  There is no CPU fallback.
+
+``CosineScorer`` / ``PldaScorer`` describe how one kind of trial is scored on a device (element type, entry points, the arguments after
+``D``, whether the two sides share cohort statistics, the preparation of raw vectors); the histogram functions here and
+``score_normalization`` are written once against them.
 """
 import copy
-import ctypes
 import logging
 
 import numpy
@@ -42,10 +45,6 @@ def _device(device):
     return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _to_device(x, dtype, device):
     """numpy array or torch tensor (any device) -> contiguous tensor of `dtype` on `device`; a tensor already there is used as is."""
     if torch.is_tensor(x):
@@ -53,22 +52,23 @@ def _to_device(x, dtype, device):
     return torch.as_tensor(numpy.ascontiguousarray(x, dtype=numpy.float32 if dtype == torch.float32 else numpy.float64)).to(device)
 
 
+def _matrix(symbol, e, t, group=(), exc=AssertionError):
+    """The (Ne, Nt) scores of resident operands from ``symbol`` (``sc_cosine`` / ``sc_plda_fast``; ``group`` is what follows ``D``)."""
+    out = torch.empty((e.shape[0], t.shape[0]), dtype=e.dtype, device=e.device)
+    _lib.launch(symbol, e.device, e, e.shape[0], t, t.shape[0], e.shape[1], *group, out, exc=exc)
+    return out
+
+
 def cosine_matrix_device(enroll_vectors, test_vectors, device=None):
     """(Ne, D) x (Nt, D) already-normalised vectors -> (Ne, Nt) float32 **device tensor**: x-vectors that are already on the GPU
     (fresh from ``Xtractor.forward`` or an all-gather) are scored where they are, nothing crosses PCIe."""
     device = _device(device if device is not None else (enroll_vectors.device if torch.is_tensor(enroll_vectors) and enroll_vectors.is_cuda else None))
     e, t = _to_device(enroll_vectors, torch.float32, device), _to_device(test_vectors, torch.float32, device)
-    D = e.shape[1]
-    if D % 4:  # the GEMM wants K % 4 == 0: zero columns do not change a dot product
-        pad = 4 - D % 4
+    if e.shape[1] % 4:  # the GEMM wants K % 4 == 0: zero columns do not change a dot product
+        pad = 4 - e.shape[1] % 4
         e = torch.nn.functional.pad(e, (0, pad))
         t = torch.nn.functional.pad(t, (0, pad))
-        D += pad
-    out = torch.empty((e.shape[0], t.shape[0]), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().sc_cosine(e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], D, out.data_ptr(), _stream(device)),
-                   AssertionError)
-    return out
+    return _matrix("sc_cosine", e, t)
 
 
 def normalize_rows_device(vectors, device=None):
@@ -76,8 +76,7 @@ def normalize_rows_device(vectors, device=None):
     device = _device(device if device is not None else (vectors.device if torch.is_tensor(vectors) and vectors.is_cuda else None))
     x = _to_device(vectors, torch.float32, device)
     out = torch.empty_like(x)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().sc_normalize_rows(x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), _stream(device)), AssertionError)
+    _lib.launch("sc_normalize_rows", device, x, x.shape[0], x.shape[1], out, exc=AssertionError)
     return out
 
 
@@ -90,13 +89,7 @@ def plda_matrix_device(enroll_vectors, test_vectors, Phi, Psi, cst, scaling_fact
     """scaling * (0.5 e'Phi e + 0.5 t'Phi t + cst + e'Psi t) for all pairs, float64 **device tensor** (f64 MFMA GEMM)."""
     device = _device(device if device is not None else (enroll_vectors.device if torch.is_tensor(enroll_vectors) and enroll_vectors.is_cuda else None))
     e, t = _to_device(enroll_vectors, torch.float64, device), _to_device(test_vectors, torch.float64, device)
-    phi, psi = _to_device(Phi, torch.float64, device), _to_device(Psi, torch.float64, device)
-    out = torch.empty((e.shape[0], t.shape[0]), dtype=torch.float64, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().sc_plda_fast(e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], phi.data_ptr(),
-                                           psi.data_ptr(), float(cst), float(scaling_factor), out.data_ptr(), _stream(device)),
-                   AssertionError)
-    return out
+    return _matrix("sc_plda_fast", e, t, (_to_device(Phi, torch.float64, device), _to_device(Psi, torch.float64, device), float(cst), float(scaling_factor)))
 
 
 def plda_matrix(enroll_vectors, test_vectors, Phi, Psi, cst, scaling_factor=1., device=None):
@@ -141,6 +134,59 @@ def _histogram_passes(one_pass, lo, hi, bins):
     return out_t, out_n
 
 
+def _check_bins(bins, exc):
+    bins = HIST_BINS if bins is None else int(bins)
+    if bins != HIST_BINS and (bins <= 0 or bins % (HIST_BINS - 2)):
+        raise exc(f"bins must be {HIST_BINS} or a multiple of {HIST_BINS - 2}")
+    return bins
+
+
+def _labels(labels, device):
+    return torch.as_tensor(labels).to(device=device, dtype=torch.int32).contiguous()
+
+
+def _hist_device(device, *tensors):
+    return _device(device if device is not None else next((x.device for x in tensors if torch.is_tensor(x) and x.is_cuda), None))
+
+
+def _stat_pairs(scorer, enroll_norm, test_norm, device):
+    """The ``(mean, std)`` pairs of a normalised histogram on the device, flat (``None`` twice for a side without one), or ``None`` without
+    either; one reduction checks every std."""
+    if enroll_norm is None and test_norm is None:
+        return None
+    stats = [(None, None) if pair is None else tuple(_to_device(v, scorer.dtype, device) for v in pair) for pair in (enroll_norm, test_norm)]
+    stds = torch.cat([std for _, std in stats if std is not None])
+    if not bool((torch.isfinite(stds) & (stds > 0)).all()):                         # one reduction, one scalar back
+        raise ValueError(f"{scorer.histograms}: every std of enroll_norm / test_norm must be finite and > 0")
+    return stats[0] + stats[1]
+
+
+def _hist_pass(scorer, group, e, t, le, lt, self_offset, lo, hi, device, stats=None):
+    """One ``scorer.hist`` call on resident operands (``scorer.hist_norm`` with the four statistics vectors ``stats``); ``group`` is what
+    follows ``D``.  The two ``HIST_BINS``-bin uint64 histograms over ``[lo, hi)``."""
+    ht = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
+    hn = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
+    head = (e, e.shape[0], t, t.shape[0], e.shape[1], *group, le, lt, -1 if self_offset is None else int(self_offset))
+    tail = (float(lo), float(hi), HIST_BINS, ht, hn)
+    if stats is None:
+        _lib.launch(scorer.hist, device, *head, *tail, exc=scorer.hist_exc)
+    else:
+        _lib.launch(scorer.hist_norm, device, *head, *stats, *tail, exc=scorer.hist_exc)
+    return ht.cpu().numpy().astype(numpy.uint64), hn.cpu().numpy().astype(numpy.uint64)
+
+
+def _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, lo, hi, device, norm_ptrs=None):
+    """``_hist_pass`` of PLDA operands, spelled out: the seam at which ``tests/test_plda_hist_cpu.py`` reads what reaches the device."""
+    return _hist_pass(PldaScorer, (phi, psi, cst, scaling_factor), e, t, le, lt, self_offset, lo, hi, device, norm_ptrs)
+
+
+def _histograms(scorer, e, t, le, lt, self_offset, lo, hi, bins, enroll_norm=None, test_norm=None):
+    """Prepared vectors, checked labels and ``bins``: labels and statistics pairs onto the device, then the passes."""
+    le, lt = _labels(le, e.device), _labels(lt, e.device)
+    stats = _stat_pairs(scorer, enroll_norm, test_norm, e.device)
+    return _histogram_passes(lambda a, b: scorer.hist_pass(e, t, le, lt, self_offset, a, b, stats), lo, hi, bins)
+
+
 def cosine_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, self_offset=None, lo=-1.0, hi=1.0, device=None, bins=None,
                       enroll_norm=None, test_norm=None):
     """Target / non-target score histograms of ALL (enrol, test) pairs without materialising the (Ne, Nt) score matrix
@@ -162,40 +208,16 @@ def cosine_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, 
             raise ValueError("x-vector dimensions must match and be a multiple of 4")
         enroll_norm = _norm_pair(enroll_norm, enroll_vectors.shape[0], "enroll")
         test_norm = _norm_pair(test_norm, test_vectors.shape[0], "test")
-    device = _device(device if device is not None else (enroll_vectors.device if torch.is_tensor(enroll_vectors) and enroll_vectors.is_cuda else None))
-    e, t = _to_device(enroll_vectors, torch.float32, device), _to_device(test_vectors, torch.float32, device)
+    scorer = CosineScorer(_hist_device(device, enroll_vectors))
+    e, t = scorer.vectors(enroll_vectors, test_vectors)
     if e.shape[1] % 4 or e.shape[1] != t.shape[1]:
         raise AssertionError("x-vector dimensions must match and be a multiple of 4")
-    le = torch.as_tensor(enroll_labels).to(device=device, dtype=torch.int32).contiguous()
-    lt = torch.as_tensor(test_labels).to(device=device, dtype=torch.int32).contiguous()
+    le, lt = _labels(enroll_labels, e.device), _labels(test_labels, e.device)
     assert le.shape == (e.shape[0],) and lt.shape == (t.shape[0],), "one label per vector"
-    bins = HIST_BINS if bins is None else int(bins)
-    inner = HIST_BINS - 2
-    if bins != HIST_BINS and (bins <= 0 or bins % inner):
-        raise AssertionError(f"bins must be {HIST_BINS} or a multiple of {inner}")
+    bins = _check_bins(bins, AssertionError)
     if not float(hi) > float(lo):
         raise AssertionError("histogram range: hi must exceed lo")
-    normalised = enroll_norm is not None or test_norm is not None
-    if normalised:
-        stats = [None if pair is None else tuple(_to_device(v, torch.float32, device) for v in pair) for pair in (enroll_norm, test_norm)]
-        stds = torch.cat([pair[1] for pair in stats if pair is not None])
-        if not bool((torch.isfinite(stds) & (stds > 0)).all()):                     # one reduction, one scalar back
-            raise ValueError("cosine_histograms: every std of enroll_norm / test_norm must be finite and > 0")
-        norm_ptrs = tuple(None if pair is None else v.data_ptr() for pair in stats for v in (pair if pair is not None else (None, None)))
-
-    def one_pass(a, b):
-        ht = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
-        hn = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
-        head = (e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], le.data_ptr(), lt.data_ptr(), -1 if self_offset is None else int(self_offset))
-        tail = (float(a), float(b), HIST_BINS, ht.data_ptr(), hn.data_ptr(), _stream(device))
-        with torch.cuda.device(device):
-            if normalised:
-                _lib.check(_lib.lib().sc_cosine_hist_norm(*head, *norm_ptrs, *tail), AssertionError)
-            else:
-                _lib.check(_lib.lib().sc_cosine_hist(*head, *tail), AssertionError)
-        return ht.cpu().numpy().astype(numpy.uint64), hn.cpu().numpy().astype(numpy.uint64)
-
-    return _histogram_passes(one_pass, lo, hi, bins)
+    return _histograms(scorer, e, t, le, lt, self_offset, lo, hi, bins, enroll_norm, test_norm)
 
 
 def _speaker_posterior_terms(K):
@@ -241,9 +263,8 @@ def full_plda_parameters(F, G, Sigma, scaling_factor=1.):
     return B, K2 - K1, 0.5 * (K2 + K2.T), constant
 
 
-def _plda_hist_operands(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor):
-    """The host half of ``plda_histograms`` / ``plda_range_from_sample``: every check that needs no device, then the D x D algebra.
-    Returns ``(mu, B, Phi, Psi, cst)``; ``B`` is ``None`` without a channel sub-space, else the projection both sides go through."""
+def _plda_checks(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G):
+    """Every check of a PLDA call that needs no device.  Returns the model as float64 arrays ``(mu, F, Sigma, G)``: what ``PldaScorer`` takes."""
     if len(enroll_vectors.shape) != 2 or len(test_vectors.shape) != 2 or enroll_vectors.shape[1] != test_vectors.shape[1]:
         raise ValueError("enrolment and test vectors are matrices of one width")
     if enroll_vectors.shape[0] == 0 or test_vectors.shape[0] == 0:
@@ -260,46 +281,83 @@ def _plda_hist_operands(enroll_vectors, test_vectors, enroll_labels, test_labels
     for name, v in (("mu", mu), ("F", F), ("Sigma", Sigma), ("G", G)):
         if v is not None and not numpy.isfinite(v).all():
             raise ValueError(f"{name} is not finite")
-    if G is None:
-        return (mu, None) + tuple(plda_parameters(mu, F, Sigma, scaling_factor))
-    return (mu,) + tuple(full_plda_parameters(F, G, Sigma, scaling_factor))
+    return mu, F, Sigma, G
 
 
-def _plda_hist_vectors(enroll_vectors, test_vectors, mu, B, device):
-    """Both sides on the device in float64, centred by ``mu`` and, with a channel sub-space, projected by ``B`` (the route of
-    ``full_PLDA_scoring``); one object for both sides when the caller passed one.  One reduction checks that they are finite."""
-    mu_d = torch.as_tensor(mu, device=device)
-    prep = lambda x: _to_device(x, torch.float64, device) - mu_d
-    e = prep(enroll_vectors)
-    t = e if test_vectors is enroll_vectors else prep(test_vectors)
-    if not bool(torch.isfinite(e).all() & torch.isfinite(t).all()):                  # one scalar back
-        raise ValueError("the centred vectors are not finite")
-    if B is not None:
-        from .backend import whiten_rows_device
-        R = numpy.ascontiguousarray(B.T)
-        pe = whiten_rows_device(e.contiguous(), None, R)
-        e, t = pe, (pe if t is e else whiten_rows_device(t.contiguous(), None, R))
-    return e.contiguous(), t.contiguous()
+# ---- scorers: how one kind of trial is scored on a device ---------------------------------------------------------------------------
+# A scorer holds the element type, the names of its entry points, the arguments that follow ``D`` in them (``group``), whether the two
+# sides of a trial share cohort statistics, and the preparation of raw vectors (``vectors``).  The histogram functions of this module and
+# every rule of ``score_normalization`` are written once, against a scorer.  There are two.  The element type and the names are class
+# attributes: a rule that needs nothing else (``_check_scores``, ``_apply``, ``_hist_pass``) takes the class as well as an instance.
+class CosineScorer:
+    """Cosine scores of float32 rows.  Nothing follows ``D`` but, in the cohort moments, ``col_shift`` / ``col_scale``."""
+    dtype = torch.float32
+    matrix, moments, topk, apply = "sc_cosine", "sc_cohort_moments", "sc_topk_stats", "sc_norm_apply"
+    hist, hist_norm, hist_exc, histograms = "sc_cosine_hist", "sc_cosine_hist_norm", AssertionError, "cosine_histograms"
+    shares_sides = True                                     # s(x, c) is s(c, x): one object on both sides needs its statistics once
+
+    def __init__(self, device, col_shift=None, col_scale=None):
+        self.device = device
+        self.columns = (None, None) if col_shift is None else (_to_device(col_shift, self.dtype, device), _to_device(col_scale, self.dtype, device))
+
+    def group(self, side="enrol", moments=False):
+        return self.columns if moments else ()
+
+    def vectors(self, enroll_vectors, test_vectors):
+        """Both sides on the device in float32, used as given; one object for both sides when the caller passed one."""
+        e = _to_device(enroll_vectors, self.dtype, self.device)
+        return e, (e if test_vectors is enroll_vectors else _to_device(test_vectors, self.dtype, self.device))
+
+    def hist_pass(self, e, t, le, lt, self_offset, lo, hi, stats):                       # PldaScorer's goes through a seam of its own
+        return _hist_pass(self, (), e, t, le, lt, self_offset, lo, hi, self.device, stats)
 
 
-def _hist_device(device, *tensors):
-    return _device(device if device is not None else next((x.device for x in tensors if torch.is_tensor(x) and x.is_cuda), None))
+class PldaScorer:
+    """PLDA log-likelihood ratios in float64.  ``(phi, psi, cst, scaling)`` follow ``D``, resident on the device and built once from the
+    host algebra of ``plda_parameters`` (``G is None``) or ``full_plda_parameters``; the ``"test"`` side of the cohort statistics scores
+    ``s(c, x)``, whose cross term is ``x' Psi' c``, so it gets ``Psi'`` (``Psi`` is symmetric only up to rounding)."""
+    dtype = torch.float64
+    matrix, moments, topk, apply = "sc_plda_fast", "sc_plda_cohort_moments", "sc_topk_stats_f64", "sc_norm_apply_f64"
+    hist, hist_norm, hist_exc, histograms = "sc_plda_hist", "sc_plda_hist_norm", ValueError, "plda_histograms"
+    shares_sides = False                                    # Psi on one side, Psi' on the other
 
-
-def _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, lo, hi, device, norm_ptrs=None):
-    """One ``sc_plda_hist`` call on resident operands (``sc_plda_hist_norm`` with the four statistics pointers ``norm_ptrs``): the two
-    ``HIST_BINS``-bin uint64 histograms over ``[lo, hi)``."""
-    ht = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
-    hn = torch.empty(HIST_BINS, dtype=torch.int64, device=device)
-    head = (e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], phi.data_ptr(), psi.data_ptr(), float(cst), float(scaling_factor),
-            le.data_ptr(), lt.data_ptr(), -1 if self_offset is None else int(self_offset))
-    tail = (float(lo), float(hi), HIST_BINS, ht.data_ptr(), hn.data_ptr(), _stream(device))
-    with torch.cuda.device(device):
-        if norm_ptrs is None:
-            _lib.check(_lib.lib().sc_plda_hist(*head, *tail))
+    def __init__(self, mu, F, Sigma, G, scaling_factor):
+        """The host algebra, once; ``on(device)`` makes it resident."""
+        if G is None:
+            self.B, (Phi, Psi, cst) = None, plda_parameters(mu, F, Sigma, scaling_factor)
         else:
-            _lib.check(_lib.lib().sc_plda_hist_norm(*head, *norm_ptrs, *tail))
-    return ht.cpu().numpy().astype(numpy.uint64), hn.cpu().numpy().astype(numpy.uint64)
+            self.B, Phi, Psi, cst = full_plda_parameters(F, G, Sigma, scaling_factor)
+        self.host = (mu, Phi, Psi)
+        self.cst, self.scaling = float(cst), float(scaling_factor)
+
+    def on(self, device):
+        mu, Phi, Psi = self.host
+        self.device, self.mu, self.psi_t = device, torch.as_tensor(mu, device=device), None
+        self.phi, self.psi = _to_device(Phi, self.dtype, device), _to_device(Psi, self.dtype, device)
+        return self
+
+    def group(self, side="enrol", moments=False):
+        if side == "test" and self.psi_t is None:
+            self.psi_t = _to_device(numpy.ascontiguousarray(self.host[2].T), self.dtype, self.device)
+        return self.phi, (self.psi_t if side == "test" else self.psi), self.cst, self.scaling
+
+    def hist_pass(self, e, t, le, lt, self_offset, lo, hi, stats):
+        return _plda_hist_pass(e, t, le, lt, *self.group(), self_offset, lo, hi, self.device, *(() if stats is None else (stats,)))
+
+    def vectors(self, enroll_vectors, test_vectors):
+        """Both sides on the device in float64, centred by ``mu`` and, with a channel sub-space, projected by ``B`` (the route of
+        ``full_PLDA_scoring``); one object for both sides when the caller passed one.  One reduction checks that they are finite."""
+        prep = lambda x: _to_device(x, self.dtype, self.device) - self.mu
+        e = prep(enroll_vectors)
+        t = e if test_vectors is enroll_vectors else prep(test_vectors)
+        if not bool(torch.isfinite(e).all() & torch.isfinite(t).all()):                  # one scalar back
+            raise ValueError("the centred vectors are not finite")
+        if self.B is not None:
+            from .backend import whiten_rows_device
+            R = numpy.ascontiguousarray(self.B.T)
+            pe = whiten_rows_device(e.contiguous(), None, R)
+            e, t = pe, (pe if t is e else whiten_rows_device(t.contiguous(), None, R))
+        return e.contiguous(), t.contiguous()
 
 
 def plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G=None, scaling_factor=1., self_offset=None, *,
@@ -335,54 +393,54 @@ def plda_norm_histograms(enroll_vectors, test_vectors, enroll_labels, test_label
                             device, enroll_norm, test_norm)
 
 
-def _plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor, self_offset, lo, hi, bins, device,
-                     enroll_norm, test_norm):
+def _plda_hist_checks(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, lo, hi, bins):
+    """The checks of ``plda_histograms`` that need no device.  Returns ``(model, enroll_labels, test_labels, bins)``: the model as
+    ``PldaScorer`` takes it, the labels as arrays or tensors, ``bins`` as an int."""
     if lo is None or hi is None:
         raise ValueError("plda_histograms: lo and hi are required (log-likelihood ratios have no natural range: plda_range_from_sample)")
     if not (numpy.isfinite(lo) and numpy.isfinite(hi) and float(hi) > float(lo)):
         raise ValueError("plda_histograms: lo and hi must be finite and hi must exceed lo")
-    bins = HIST_BINS if bins is None else int(bins)
-    if bins != HIST_BINS and (bins <= 0 or bins % (HIST_BINS - 2)):
-        raise ValueError(f"bins must be {HIST_BINS} or a multiple of {HIST_BINS - 2}")
+    bins = _check_bins(bins, ValueError)
     enroll_labels = enroll_labels if torch.is_tensor(enroll_labels) else numpy.asarray(enroll_labels)
     test_labels = test_labels if torch.is_tensor(test_labels) else numpy.asarray(test_labels)
-    mu, B, Phi, Psi, cst = _plda_hist_operands(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor)
+    return _plda_checks(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G), enroll_labels, test_labels, bins
+
+
+def _plda_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor, self_offset, lo, hi, bins, device,
+                     enroll_norm, test_norm):
+    model, enroll_labels, test_labels, bins = _plda_hist_checks(enroll_vectors, test_vectors, enroll_labels, test_labels, mu, F, Sigma, G, lo, hi, bins)
+    scorer = PldaScorer(*model, scaling_factor)
     enroll_norm = _norm_pair(enroll_norm, enroll_vectors.shape[0], "enroll")
     test_norm = _norm_pair(test_norm, test_vectors.shape[0], "test")
-    device = _hist_device(device, enroll_vectors, test_vectors)
-    e, t = _plda_hist_vectors(enroll_vectors, test_vectors, mu, B, device)
-    phi, psi = _to_device(Phi, torch.float64, device), _to_device(Psi, torch.float64, device)
-    le = torch.as_tensor(enroll_labels).to(device=device, dtype=torch.int32).contiguous()
-    lt = torch.as_tensor(test_labels).to(device=device, dtype=torch.int32).contiguous()
-    norm_ptrs = None
-    if enroll_norm is not None or test_norm is not None:
-        stats = [None if pair is None else tuple(_to_device(v, torch.float64, device) for v in pair) for pair in (enroll_norm, test_norm)]
-        stds = torch.cat([pair[1] for pair in stats if pair is not None])
-        if not bool((torch.isfinite(stds) & (stds > 0)).all()):                     # one reduction, one scalar back
-            raise ValueError("plda_histograms: every std of enroll_norm / test_norm must be finite and > 0")
-        norm_ptrs = tuple(None if pair is None else v.data_ptr() for pair in stats for v in (pair if pair is not None else (None, None)))
+    e, t = scorer.on(_hist_device(device, enroll_vectors, test_vectors)).vectors(enroll_vectors, test_vectors)
+    return _histograms(scorer, e, t, enroll_labels, test_labels, self_offset, lo, hi, bins, enroll_norm, test_norm)
 
-    extra = () if norm_ptrs is None else (norm_ptrs,)
-    one_pass = lambda a, b: _plda_hist_pass(e, t, le, lt, phi, psi, cst, scaling_factor, self_offset, a, b, device, *extra)
-    return _histogram_passes(one_pass, lo, hi, bins)
+
+def _range_from_sample(scorer, enroll_vectors, test_vectors, normalise=None):
+    """``(lo, hi)`` from a strided sample of at most 2 048 rows per side: its materialised score matrix, normalised in place by
+    ``normalise(z, enrol sample, test sample)`` if given, without the self-trials when the two sides are the same object; the smallest and
+    largest entry, each widened by a quarter of the sampled range (what still falls outside is counted in the end bins)."""
+    sample = lambda x: x[:: max(1, x.shape[0] // 2048)][:2048]
+    gather = lambda x: x.contiguous() if torch.is_tensor(x) else x                  # once: the sample is prepared for the matrix and for each side
+    es = gather(sample(enroll_vectors))
+    ts = es if test_vectors is enroll_vectors else gather(sample(test_vectors))
+    e, t = scorer.vectors(es, ts)
+    z = _matrix(scorer.matrix, e, t, scorer.group())
+    if normalise is not None:
+        normalise(z, es, ts)
+    if es is ts:
+        z = z[~torch.eye(z.shape[0], dtype=torch.bool, device=z.device)]            # a set against itself: the self-trials are not trials
+    zmin, zmax = float(z.min()), float(z.max())
+    pad = 0.25 * (zmax - zmin)
+    return zmin - pad, zmax + pad
 
 
 def plda_range_from_sample(enroll_vectors, test_vectors, mu, F, Sigma, G=None, scaling_factor=1., device=None):
     """``(lo, hi)`` for ``plda_histograms``, as ``score_normalization.normalised_range_from_sample`` finds it: a strided sample of at most
     2 048 rows per side, its score matrix from ``plda_matrix_device`` (without the self-trials when the two sides are the same object), and
     the sample's smallest and largest score, each widened by a quarter of the sampled range."""
-    mu, B, Phi, Psi, cst = _plda_hist_operands(enroll_vectors, test_vectors, None, None, mu, F, Sigma, G, scaling_factor)
-    device = _hist_device(device, enroll_vectors, test_vectors)
-    sample = lambda x: x[:: max(1, x.shape[0] // 2048)][:2048]
-    es = sample(enroll_vectors)
-    ts = es if test_vectors is enroll_vectors else sample(test_vectors)
-    e, t = _plda_hist_vectors(es, ts, mu, B, device)
-    z = plda_matrix_device(e, t, Phi, Psi, cst, scaling_factor, device)
-    if es is ts:
-        z = z[~torch.eye(z.shape[0], dtype=torch.bool, device=device)]               # a set against itself: the self-trials are not trials
-    zmin, zmax = float(z.min()), float(z.max())
-    pad = 0.25 * (zmax - zmin)
-    return zmin - pad, zmax + pad
+    model = _plda_checks(enroll_vectors, test_vectors, None, None, mu, F, Sigma, G)
+    return _range_from_sample(PldaScorer(*model, scaling_factor).on(_hist_device(device, enroll_vectors, test_vectors)), enroll_vectors, test_vectors)
 
 
 def _open_set(scoremat, p_known):

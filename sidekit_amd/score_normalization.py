@@ -25,42 +25,35 @@ every pair counted into target / non-target histograms (``iv_scoring.cosine_hist
 ``sc_cosine_hist_norm`` normalises each score between the GEMM's accumulator and its bin, in ``sc_norm_apply``'s expressions, so the counts
 are those of the materialised path).  ``normalised_range_from_sample`` proposes its ``lo`` / ``hi``.  zt-norm is not offered there: it is a
 t-norm against a z-normalised cohort, a different chain of expressions from the three ``sc_norm_apply`` has.
+
+Every rule of this module is written once, against a scorer (``iv_scoring.CosineScorer`` / ``iv_scoring.PldaScorer``: element type, entry
+points, the arguments that follow ``D``, whether the two sides share statistics); the public functions run their own checks and call it.
 """
 import copy
-import ctypes
 
 import numpy
 import torch
 
-from . import _lib
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+from . import _lib, iv_scoring
+from .iv_scoring import CosineScorer, PldaScorer, _to_device, normalize_rows_device
 
 
 def asnorm(enrol_xv, cohort_xv, ndx=None, topk=200, device=None):
     """Same arguments as the reference (``ndx`` is unused there too); returns the (N, N) float32 numpy matrix."""
     if not torch.cuda.is_available():
-        raise RuntimeError("sidekit_amd computes on the GPU only (no CPU fallback) and no GPU is visible")
+        raise RuntimeError(_NO_GPU)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    e = torch.as_tensor(enrol_xv, dtype=torch.float32).to(device).contiguous()
-    from .iv_scoring import normalize_rows_device
-    c = normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), device)     # F.normalize of the cohort, on the device
+    e = _to_device(enrol_xv, torch.float32, device)
+    c = _cohort_on(device, cohort_xv, True)                                               # F.normalize of the cohort, on the device
     n, d = e.shape
     if d % 4 or c.shape[1] != d:
         raise ValueError("x-vector dimension must match and be a multiple of 4")
-    lib = _lib.lib()
-    scores = torch.empty((n, n), dtype=torch.float32, device=device)
-    calib = torch.empty((n, c.shape[0]), dtype=torch.float32, device=device)
+    scores = iv_scoring._matrix(CosineScorer.matrix, e, e, exc=ValueError)
+    calib = iv_scoring._matrix(CosineScorer.matrix, e, c, exc=ValueError)
     mean = torch.empty(n, dtype=torch.float32, device=device)
     std = torch.empty(n, dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        st = _stream(device)
-        _lib.check(lib.sc_cosine(e.data_ptr(), n, e.data_ptr(), n, d, scores.data_ptr(), st))
-        _lib.check(lib.sc_cosine(e.data_ptr(), n, c.data_ptr(), c.shape[0], d, calib.data_ptr(), st))
-        _lib.check(lib.sc_topk_stats(calib.data_ptr(), n, c.shape[0], int(topk), mean.data_ptr(), std.data_ptr(), st))
-        _lib.check(lib.sc_snorm_apply(scores.data_ptr(), n, n, mean.data_ptr(), std.data_ptr(), mean.data_ptr(), std.data_ptr(), st))
+    _lib.launch(CosineScorer.topk, device, calib, n, c.shape[0], int(topk), mean, std)
+    _lib.launch("sc_snorm_apply", device, scores, n, n, mean, std, mean, std)
     return scores.cpu().numpy()
 
 
@@ -85,6 +78,27 @@ def _check_xv(xv, cohort_xv, what="x-vectors"):
     return n, m, d
 
 
+def _check_topk(topk, m):
+    if not 1 < int(topk) <= m:
+        raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={m})")
+
+
+def _check_kind(kind, topk, m):
+    if kind not in ("z", "t", "s"):
+        raise ValueError(f"kind is 'z', 't' or 's' (zt-norm has no histogram form), got {kind!r}")
+    if topk is not None:
+        if kind != "s":
+            raise ValueError("topk (adaptive statistics) goes with kind='s' only")
+        _check_topk(topk, m)
+
+
+def _check_scores(scorer, scores, ne, nt):
+    if not (torch.is_tensor(scores) and scores.is_cuda and scores.dtype == scorer.dtype and scores.is_contiguous()):
+        raise ValueError(f"scores must be a contiguous {str(scorer.dtype).split('.')[1]} device tensor (it is normalised in place)")
+    if scores.dim() != 2 or (ne is not None and scores.shape[0] != ne) or (nt is not None and scores.shape[1] != nt):
+        raise ValueError(f"scores have shape {tuple(scores.shape)}, the x-vectors say ({ne if ne is not None else 'any'}, {nt if nt is not None else 'any'})")
+
+
 def _device_of(*xs):
     if not torch.cuda.is_available():
         raise RuntimeError(_NO_GPU)
@@ -94,14 +108,62 @@ def _device_of(*xs):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _f32(x, device):
-    return torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
+def _cohort_on(device, cohort_xv, normalize):
+    if normalize:
+        return normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), device)
+    return _to_device(cohort_xv, torch.float32, device)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+# ---- the rules, once: each takes a scorer and operands that passed the caller's checks ----------------------------------------------
+def _cohort_stats(scorer, x, c, side="enrol", topk=None, self_offset=None, max_workspace_bytes=1 << 30):
+    """``(mean, std)`` per row of ``x`` against the cohort ``c`` (both prepared by ``scorer.vectors``).  ``topk=None``: the moments of the
+    whole cohort, the scores never stored; else the top-k statistics over row blocks whose (rows, M) score buffer fits in
+    ``max_workspace_bytes``.  ``side="test"`` scores ``s(c, x)``."""
+    (n, d), m = x.shape, c.shape[0]
+    mean = torch.empty(n, dtype=scorer.dtype, device=x.device)
+    std = torch.empty(n, dtype=scorer.dtype, device=x.device)
+    if topk is None:
+        _lib.launch(scorer.moments, x.device, x, n, c, m, d, *scorer.group(side, moments=True), -1 if self_offset is None else int(self_offset),
+                    mean, std)
+    elif n:
+        rows = max(1, min(n, int(max_workspace_bytes) // (mean.element_size() * m)))
+        calib = torch.empty((rows, m), dtype=scorer.dtype, device=x.device)
+        for r0 in range(0, n, rows):
+            nr = min(rows, n - r0)
+            _lib.launch(scorer.matrix, x.device, x[r0:], nr, c, m, d, *scorer.group(side), calib)
+            _lib.launch(scorer.topk, x.device, calib, nr, m, int(topk), mean[r0:], std[r0:])
+    return mean, std
 
 
+def _side_stats(scorer, kind, enroll_xv, test_xv, cohort_xv, topk=None, max_workspace_bytes=1 << 30):
+    """(enrolment pair, test pair) of ``kind``: the side a kind does not use is ``None``.  The cohort is prepared once; ``test_xv is
+    enroll_xv`` prepares the vectors once and, where the scorer's two sides score alike, computes the statistics once."""
+    e, c = scorer.vectors(enroll_xv, cohort_xv)
+    en = _cohort_stats(scorer, e, c, "enrol", topk, None, max_workspace_bytes) if kind in ("z", "s") else None
+    if kind == "z":
+        return en, None
+    if kind == "s" and test_xv is enroll_xv and scorer.shares_sides:
+        return en, en
+    t = e if test_xv is enroll_xv else scorer.vectors(test_xv, test_xv)[0]
+    return en, _cohort_stats(scorer, t, c, "test", topk, None, max_workspace_bytes)
+
+
+def _apply(scorer, scores, enrol=None, test=None):
+    """``scorer.apply`` in place: ``enrol`` / ``test`` are (mean, std) pairs or None."""
+    _lib.launch(scorer.apply, scores.device, scores, scores.shape[0], scores.shape[1], *(enrol or (None, None)), *(test or (None, None)))
+    return scores
+
+
+def _norm_device(scorer, kind, scores, enroll_xv, test_xv, cohort_xv, topk=None, max_workspace_bytes=1 << 30):
+    """z-, t- or s-norm of a resident score matrix, in place; z and t prepare and use their own side only."""
+    if kind == "z":
+        return _apply(scorer, scores, enrol=_cohort_stats(scorer, *scorer.vectors(enroll_xv, cohort_xv), "enrol"))
+    if kind == "t":
+        return _apply(scorer, scores, test=_cohort_stats(scorer, *scorer.vectors(test_xv, cohort_xv), "test"))
+    return _apply(scorer, scores, *_side_stats(scorer, "s", enroll_xv, test_xv, cohort_xv, topk, max_workspace_bytes))
+
+
+# ---- cosine scores ---------------------------------------------------------------------------------------------------------------
 def cohort_stats_device(xv, cohort_xv, topk=None, self_offset=None, col_shift=None, col_scale=None, max_workspace_bytes=1 << 30,
                         normalize=False):
     """Per row of ``xv`` (N, D): ``(mean, std)`` of its cosine scores against the cohort (M, D), float32 **device tensors**; rows are used
@@ -118,80 +180,43 @@ def cohort_stats_device(xv, cohort_xv, topk=None, self_offset=None, col_shift=No
     if topk is not None:
         if self_offset is not None or col_shift is not None:
             raise ValueError("self_offset / col_shift / col_scale apply to whole-cohort statistics (topk=None) only")
-        if not 1 < int(topk) <= m:
-            raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={m})")
+        _check_topk(topk, m)
     if col_shift is not None and (tuple(col_shift.shape) != (m,) or tuple(col_scale.shape) != (m,)):
         raise ValueError(f"col_shift and col_scale must have one entry per cohort row ({m})")
     device = _device_of(xv, cohort_xv)
-    x = _f32(xv, device)
-    if normalize:
-        from .iv_scoring import normalize_rows_device
-        c = normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), device)
-    else:
-        c = _f32(cohort_xv, device)
-    mean = torch.empty(n, dtype=torch.float32, device=device)
-    std = torch.empty(n, dtype=torch.float32, device=device)
-    lib = _lib.lib()
-    with torch.cuda.device(device):
-        st = _stream(device)
-        if topk is None:
-            shift = None if col_shift is None else _f32(col_shift, device)
-            scale = None if col_scale is None else _f32(col_scale, device)
-            _lib.check(lib.sc_cohort_moments(x.data_ptr(), n, c.data_ptr(), m, d, _ptr(shift), _ptr(scale),
-                                             -1 if self_offset is None else int(self_offset), mean.data_ptr(), std.data_ptr(), st))
-        elif n:
-            rows = max(1, min(n, int(max_workspace_bytes) // (4 * m)))
-            calib = torch.empty((rows, m), dtype=torch.float32, device=device)
-            for r0 in range(0, n, rows):
-                nr = min(rows, n - r0)
-                _lib.check(lib.sc_cosine(x[r0:].data_ptr(), nr, c.data_ptr(), m, d, calib.data_ptr(), st))
-                _lib.check(lib.sc_topk_stats(calib.data_ptr(), nr, m, int(topk), mean[r0:].data_ptr(), std[r0:].data_ptr(), st))
-    return mean, std
-
-
-def _check_scores(scores, ne, nt):
-    if not (torch.is_tensor(scores) and scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous()):
-        raise ValueError("scores must be a contiguous float32 device tensor (it is normalised in place)")
-    if scores.dim() != 2 or (ne is not None and scores.shape[0] != ne) or (nt is not None and scores.shape[1] != nt):
-        raise ValueError(f"scores have shape {tuple(scores.shape)}, the x-vectors say ({ne if ne is not None else 'any'}, {nt if nt is not None else 'any'})")
-
-
-def _apply(scores, enrol=None, test=None):
-    """``sc_norm_apply`` in place: ``enrol`` / ``test`` are (mean, std) pairs or None."""
-    me, se = enrol if enrol is not None else (None, None)
-    mt, sd = test if test is not None else (None, None)
-    with torch.cuda.device(scores.device):
-        _lib.check(_lib.lib().sc_norm_apply(scores.data_ptr(), scores.shape[0], scores.shape[1], _ptr(me), _ptr(se), _ptr(mt), _ptr(sd),
-                                            _stream(scores.device)))
-    return scores
+    x = _to_device(xv, torch.float32, device)
+    return _cohort_stats(CosineScorer(device, col_shift, col_scale), x, _cohort_on(device, cohort_xv, normalize), "enrol", topk, self_offset,
+                         max_workspace_bytes)
 
 
 def znorm_device(scores, enroll_xv, cohort_xv, normalize=False):
     """z-norm of a device (Ne, Nt) float32 score tensor, in place: ``(s_ij - m_i) / sd_i`` with the statistics of enrolment i's cohort scores."""
     _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
-    _check_scores(scores, enroll_xv.shape[0], None)
-    return _apply(scores, enrol=cohort_stats_device(enroll_xv, cohort_xv, normalize=normalize))
+    _check_scores(CosineScorer, scores, enroll_xv.shape[0], None)
+    device = _device_of(enroll_xv, cohort_xv)
+    return _norm_device(CosineScorer(device), "z", scores, enroll_xv, None, _cohort_on(device, cohort_xv, normalize))
 
 
 def tnorm_device(scores, test_xv, cohort_xv, normalize=False):
     """t-norm, in place: ``(s_ij - m_j) / sd_j`` with the statistics of test segment j's cohort scores."""
     _check_xv(test_xv, cohort_xv, "test x-vectors")
-    _check_scores(scores, None, test_xv.shape[0])
-    return _apply(scores, test=cohort_stats_device(test_xv, cohort_xv, normalize=normalize))
+    _check_scores(CosineScorer, scores, None, test_xv.shape[0])
+    device = _device_of(test_xv, cohort_xv)
+    return _norm_device(CosineScorer(device), "t", scores, None, test_xv, _cohort_on(device, cohort_xv, normalize))
 
 
 def snorm_device(scores, enroll_xv, test_xv, cohort_xv, topk=None, normalize=False, max_workspace_bytes=1 << 30):
     """s-norm, in place: ``0.5 ((s - m_i)/sd_i + (s - m_j)/sd_j)``; ``topk=k`` makes it adaptive (statistics of each side's k best
     cohort scores, unbiased std, as ``asnorm``).  ``test_xv is enroll_xv`` computes the statistics once."""
-    _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
+    _, m, _ = _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
     _check_xv(test_xv, cohort_xv, "test x-vectors")
-    _check_scores(scores, enroll_xv.shape[0], test_xv.shape[0])
+    _check_scores(CosineScorer, scores, enroll_xv.shape[0], test_xv.shape[0])
     if normalize:
-        from .iv_scoring import normalize_rows_device
-        cohort_xv = normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), scores.device)
-    e = cohort_stats_device(enroll_xv, cohort_xv, topk=topk, max_workspace_bytes=max_workspace_bytes)
-    t = e if test_xv is enroll_xv else cohort_stats_device(test_xv, cohort_xv, topk=topk, max_workspace_bytes=max_workspace_bytes)
-    return _apply(scores, enrol=e, test=t)
+        cohort_xv = _cohort_on(scores.device, cohort_xv, True)
+    if topk is not None:
+        _check_topk(topk, m)
+    scorer = CosineScorer(_device_of(enroll_xv, test_xv, cohort_xv))
+    return _norm_device(scorer, "s", scores, enroll_xv, test_xv, cohort_xv, topk, max_workspace_bytes)
 
 
 def ztnorm_device(scores, enroll_xv, test_xv, cohort_xv, normalize=False):
@@ -199,58 +224,23 @@ def ztnorm_device(scores, enroll_xv, test_xv, cohort_xv, normalize=False):
     neither the cohort x cohort nor the cohort x test matrix is formed."""
     _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
     _check_xv(test_xv, cohort_xv, "test x-vectors")
-    _check_scores(scores, enroll_xv.shape[0], test_xv.shape[0])
-    if normalize:
-        from .iv_scoring import normalize_rows_device
-        cohort_xv = normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), scores.device)
-    cohort = _f32(cohort_xv, scores.device)
+    _check_scores(CosineScorer, scores, enroll_xv.shape[0], test_xv.shape[0])
+    cohort = _cohort_on(scores.device, cohort_xv, normalize)
     m_c, sd_c = cohort_stats_device(cohort, cohort, self_offset=0)                         # znorm(imp_test, imp_imp, sym=True): per cohort model
     test = cohort_stats_device(test_xv, cohort, col_shift=m_c, col_scale=1.0 / sd_c)       # tnorm's statistics of the z-normalised imp_test
-    _apply(scores, enrol=cohort_stats_device(enroll_xv, cohort))                           # znorm(enrol_test, enrol_imp)
-    return _apply(scores, test=test)
+    _apply(CosineScorer, scores, enrol=cohort_stats_device(enroll_xv, cohort))             # znorm(enrol_test, enrol_imp)
+    return _apply(CosineScorer, scores, test=test)
 
 
 def asnorm_trials(enroll_xv, test_xv, cohort_xv, topk=200, normalize=True, max_workspace_bytes=1 << 30):
     """Adaptive s-norm of an enrolment x test trial set: the (Ne, Nt) normalised cosine matrix as a float32 **device tensor**.  With
     ``test_xv is enroll_xv`` this is ``asnorm``."""
-    _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
+    _, m, _ = _check_xv(enroll_xv, cohort_xv, "enrolment x-vectors")
     _check_xv(test_xv, cohort_xv, "test x-vectors")
-    if not 1 < int(topk) <= cohort_xv.shape[0]:
-        raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={cohort_xv.shape[0]})")
-    device = _device_of(enroll_xv, test_xv, cohort_xv)
-    e = _f32(enroll_xv, device)
-    t = e if test_xv is enroll_xv else _f32(test_xv, device)
-    scores = torch.empty((e.shape[0], t.shape[0]), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().sc_cosine(e.data_ptr(), e.shape[0], t.data_ptr(), t.shape[0], e.shape[1], scores.data_ptr(), _stream(device)))
+    _check_topk(topk, m)
+    e, t = CosineScorer(_device_of(enroll_xv, test_xv, cohort_xv)).vectors(enroll_xv, test_xv)
+    scores = iv_scoring._matrix(CosineScorer.matrix, e, t, exc=ValueError)
     return snorm_device(scores, e, t, cohort_xv, topk=topk, normalize=normalize, max_workspace_bytes=max_workspace_bytes)
-
-
-def _check_kind(kind, topk, m):
-    if kind not in ("z", "t", "s"):
-        raise ValueError(f"kind is 'z', 't' or 's' (zt-norm has no histogram form), got {kind!r}")
-    if topk is not None:
-        if kind != "s":
-            raise ValueError("topk (adaptive statistics) goes with kind='s' only")
-        if not 1 < int(topk) <= m:
-            raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={m})")
-
-
-def _side_stats(kind, enroll_xv, test_xv, cohort, topk, max_workspace_bytes):
-    """(enrolment pair, test pair) of ``kind``: the side a kind does not use is ``None``; ``test_xv is enroll_xv`` computes once."""
-    e = cohort_stats_device(enroll_xv, cohort, topk=topk, max_workspace_bytes=max_workspace_bytes) if kind in ("z", "s") else None
-    if kind == "z":
-        return e, None
-    if kind == "s" and test_xv is enroll_xv:
-        return e, e
-    return e, cohort_stats_device(test_xv, cohort, topk=topk, max_workspace_bytes=max_workspace_bytes)
-
-
-def _cohort_on(device, cohort_xv, normalize):
-    if normalize:
-        from .iv_scoring import normalize_rows_device
-        return normalize_rows_device(torch.as_tensor(cohort_xv, dtype=torch.float32), device)
-    return _f32(cohort_xv, device)
 
 
 def normalised_histograms(enroll_xv, test_xv, enroll_labels, test_labels, cohort_xv, kind="s", topk=None, normalize=False, self_offset=None, *,
@@ -268,13 +258,12 @@ def normalised_histograms(enroll_xv, test_xv, enroll_labels, test_labels, cohort
         raise ValueError("lo and hi are required keywords: normalised scores have no default range (normalised_range_from_sample estimates one)")
     if not float(hi) > float(lo):
         raise ValueError("histogram range: hi must exceed lo")
-    from .iv_scoring import cosine_histograms
     device = _device_of(enroll_xv, test_xv, cohort_xv)
-    e = _f32(enroll_xv, device)
-    t = e if test_xv is enroll_xv else _f32(test_xv, device)
-    en, tn = _side_stats(kind, e, t, _cohort_on(device, cohort_xv, normalize), topk, max_workspace_bytes)
-    return cosine_histograms(e, t, enroll_labels, test_labels, self_offset=self_offset, lo=lo, hi=hi, device=device, bins=bins,
-                             enroll_norm=en, test_norm=tn)
+    scorer = CosineScorer(device)
+    e, t = scorer.vectors(enroll_xv, test_xv)
+    en, tn = _side_stats(scorer, kind, e, t, _cohort_on(device, cohort_xv, normalize), topk, max_workspace_bytes)
+    return iv_scoring.cosine_histograms(e, t, enroll_labels, test_labels, self_offset=self_offset, lo=lo, hi=hi, device=device, bins=bins,
+                                        enroll_norm=en, test_norm=tn)
 
 
 def normalised_range_from_sample(enroll_xv, test_xv, cohort_xv, kind="s", topk=None, normalize=False):
@@ -285,70 +274,26 @@ def normalised_range_from_sample(enroll_xv, test_xv, cohort_xv, kind="s", topk=N
     _check_xv(test_xv, cohort_xv, "test x-vectors")
     _check_kind(kind, topk, m)
     device = _device_of(enroll_xv, test_xv, cohort_xv)
-    e = _f32(enroll_xv, device)
-    t = e if test_xv is enroll_xv else _f32(test_xv, device)
-    es = e[:: max(1, e.shape[0] // 2048)][:2048].contiguous()
-    ts = es if t is e else t[:: max(1, t.shape[0] // 2048)][:2048].contiguous()
+    scorer = CosineScorer(device)
+    e, t = scorer.vectors(enroll_xv, test_xv)
     cohort = _cohort_on(device, cohort_xv, normalize)
-    from .iv_scoring import cosine_matrix_device
-    z = cosine_matrix_device(es, ts, device)
-    if kind == "z":
-        znorm_device(z, es, cohort)
-    elif kind == "t":
-        tnorm_device(z, ts, cohort)
-    else:
-        snorm_device(z, es, ts, cohort, topk=topk)
-    if es is ts:
-        z = z[~torch.eye(z.shape[0], dtype=torch.bool, device=device)]               # a set against itself: the self-trials are not trials
-    zmin, zmax = float(z.min()), float(z.max())
-    pad = 0.25 * (zmax - zmin)
-    return zmin - pad, zmax + pad
+    return iv_scoring._range_from_sample(scorer, e, t, lambda z, es, ts: _norm_device(scorer, kind, z, es, ts, cohort, topk))
 
 
 # ---- PLDA log-likelihood ratios: the same normalisations in float64 -----------------------------------------------------------------
-def _plda_model(xv, cohort_xv, mu, F, Sigma, G, scaling_factor, what="x-vectors"):
-    """The host half (``iv_scoring._plda_hist_operands``: every check that needs no device, then the D x D algebra) for ``xv`` against the
-    cohort: ``(mu, B, Phi, Psi, cst)``."""
-    from .iv_scoring import _plda_hist_operands
+def _plda_model(xv, cohort_xv, mu, F, Sigma, G, what="x-vectors"):
+    """Every check of ``xv`` against the cohort that needs no device (``iv_scoring._plda_checks``); the model ``PldaScorer`` takes."""
     _shape2(xv, what), _shape2(cohort_xv, "cohort")
     if cohort_xv.shape[0] == 0:
         raise ValueError("the cohort is empty")
-    return _plda_hist_operands(xv, cohort_xv, None, None, mu, F, Sigma, G, scaling_factor)
+    return iv_scoring._plda_checks(xv, cohort_xv, None, None, mu, F, Sigma, G)
 
 
 def _check_plda_topk(topk, self_offset, m):
     if topk is not None:
         if self_offset is not None:
             raise ValueError("self_offset applies to whole-cohort statistics (topk=None) only")
-        if not 1 < int(topk) <= m:
-            raise ValueError(f"need 1 < topk <= cohort size (topk={topk}, cohort={m})")
-
-
-def _plda_stats_prepared(x, c, Phi, Psi, cst, scaling_factor, side, topk, self_offset, max_workspace_bytes):
-    """``plda_cohort_stats_device`` on operands that are centred (and projected), float64, contiguous and on the device."""
-    from .iv_scoring import _to_device
-    device = x.device
-    n, d = x.shape
-    m = c.shape[0]
-    phi = _to_device(Phi, torch.float64, device)
-    psi = _to_device(numpy.ascontiguousarray(Psi.T) if side == "test" else Psi, torch.float64, device)
-    mean = torch.empty(n, dtype=torch.float64, device=device)
-    std = torch.empty(n, dtype=torch.float64, device=device)
-    lib = _lib.lib()
-    with torch.cuda.device(device):
-        st = _stream(device)
-        if topk is None:
-            _lib.check(lib.sc_plda_cohort_moments(x.data_ptr(), n, c.data_ptr(), m, d, phi.data_ptr(), psi.data_ptr(), float(cst), float(scaling_factor),
-                                                  -1 if self_offset is None else int(self_offset), mean.data_ptr(), std.data_ptr(), st))
-        elif n:
-            rows = max(1, min(n, int(max_workspace_bytes) // (8 * m)))
-            calib = torch.empty((rows, m), dtype=torch.float64, device=device)
-            for r0 in range(0, n, rows):
-                nr = min(rows, n - r0)
-                _lib.check(lib.sc_plda_fast(x[r0:].data_ptr(), nr, c.data_ptr(), m, d, phi.data_ptr(), psi.data_ptr(), float(cst), float(scaling_factor),
-                                            calib.data_ptr(), st))
-                _lib.check(lib.sc_topk_stats_f64(calib.data_ptr(), nr, m, int(topk), mean[r0:].data_ptr(), std[r0:].data_ptr(), st))
-    return mean, std
+        _check_topk(topk, m)
 
 
 def plda_cohort_stats_device(xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1., side="enrol", topk=None, self_offset=None,
@@ -363,76 +308,46 @@ def plda_cohort_stats_device(xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor
     (``sc_plda_fast`` + ``sc_topk_stats_f64`` over row blocks whose (rows, M) float64 buffer fits in ``max_workspace_bytes``)."""
     if side not in ("enrol", "test"):
         raise ValueError(f"side is 'enrol' or 'test', got {side!r}")
-    mu, B, Phi, Psi, cst = _plda_model(xv, cohort_xv, mu, F, Sigma, G, scaling_factor)
+    model = _plda_model(xv, cohort_xv, mu, F, Sigma, G)
     _check_plda_topk(topk, self_offset, cohort_xv.shape[0])
-    from .iv_scoring import _plda_hist_vectors
-    device = _device_of(xv, cohort_xv)
-    x, c = _plda_hist_vectors(xv, cohort_xv, mu, B, device)
-    return _plda_stats_prepared(x, c, Phi, Psi, cst, scaling_factor, side, topk, self_offset, max_workspace_bytes)
-
-
-def _check_scores_f64(scores, ne, nt):
-    if not (torch.is_tensor(scores) and scores.is_cuda and scores.dtype == torch.float64 and scores.is_contiguous()):
-        raise ValueError("scores must be a contiguous float64 device tensor (it is normalised in place)")
-    if scores.dim() != 2 or (ne is not None and scores.shape[0] != ne) or (nt is not None and scores.shape[1] != nt):
-        raise ValueError(f"scores have shape {tuple(scores.shape)}, the x-vectors say ({ne if ne is not None else 'any'}, {nt if nt is not None else 'any'})")
-
-
-def _apply_f64(scores, enrol=None, test=None):
-    """``sc_norm_apply_f64`` in place: ``enrol`` / ``test`` are (mean, std) pairs or None."""
-    me, se = enrol if enrol is not None else (None, None)
-    mt, sd = test if test is not None else (None, None)
-    with torch.cuda.device(scores.device):
-        _lib.check(_lib.lib().sc_norm_apply_f64(scores.data_ptr(), scores.shape[0], scores.shape[1], _ptr(me), _ptr(se), _ptr(mt), _ptr(sd),
-                                                _stream(scores.device)))
-    return scores
+    scorer = PldaScorer(*model, scaling_factor).on(_device_of(xv, cohort_xv))
+    return _cohort_stats(scorer, *scorer.vectors(xv, cohort_xv), side, topk, self_offset, max_workspace_bytes)
 
 
 def plda_znorm_device(scores, enroll_xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1.):
     """z-norm of a device (Ne, Nt) float64 PLDA score tensor (``iv_scoring.plda_matrix_device``'s), in place: ``(s_ij - m_i) / sd_i`` with
     the statistics of enrolment i's cohort scores ``s(e_i, c)``."""
-    _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "enrolment x-vectors")
-    _check_scores_f64(scores, enroll_xv.shape[0], None)
-    return _apply_f64(scores, enrol=plda_cohort_stats_device(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, side="enrol"))
+    model = _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, "enrolment x-vectors")
+    _check_scores(PldaScorer, scores, enroll_xv.shape[0], None)
+    scorer = PldaScorer(*model, scaling_factor).on(_device_of(enroll_xv, cohort_xv))
+    return _norm_device(scorer, "z", scores, enroll_xv, None, cohort_xv)
 
 
 def plda_tnorm_device(scores, test_xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1.):
     """t-norm, in place: ``(s_ij - m_j) / sd_j`` with the statistics of the cohort's scores ``s(c, t_j)`` on test segment j."""
-    _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "test x-vectors")
-    _check_scores_f64(scores, None, test_xv.shape[0])
-    return _apply_f64(scores, test=plda_cohort_stats_device(test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, side="test"))
+    model = _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, "test x-vectors")
+    _check_scores(PldaScorer, scores, None, test_xv.shape[0])
+    scorer = PldaScorer(*model, scaling_factor).on(_device_of(test_xv, cohort_xv))
+    return _norm_device(scorer, "t", scores, None, test_xv, cohort_xv)
 
 
 def plda_snorm_device(scores, enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1., topk=None, max_workspace_bytes=1 << 30):
     """s-norm, in place: ``0.5 ((s - m_i)/sd_i + (s - m_j)/sd_j)``; ``topk=k`` makes it adaptive (each side's k best cohort scores, unbiased
     std).  ``test_xv is enroll_xv`` does NOT share statistics: the enrolment side's cohort scores are ``s(e, c)``, the test side's
     ``s(c, t)``, which differ by ``Psi`` against ``Psi'`` (equal only up to rounding); both are computed."""
-    _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "enrolment x-vectors")
-    _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "test x-vectors")
+    model = _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, "enrolment x-vectors")
+    _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, "test x-vectors")
     _check_plda_topk(topk, None, cohort_xv.shape[0])
-    _check_scores_f64(scores, enroll_xv.shape[0], test_xv.shape[0])
-    e, t = _plda_side_stats("s", enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, topk, max_workspace_bytes)
-    return _apply_f64(scores, enrol=e, test=t)
+    _check_scores(PldaScorer, scores, enroll_xv.shape[0], test_xv.shape[0])
+    scorer = PldaScorer(*model, scaling_factor).on(_device_of(enroll_xv, test_xv, cohort_xv))
+    return _norm_device(scorer, "s", scores, enroll_xv, test_xv, cohort_xv, topk, max_workspace_bytes)
 
 
-def _plda_side_stats(kind, enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, topk, max_workspace_bytes):
-    """(enrolment pair, test pair) of ``kind``; the side a kind does not use is ``None``.  The cohort is centred (and projected) once."""
-    from .iv_scoring import _plda_hist_vectors
-    mu, B, Phi, Psi, cst = _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor)
-    device = _device_of(enroll_xv, test_xv, cohort_xv)
-    e, c = _plda_hist_vectors(enroll_xv, cohort_xv, mu, B, device)
-    stats = lambda x, side: _plda_stats_prepared(x, c, Phi, Psi, cst, scaling_factor, side, topk, None, max_workspace_bytes)
-    en = stats(e, "enrol") if kind in ("z", "s") else None
-    if kind == "z":
-        return en, None
-    t = e if test_xv is enroll_xv else _plda_hist_vectors(test_xv, test_xv, mu, B, device)[0]
-    return en, stats(t, "test")
-
-
-def _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, kind, topk):
-    _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "enrolment x-vectors")
-    _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, "test x-vectors")
+def _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, kind, topk):
+    model = _plda_model(enroll_xv, cohort_xv, mu, F, Sigma, G, "enrolment x-vectors")
+    _plda_model(test_xv, cohort_xv, mu, F, Sigma, G, "test x-vectors")
     _check_kind(kind, topk, cohort_xv.shape[0])
+    return model
 
 
 def plda_normalised_histograms(enroll_xv, test_xv, enroll_labels, test_labels, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1., kind="s",
@@ -444,15 +359,16 @@ def plda_normalised_histograms(enroll_xv, test_xv, enroll_labels, test_labels, c
     ``iv_scoring.plda_histograms``; ``iv_scoring.plda_norm_histograms`` does the counting with the statistics of ``plda_cohort_stats_device`` (``sc_plda_hist_norm``: the
     counts are those of the materialised path).  ``self_offset`` (of the TRIALS: the cohort is a set of its own), ``bins`` and the labels are
     ``plda_histograms``'.  ``lo`` / ``hi`` are required keywords (``plda_normalised_range_from_sample`` estimates them).  zt-norm is not offered."""
-    _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, kind, topk)
+    model = _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, kind, topk)
     if lo is None or hi is None:
         raise ValueError("lo and hi are required keywords: normalised scores have no default range (plda_normalised_range_from_sample estimates one)")
     if not float(hi) > float(lo):
         raise ValueError("histogram range: hi must exceed lo")
-    from .iv_scoring import plda_norm_histograms
-    en, tn = _plda_side_stats(kind, enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, topk, max_workspace_bytes)
-    return plda_norm_histograms(enroll_xv, test_xv, enroll_labels, test_labels, mu, F, Sigma, G, scaling_factor, self_offset, lo=lo, hi=hi, bins=bins,
-                                enroll_norm=en, test_norm=tn)
+    scorer = PldaScorer(*model, scaling_factor).on(_device_of(enroll_xv, test_xv, cohort_xv))
+    en, tn = _side_stats(scorer, kind, enroll_xv, test_xv, cohort_xv, topk, max_workspace_bytes)
+    _, le, lt, bins = iv_scoring._plda_hist_checks(enroll_xv, test_xv, enroll_labels, test_labels, mu, F, Sigma, G, lo, hi, bins)   # plda_norm_histograms' own
+    e, t = scorer.vectors(enroll_xv, test_xv)
+    return iv_scoring._histograms(scorer, e, t, le, lt, self_offset, lo, hi, bins, en, tn)
 
 
 def plda_normalised_range_from_sample(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G=None, scaling_factor=1., kind="s", topk=None):
@@ -460,26 +376,9 @@ def plda_normalised_range_from_sample(enroll_xv, test_xv, cohort_xv, mu, F, Sigm
     per side, its materialised PLDA score matrix normalised by ``plda_znorm_device`` / ``plda_tnorm_device`` / ``plda_snorm_device`` against
     the whole cohort (without the self-trials when the two sides are the same object), and the sample's smallest and largest normalised
     score, each widened by a quarter of the sampled range."""
-    _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, scaling_factor, kind, topk)
-    from .iv_scoring import _plda_hist_vectors, plda_matrix_device
-    device = _device_of(enroll_xv, test_xv, cohort_xv)
-    sample = lambda x: x[:: max(1, x.shape[0] // 2048)][:2048]
-    es = sample(enroll_xv)
-    ts = es if test_xv is enroll_xv else sample(test_xv)
-    pmu, B, Phi, Psi, cst = _plda_model(es, cohort_xv, mu, F, Sigma, G, scaling_factor)
-    e, t = _plda_hist_vectors(es, ts, pmu, B, device)
-    z = plda_matrix_device(e, t, Phi, Psi, cst, scaling_factor, device)
-    if kind == "z":
-        plda_znorm_device(z, es, cohort_xv, mu, F, Sigma, G, scaling_factor)
-    elif kind == "t":
-        plda_tnorm_device(z, ts, cohort_xv, mu, F, Sigma, G, scaling_factor)
-    else:
-        plda_snorm_device(z, es, ts, cohort_xv, mu, F, Sigma, G, scaling_factor, topk=topk)
-    if es is ts:
-        z = z[~torch.eye(z.shape[0], dtype=torch.bool, device=device)]               # a set against itself: the self-trials are not trials
-    zmin, zmax = float(z.min()), float(z.max())
-    pad = 0.25 * (zmax - zmin)
-    return zmin - pad, zmax + pad
+    model = _check_plda_hist_args(enroll_xv, test_xv, cohort_xv, mu, F, Sigma, G, kind, topk)
+    scorer = PldaScorer(*model, scaling_factor).on(_device_of(enroll_xv, test_xv, cohort_xv))
+    return iv_scoring._range_from_sample(scorer, enroll_xv, test_xv, lambda z, es, ts: _norm_device(scorer, kind, z, es, ts, cohort_xv, topk))
 
 
 def matrix_moments_device(scoremat, axis, skip_diag=False):
@@ -493,13 +392,11 @@ def matrix_moments_device(scoremat, axis, skip_diag=False):
     if rows == 0 or cols == 0:
         raise ValueError("empty score matrix")
     device = _device_of(scoremat)
-    s = _f32(scoremat, device)
+    s = _to_device(scoremat, torch.float32, device)
     n = rows if axis == 1 else cols
     mean = torch.empty(n, dtype=torch.float32, device=device)
     std = torch.empty(n, dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().sc_matrix_moments(s.data_ptr(), rows, cols, int(axis), int(bool(skip_diag)), mean.data_ptr(), std.data_ptr(),
-                                                _stream(device)))
+    _lib.launch("sc_matrix_moments", device, s, rows, cols, int(axis), int(bool(skip_diag)), mean, std)
     return mean, std
 
 
@@ -527,7 +424,7 @@ def znorm(enrol_test_scores, enrol_imp_scores, sym=False):
     if sym and enrol_imp_scores.scoremat.shape[0] != enrol_imp_scores.scoremat.shape[1]:
         raise ValueError("sym=True needs a square impostor x impostor matrix")
     stats = matrix_moments_device(enrol_imp_scores.scoremat, 1, skip_diag=sym)
-    return _normalised(scores_znorm, _apply(_f32(scores_znorm.scoremat, stats[0].device), enrol=stats))
+    return _normalised(scores_znorm, _apply(CosineScorer, _to_device(scores_znorm.scoremat, torch.float32, stats[0].device), enrol=stats))
 
 
 def tnorm(enrol_test_scores, imp_test_scores):
@@ -538,7 +435,7 @@ def tnorm(enrol_test_scores, imp_test_scores):
     imp_test_scores.sort()
     _same_ids(scores_tnorm.segset, imp_test_scores.segset, "segset")
     stats = matrix_moments_device(imp_test_scores.scoremat, 0)
-    return _normalised(scores_tnorm, _apply(_f32(scores_tnorm.scoremat, stats[0].device), test=stats))
+    return _normalised(scores_tnorm, _apply(CosineScorer, _to_device(scores_tnorm.scoremat, torch.float32, stats[0].device), test=stats))
 
 
 def ztnorm(enrol_test_scores, enrol_imp_scores, imp_test_scores, imp_imp_scores):

@@ -337,6 +337,26 @@ def test_guards(gpu, odd, monkeypatch):
     assert int(got[0].sum() + got[1].sum()) == 130 * 257 - 257
 
 
+def test_one_object_on_both_sides_does_not_share_statistics(gpu, odd, monkeypatch):
+    """``test_xv is enroll_xv``: the enrolment side scores ``s(x, c)`` with ``Psi``, the test side ``s(c, x)`` with ``Psi'``; both are computed."""
+    x, c, model = odd["X"][:65], odd["c"], odd["model"]
+    Phi, Psi, cst = odd["params"]
+    mat = iv_scoring.plda_matrix_device(odd["Xc"][:65], odd["Xc"][:65], Phi, Psi, cst)
+    reached, lib = [], _lib.lib()
+    st = ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream)
+    for topk, want in ((None, {"sc_plda_cohort_moments": 2}), (7, {"sc_plda_fast": 2, "sc_topk_stats_f64": 2})):   # 65 rows: one row block per side
+        (me, se), (mt, sd) = (sn.plda_cohort_stats_device(x, c, *model, side=side, topk=topk) for side in ("enrol", "test"))
+        by_hand = mat.clone()
+        assert lib.sc_norm_apply_f64(by_hand.data_ptr(), 65, 65, me.data_ptr(), se.data_ptr(), mt.data_ptr(), sd.data_ptr(), st) == _lib.SK_OK
+        del reached[:]
+        monkeypatch.setattr(_lib, "lib", lambda: _Spy(lib, reached))
+        got = sn.plda_snorm_device(mat.clone(), x, x, c, *model, topk=topk)
+        monkeypatch.undo()
+        for name, count in want.items():
+            assert reached.count(name) == count, (topk, reached)
+        assert got.shape == (65, 65) and torch.equal(got, by_hand), topk
+
+
 # ---- the corpus of the neighbouring tests -------------------------------------------------------------------------------------------
 N, M, K = 1000, 200, 50
 TABLE = {"z": ((-7.75, 8.625), 0.082935), "t": ((-7.75, 8.625), 0.082935), "s": ((-7.375, 8.25), 0.081103), "as": ((-20.5, 16.75), 0.081404)}

@@ -12,6 +12,8 @@ from sidekit_amd import _lib
 from sidekit_amd import score_normalization as sn
 from sidekit_amd.bosaris import Scores
 
+from test_gpu_plda_norm import _Spy
+
 pytestmark = pytest.mark.gpu
 TOL = dict(rtol=5e-5, atol=5e-5)      # normalised scores: the tolerance of the asnorm tests (same arithmetic, same 1 / std amplification)
 
@@ -259,6 +261,22 @@ def test_adaptive_statistics_in_bounded_memory(gpu):
     assert torch.cuda.max_memory_allocated(gpu) - base <= 2 * N * 4 + (1 << 20)
     with pytest.raises(ValueError):
         sn.cohort_stats_device(x[:4], c[:10], topk=20)
+
+
+def test_one_object_on_both_sides_shares_the_statistics(gpu, monkeypatch):
+    """Cosine scores are symmetric: ``test_xv is enroll_xv`` computes the cohort moments once, an equal tensor of its own twice, same bits."""
+    rs = numpy.random.RandomState(13)
+    x, c = (torch.from_numpy(_unit(rs, n, 36)).to(gpu) for n in (65, 33))
+    mat = torch.from_numpy(_cosine(x, x).astype(numpy.float32)).to(gpu)
+    reached, lib = [], _lib.lib()
+    monkeypatch.setattr(_lib, "lib", lambda: _Spy(lib, reached))
+    shared = sn.snorm_device(mat.clone(), x, x, c)
+    assert reached.count("sc_cohort_moments") == 1, reached
+    del reached[:]
+    apart = sn.snorm_device(mat.clone(), x, x.clone(), c)
+    assert reached.count("sc_cohort_moments") == 2, reached
+    monkeypatch.undo()
+    assert shared.shape == (65, 65) and torch.equal(shared, apart) and not torch.equal(shared, mat)
 
 
 def test_drop_in_names_after_install_as_sidekit(gpu, fx):
