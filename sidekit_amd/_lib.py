@@ -97,6 +97,13 @@ SIGNATURES = {
     "sk_wav_read_pcm16": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _I64, _I32, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/gaussian_backend.h (sidekit_amd/lid_utils.py)
+GAUSSIAN_SIGNATURES = {
+    "sc_class_scatter": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _I32, _I64, _P, _P]),
+    "sc_gauss_loglik": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _P]),
+    "sc_closed_set_llr": (ctypes.c_int, [_P, _I32, _I64, _F64, _P, _P]),
+}
+
 _lib = None
 
 
@@ -113,7 +120,7 @@ def lib():
     if os.path.exists(hip_rt):
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     cdll = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -176,4 +176,12 @@ struct PldaPrep { double *epsi, *qe, *qt, *extra; int nparts; };
 int plda_prep_locked(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
                      hipStream_t st, PldaPrep* out, size_t extra_doubles = 0);
 
+// ---- plda_train.hip -------------------------------------------------------------------------
+// The cut of a TN product (sc_gemm_tn, sc_scatter_within; sc_class_scatter: `batch` products of the same M x N whose longest K is given):
+// the tile edge TL (big: 128), and K in `nsplit` slabs of `slab` rows whose partial tiles are added in slab order.
+struct TnCut { bool big; int TL; long nsplit, slab; };
+TnCut tn_cut(long K, int M, int N, long batch = 1);
+// G[i] = sum_p part[p * mn + i], p ascending: the slabs' partial tiles joined in slab order
+int launch_slab_reduce(const double* part, int nslabs, long mn, double* G, hipStream_t st);
+
 }  // namespace sk

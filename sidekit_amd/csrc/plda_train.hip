@@ -165,13 +165,12 @@ __global__ __launch_bounds__(256, 4) void dgemm_nn_kernel(const double* __restri
 }
 
 // The cut of a TN product: 128 x 128 tiles when the output has them and K is long (the total scatter), 64 x 64 otherwise; K is cut into
-// slabs (a multiple of the k-tile) until about 512 workgroups exist.  A function of (M, N, K) alone.
-struct TnCut { bool big; int TL; long nsplit, slab; };
-static TnCut tn_cut(long K, int M, int N) {
+// slabs (a multiple of the k-tile) until about 512 workgroups exist.  A function of (M, N, K, batch) alone (TnCut: kernels.h).
+TnCut tn_cut(long K, int M, int N, long batch) {
   TnCut c;
   c.big = M >= 128 && N >= 128 && K >= 4096;
   c.TL = c.big ? 128 : 64;
-  const long tiles = (long)cdiv(M, c.TL) * cdiv(N, c.TL);
+  const long tiles = batch * cdiv(M, c.TL) * cdiv(N, c.TL);
   c.nsplit = (K + 511) / 512;
   const long want = tiles >= 512 ? 1 : 512 / tiles;
   if (c.nsplit > want) c.nsplit = want;
@@ -179,6 +178,12 @@ static TnCut tn_cut(long K, int M, int N) {
   c.slab = (c.slab + DK - 1) / DK * DK;
   c.nsplit = (K + c.slab - 1) / c.slab;
   return c;
+}
+
+int launch_slab_reduce(const double* part, int nslabs, long mn, double* G, hipStream_t st) {
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, st, part, nslabs, mn, G);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
 }
 
 // launch(big, grid, slab, out) enqueues the tile kernel; with more than one slab its partial tiles go to the workspace and are added in
@@ -196,11 +201,7 @@ static int launch_tn_slabs(long K, int M, int N, double* G, hipStream_t st, Laun
   }
   launch(c.big, dim3(cdiv(N, c.TL), cdiv(M, c.TL), (unsigned)c.nsplit), (int)c.slab, out);
   SK_HIP(hipGetLastError());
-  if (c.nsplit > 1) {
-    const long mn = (long)M * N;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, st, out, (int)c.nsplit, mn, G);
-    SK_HIP(hipGetLastError());
-  }
+  if (c.nsplit > 1) SK_TRY(launch_slab_reduce(out, (int)c.nsplit, (long)M * N, G, st));
   return SK_OK;
 }
 
