@@ -2,7 +2,7 @@
 
 Sub-modules mirror the reference package layout for the hot path only:
 ``sidekit_amd.nnet.xvector.Xtractor``, ``sidekit_amd.iv_scoring``, ``sidekit_amd.factor_analyser``, ``sidekit_amd.statserver``,
-``sidekit_amd.bosaris``, ``sidekit_amd.score_normalization``, ``sidekit_amd.lid_utils``, ``sidekit_amd.sidekit_io``, ``sidekit_amd.frontend.vad``.
+``sidekit_amd.bosaris``, ``sidekit_amd.score_normalization``, ``sidekit_amd.lid_utils``, ``sidekit_amd.mixture``, ``sidekit_amd.sidekit_io``, ``sidekit_amd.frontend.vad``.
 ``install_as_sidekit()`` registers them under the ``sidekit`` names so that reference-style drivers
 (``extract_xvectors.py``, scoring scripts) import them unchanged.
 """
@@ -27,6 +27,7 @@ _LAZY = {
     "mahalanobis_scoring": "iv_scoring", "two_covariance_scoring": "iv_scoring",
     "plda_histograms": "iv_scoring", "plda_range_from_sample": "iv_scoring", "plda_norm_histograms": "iv_scoring",
     "FactorAnalyser": "factor_analyser",
+    "Mixture": "mixture",
     "asnorm": "score_normalization", "znorm": "score_normalization", "tnorm": "score_normalization", "ztnorm": "score_normalization",
     "asnorm_trials": "score_normalization", "cohort_stats_device": "score_normalization", "znorm_device": "score_normalization",
     "tnorm_device": "score_normalization", "snorm_device": "score_normalization", "ztnorm_device": "score_normalization",
@@ -40,7 +41,7 @@ _LAZY = {
 
 # every module of the mirror, by its reference name
 SUBMODULES = ("bosaris", "bosaris.idmap", "bosaris.ndx", "bosaris.key", "bosaris.scores", "bosaris.detplot", "statserver", "iv_scoring", "factor_analyser",
-              "score_normalization", "lid_utils", "sidekit_io", "nnet", "nnet.xvector", "nnet.preprocessor", "frontend", "frontend.vad")
+              "score_normalization", "lid_utils", "mixture", "sidekit_io", "nnet", "nnet.xvector", "nnet.preprocessor", "frontend", "frontend.vad")
 
 
 def __getattr__(name):

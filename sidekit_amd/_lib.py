@@ -104,6 +104,12 @@ GAUSSIAN_SIGNATURES = {
     "sc_closed_set_llr": (ctypes.c_int, [_P, _I32, _I64, _F64, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/mixture.h (sidekit_amd/mixture.py)
+MIXTURE_SIGNATURES = {
+    "sc_gmm_frame_loglik": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    "sc_gmm_stats": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -120,7 +126,7 @@ def lib():
     if os.path.exists(hip_rt):
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     cdll = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()) + list(MIXTURE_SIGNATURES.items()):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -5,9 +5,9 @@ the ~10 methods the x-vector scoring path calls: ``validate`` (:318-336), ``alig
 ``align_segments`` (:656-684), ``norm_stat1`` / ``rotate_stat1`` / ``center_stat1`` / ``whiten_stat1``
 (:797-817,852-896), ``get_mean_stat1`` (:789-795), ``sum_stat_per_model`` (:1335-1355), ``mean_stat_per_model`` (:1357-1374), and the
 back-end normalisations of x-vectors, which run on the GPU through ``sidekit_amd.backend`` (``get_within_covariance_stat1`` ...
-``get_wccn_choleski_stat1`` :940-1054, ``whiten_cholesky_stat1`` :898-918, spectral normalisation :1279-1333).  GMM statistics,
-MAP and i-vector extraction are out of scope; ``read`` / ``write`` (:392-489) exchange HDF5 files with the
-reference through ``sidekit_amd.hdf5_lite``.  Values are float64
+``get_wccn_choleski_stat1`` :940-1054, ``whiten_cholesky_stat1`` :898-918, spectral normalisation :1279-1333).  ``accumulate_stat`` (:687-739) computes the Baum-Welch
+statistics of a diagonal ``Mixture`` on the GPU (``sidekit_amd.mixture``); MAP adaptation and i-vector extraction are out of scope
+(SURVEY 2.1); ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
 (``STAT_TYPE``, ``sidekit/__init__.py:59``); the alignments use hashed lookups instead of per-id scans.
 """
 import copy
@@ -176,6 +176,76 @@ class StatServer:
             self.stat1 = self.stat1 / numpy.sqrt(sigma.astype(STAT_TYPE))
             return
         self.rotate_stat1(sigma if isSqrInvSigma else whitening_transform(sigma))
+
+    # ---- Baum-Welch statistics on the GPU (sidekit_amd/mixture.py): no CPU fallback ------------------------------------------------------
+
+    ACCUMULATE_BYTES = 1 << 30   # frames of the segments that go to the device in one accumulate_stat group, and the bound of its workspace
+
+    def accumulate_stat_device(self, ubm, frames, seg_off):
+        """Zeroth and first order statistics of every session from resident frames: session i is frames ``[seg_off[i], seg_off[i + 1])``
+        of ``frames`` ((N, D) CUDA tensor, float32 or float64).  Fills ``stat0`` (sessions x C) and ``stat1`` (sessions x C D)."""
+        from .mixture import Mixture, gmm_stats_device
+        assert isinstance(ubm, Mixture), 'First parameter has to be a Mixture'
+        assert len(seg_off) == self.segset.shape[0] + 1, "seg_off: one offset per session and the end of the last"
+        if not ubm.dim() == frames.shape[1]:
+            raise Exception('dimension of ubm and features differ: {:d} / {:d}'.format(ubm.dim(), frames.shape[1]))
+        stat0, stat1, _, _ = gmm_stats_device(ubm, frames, seg_off, order=1, max_workspace_bytes=self.ACCUMULATE_BYTES)
+        to_host = (lambda t: t) if isinstance(stat0, numpy.ndarray) else (lambda t: t.cpu().numpy())
+        self.stat0 = to_host(stat0).astype(STAT_TYPE, copy=False)
+        self.stat1 = to_host(stat1).reshape(stat0.shape[0], ubm.sv_size()).astype(STAT_TYPE, copy=False)
+
+    def accumulate_stat(self, ubm, feature_server, seg_indices=None, channel_extension=("", "_b"), num_thread=1):
+        """Statistics of the sessions ``seg_indices`` (all when ``None``) under ``ubm`` (``statserver.py:687-739``).  ``feature_server``: any
+        object whose ``load(show, channel=)`` returns ``(cep, vad_label)``; each session is cut to its ``start`` / ``stop`` and to its
+        speech frames as in the reference, the sessions are stacked in groups of at most ``ACCUMULATE_BYTES`` of frames and a group is
+        one ``gmm_stats_device`` call.  ``num_thread`` is accepted and unused."""
+        from .mixture import Mixture, gmm_stats_device
+        assert isinstance(ubm, Mixture), 'First parameter has to be a Mixture'
+        sessions = self.segset.shape[0]
+        if seg_indices is None or self.stat0.shape[0] != sessions or self.stat1.shape[0] != sessions:   # nothing usable is held: every session
+            self.stat0 = numpy.zeros((sessions, ubm.distrib_nb()), dtype=STAT_TYPE)
+            self.stat1 = numpy.zeros((sessions, ubm.sv_size()), dtype=STAT_TYPE)
+            seg_indices = range(sessions)
+        feature_server.keep_all_features = True
+        group, held = [], 0
+        for idx in seg_indices:
+            frames = self._speech_frames(idx, feature_server, channel_extension)
+            if frames.shape[1] != ubm.dim():
+                raise Exception('dimension of ubm and features differ: {:d} / {:d}'.format(ubm.dim(), frames.shape[1]))
+            group.append((idx, frames))
+            held += frames.nbytes
+            if held >= self.ACCUMULATE_BYTES:
+                self._accumulate_group(ubm, group, gmm_stats_device)
+                group, held = [], 0
+        self._accumulate_group(ubm, group, gmm_stats_device)
+
+    def _speech_frames(self, idx, feature_server, channel_extension):
+        """The frames of session ``idx`` that count: rows ``start`` to ``stop`` (to the end of the labels when ``stop`` is unset or beyond
+        it) of what the server loads for the show, those the VAD labels keep.  A show name that ends in the second channel's extension
+        is channel 1 when a features extractor stands behind the server; the channel's extension is cut off the name that is loaded."""
+        name = self.segset[idx]
+        second = getattr(feature_server, "features_extractor", None) is not None and name.endswith(channel_extension[1])
+        extension = channel_extension[1 if second else 0]
+        cep, labels = feature_server.load(name[:name.rfind(extension)], channel=int(second))
+        first, last = self.start[idx], labels.shape[0]
+        if self.stop[idx] is not None:
+            last = min(self.stop[idx], last)
+        logging.info('%s: frames %s to %s', name, first, last)
+        return cep[first:last][labels[first:last]]
+
+    def _accumulate_group(self, ubm, group, gmm_stats_device):
+        """One ``gmm_stats_device`` call for the stacked frames of ``group`` = [(session, frames)]; sessions without frames keep zeros"""
+        if not group:
+            return
+        rows = [idx for idx, _ in group]
+        offsets = numpy.concatenate(([0], numpy.cumsum([f.shape[0] for _, f in group])))
+        self.stat0[rows, :] = 0.0
+        self.stat1[rows, :] = 0.0
+        if offsets[-1] > 0:
+            stat0, stat1, _, _ = gmm_stats_device(ubm, numpy.concatenate([f for _, f in group]), offsets, order=1,
+                                                  max_workspace_bytes=self.ACCUMULATE_BYTES)
+            self.stat0[rows, :] = stat0
+            self.stat1[rows, :] = stat1.reshape(len(rows), ubm.sv_size())
 
     # ---- back-end normalisation on the GPU (sidekit_amd/backend.py): stat1 is uploaded once per call, no CPU fallback ----------------
 
