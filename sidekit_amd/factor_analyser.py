@@ -1,5 +1,7 @@
-"""PLDA training -- mirror of ``sidekit/factor_analyser.py``: ``FactorAnalyser`` with ``plda`` (:830-932), ``write`` / ``read``
-(:265-324), and ``plda_device`` for x-vectors that are already on the GPU.
+"""PLDA and total-variability training -- mirror of ``sidekit/factor_analyser.py``: ``FactorAnalyser`` with ``plda`` (:830-932),
+``total_variability`` / ``total_variability_single`` (:433-686), ``extract_ivectors`` / ``extract_ivectors_single`` (:688-828), ``write`` /
+``read`` (:265-324), ``plda_device`` for x-vectors and ``total_variability_device`` / ``extract_ivectors_device`` for Baum-Welch
+statistics that are already on the GPU.
 
 The producer of the ``(mean, F, Sigma)`` that ``iv_scoring.fast_PLDA_scoring`` consumes.  The split is the scoring side's: everything
 with an utterance (N) or class (C) dimension runs on the device in float64 through the C ABI -- ``sc_class_sums`` (the sums
@@ -13,8 +15,17 @@ The E-step is restated.  The reference inverts ``I + n F'F`` once per distinct s
 so the device forms ``Q = (S_w F_w U) / (1 + n a')`` in one GEMM with a per-element scale, the accumulators ``Q'Q``, ``Q' diag(n) Q``,
 ``Q' S_w`` are rotated back by ``U`` on the host, and the two sums of inverses become ``U diag(sum_i 1 / (1 + n_i a)) U'`` and
 ``U diag(sum_i n_i / (1 + n_i a)) U'``.  ``F`` is defined up to the sign of each column (the eigenvectors that initialise it have none).
-There is no CPU fallback for training; importing the module, ``write`` and ``read`` work on any host.
+
+Total variability follows the same split.  ``e_on_batch`` (:51-91) loops over the sessions in Python and inverts one ``R x R`` matrix built
+from the whole ``C D x R`` loading matrix per session; here the four large products are GEMMs -- the packed sums ``stat0 . G`` with
+``G[c] = F_c' F_c`` (``sc_tv_gram``, once per iteration), the projections ``S_w . F`` and the accumulators (``sc_dgemm_nn``, ``sc_gemm_tn``)
+-- and the per-session step between them (``Lambda = I + sum``, its inverse, ``e_h``, ``E_hh``) is one kernel, ``sc_tv_posterior``
+(``include/sidekit_amd/ivector.h``), a workgroup per session with the packed matrix in LDS.  The M-step (``C`` solves of ``R x R`` systems, one
+Cholesky factor) stays on the host in the reference's operation order.  Ranks above ``TV_MAX_RANK`` (a blocked factorisation outside
+LDS), ``total_variability_raw``, full-covariance UBMs and ``weighted_likelihood_plda`` are not built.
+There is no CPU fallback for training or extraction; importing the module, ``write`` and ``read`` work on any host.
 """
+import copy
 import ctypes
 import logging
 import os
@@ -26,6 +37,7 @@ from . import _lib, hdf5_lite
 from .statserver import STAT_TYPE, StatServer
 
 SLICE_ROWS = 256   # rows one workgroup of the class-sum kernel adds; longer classes are cut into slices joined in order
+TV_MAX_RANK = 192  # SC_TV_MAX_RANK (include/sidekit_amd/ivector.h): one packed triangle of the rank in LDS
 
 
 class ClassIndex:
@@ -181,8 +193,193 @@ def plda_device(xv, class_index, rank_f, nb_iter=10, scaling_factor=1.):
     return _em(xv, ClassIndex(class_index), rank_f, nb_iter, scaling_factor)
 
 
+# ---- total variability ------------------------------------------------------------------------------------------------------------------
+
+def packed_size(rank):
+    """Doubles of a packed upper triangle; (i, j), i <= j, is at ``i R - i (i - 1) / 2 + (j - i)``, the order of ``numpy.triu_indices``"""
+    return rank * (rank + 1) // 2
+
+
+def _unpack(p, rank):
+    full = numpy.zeros((rank, rank), dtype=STAT_TYPE)
+    upper = numpy.triu_indices(rank)
+    full[upper] = full.T[upper] = p
+    return full
+
+
+def _check_rank(tv_rank):
+    if not 1 <= tv_rank <= TV_MAX_RANK:
+        raise ValueError("tv_rank = {} is outside [1, {}]: sc_tv_posterior keeps one packed triangle of the rank in LDS "
+                         "(SC_TV_MAX_RANK = {})".format(tv_rank, TV_MAX_RANK, TV_MAX_RANK))
+
+
+def _check_ubm(ubm):
+    """A diagonal mixture -> (C, D); a full-covariance one is refused like everywhere in ``sidekit_amd.mixture``"""
+    from .mixture import Mixture, _full_covariance
+    assert isinstance(ubm, Mixture) and ubm.validate(), "Second argument must be a proper Mixture"
+    if ubm.invcov.ndim == 3:
+        raise _full_covariance()
+    return ubm.mu.shape
+
+
+def _statistics(torch, stat0, stat1, C, D):
+    """Resident statistics as ``gmm_stats_device`` returns them (stat1 (N, C, D) or (N, C D)) -> float64 (N, C) and (N, C D), used where they are"""
+    assert torch.is_tensor(stat0) and torch.is_tensor(stat1) and stat0.is_cuda and stat1.is_cuda, "expected statistics on the device (CUDA tensors)"
+    stat0, stat1 = _f64(torch, stat0, stat0.device), _f64(torch, stat1, stat0.device)
+    assert stat0.dim() == 2 and stat0.shape[1] == C and stat0.shape[0] > 0, "stat0: (sessions, C)"
+    assert stat1.shape[0] == stat0.shape[0] and stat1.numel() == stat0.shape[0] * C * D, "stat1: (sessions, C D)"
+    return stat0, stat1.reshape(stat0.shape[0], C * D)
+
+
+def _whitener(torch, ubm, dev):
+    """(mean, sqrt(invcov)) as (C, D) device tensors"""
+    return _f64(torch, ubm.mu, dev), torch.sqrt(_f64(torch, ubm.invcov, dev))
+
+
+def _whiten(stat0, stat1, whitener):
+    """``(stat1 - stat0[:, index_map] * mean_sv) * sqrt(invcov_sv)`` (:75-78) as a new tensor"""
+    mean, scale = whitener
+    N, C = stat0.shape
+    return ((stat1.view(N, C, -1) - stat0[:, :, None] * mean) * scale).view(N, -1)
+
+
+def _batch_rows(N, C, D, R, max_workspace_bytes):
+    """Sessions per device batch: the packed triangle, the whitened statistics, the counts and two R-vectors per session within the budget"""
+    return max(1, min(N, int(max_workspace_bytes) // (8 * (packed_size(R) + C * D + C + 2 * R))))
+
+
+def tv_gram_device(F, C):
+    """``G[c] = F_c' F_c`` packed, (C, P) (``sc_tv_gram``): F ((C D), R) float64 CUDA tensor"""
+    torch = _torch()
+    F = _f64(torch, F, F.device)
+    R = F.shape[1]
+    _check_rank(R)
+    assert F.shape[0] % C == 0
+    G = torch.empty((C, packed_size(R)), dtype=torch.float64, device=F.device)
+    _lib.launch("sc_tv_gram", F.device, F, C, F.shape[0] // C, R, G)
+    return G
+
+
+def tv_posterior_device(stat0, stat1_w, F, G=None, want="packed"):
+    """The posterior of every session given WHITENED first-order statistics (``e_on_batch`` :85-89): ``stat0`` (N, C), ``stat1_w``
+    (N, C D), ``F`` ((C D), R) float64 CUDA tensors, ``G`` the packed Gram matrices of ``F`` (``tv_gram_device``; formed when None).
+    Returns ``(e_h (N, R), E_hh)``: ``want="packed"``: the (N, P) packed upper triangles of ``inv_lambda + e_h e_h'``; ``"diag"``: their
+    (N, R) diagonals only.  Two ``sc_dgemm_nn`` and one ``sc_tv_posterior``; the packed sums are overwritten by the packed output."""
+    assert want in ("packed", "diag")
+    torch = _torch()
+    dev = stat0.device
+    R = F.shape[1]
+    _check_rank(R)
+    if G is None:
+        G = tv_gram_device(F, stat0.shape[1])
+    Lp = dgemm_nn_device(stat0, G)
+    B = dgemm_nn_device(stat1_w, F)
+    e_h = torch.empty_like(B)
+    diag = torch.empty_like(B) if want == "diag" else None
+    _lib.launch("sc_tv_posterior", dev, Lp, B, Lp.shape[0], R, e_h, Lp if want == "packed" else None, diag)
+    return e_h, (Lp if want == "packed" else diag)
+
+
+def tv_m_step(_A, _C, _R, nb_sessions, min_div=True):
+    """The host M-step (:516-530) from the accumulators ``_A`` (C, P), ``_C`` (R, C D), ``_R`` (P,) summed over ``nb_sessions``: per
+    component ``F_c = solve(unpack(_A[c]), _C[:, c]).T``, then ``F . cholesky(unpack(_R / nb_sessions))`` when ``min_div``"""
+    C, R = _A.shape[0], _C.shape[0]
+    D = _C.shape[1] // C
+    F = numpy.empty((C * D, R), dtype=STAT_TYPE)
+    for c in range(C):
+        F[c * D:(c + 1) * D, :] = scipy.linalg.solve(_unpack(_A[c], R), _C[:, c * D:(c + 1) * D]).T
+    if min_div:
+        F = F.dot(scipy.linalg.cholesky(_unpack(_R / nb_sessions, R)))
+    return F
+
+
+def _tv_e_step(torch, stat0, stat1, whitener, F_d, rows):
+    """The accumulators of one E-step over all sessions, added in batch order -> host ``(_A, _C, _R)``"""
+    N, C = stat0.shape
+    G = tv_gram_device(F_d, C)
+    ones = torch.ones((rows, 1), dtype=torch.float64, device=stat0.device)
+    acc = None
+    for a in range(0, N, rows):
+        s0 = stat0[a:a + rows]
+        sw = _whiten(s0, stat1[a:a + rows], whitener)
+        e_h, e_hh = tv_posterior_device(s0, sw, F_d, G)
+        part = (gemm_tn_device(s0, e_hh), gemm_tn_device(e_h, sw), gemm_tn_device(ones[:s0.shape[0]], e_hh))
+        acc = part if acc is None else tuple(t.add_(p) for t, p in zip(acc, part))
+    return acc[0].cpu().numpy(), acc[1].cpu().numpy(), acc[2].cpu().numpy()[0]
+
+
+def total_variability_device(stat0, stat1, ubm, tv_rank, nb_iter=20, min_div=True, tv_init=None, max_workspace_bytes=1 << 30,
+                             after_iteration=None):
+    """Train a total variability matrix on Baum-Welch statistics that are on the GPU (the output of ``mixture.gmm_stats_device`` as it
+    is): ``stat0`` (N, C), ``stat1`` (N, C, D) or (N, C D), not whitened and not modified.  ``tv_init=None`` draws
+    ``numpy.random.randn(sv_size, tv_rank)`` as the reference does (:476), so ``numpy.random.seed`` gives the same start.  Sessions go
+    through the E-step in batches cut from ``max_workspace_bytes`` (``P + C D + C + 2 R`` doubles per session, one session at least);
+    the accumulators are added in batch order.  The M-step runs on the host.  ``after_iteration(it, F)`` is called after every
+    iteration.  Returns ``F`` ((C D), R), a float64 numpy array; the statistics are never copied to the host."""
+    C, D = _check_ubm(ubm)
+    _check_rank(tv_rank)
+    assert isinstance(nb_iter, int) and 0 < nb_iter, "nb_iter must be a positive integer"
+    torch = _torch()
+    stat0, stat1 = _statistics(torch, stat0, stat1, C, D)
+    N, dev = stat0.shape[0], stat0.device
+    F = numpy.random.randn(C * D, tv_rank) if tv_init is None else numpy.array(tv_init, dtype=STAT_TYPE)
+    assert F.shape == (C * D, tv_rank), "tv_init: (C D, tv_rank)"
+    whitener = _whitener(torch, ubm, dev)
+    rows = _batch_rows(N, C, D, tv_rank, max_workspace_bytes)
+    for it in range(nb_iter):
+        logging.info('Total variability, it %d / %d', it + 1, nb_iter)
+        _A, _C, _R = _tv_e_step(torch, stat0, stat1, whitener, _f64(torch, F, dev), rows)
+        F = tv_m_step(_A, _C, _R, N, min_div)
+        if after_iteration is not None:
+            after_iteration(it, F)
+    return F
+
+
+def _extract(stat0, stat1, whitener, F, uncertainty, max_workspace_bytes):
+    """i-vectors (and the diagonal of ``E_hh``) of resident statistics; ``whitener=None``: ``stat1`` is whitened already"""
+    torch = _torch()
+    N, C = stat0.shape
+    R = F.shape[1]
+    F_d = _f64(torch, F, stat0.device)
+    G = tv_gram_device(F_d, C)
+    iv = torch.empty((N, R), dtype=torch.float64, device=stat0.device)
+    iv_sigma = torch.empty_like(iv)
+    rows = _batch_rows(N, C, stat1.shape[1] // C, R, max_workspace_bytes)
+    for a in range(0, N, rows):
+        s0, s1 = stat0[a:a + rows], stat1[a:a + rows]
+        iv[a:a + rows], iv_sigma[a:a + rows] = tv_posterior_device(s0, s1 if whitener is None else _whiten(s0, s1, whitener), F_d, G, want="diag")
+    return (iv, iv_sigma) if uncertainty else iv
+
+
+def extract_ivectors_device(stat0, stat1, ubm, F, uncertainty=False, max_workspace_bytes=1 << 30):
+    """i-vectors of Baum-Welch statistics that are on the GPU (``stat0`` (N, C), ``stat1`` (N, C, D) or (N, C D), not whitened, not
+    modified) under the loading matrix ``F`` ((C D), R): ``iv`` (N, R), or ``(iv, iv_sigma)`` with the diagonal of ``E_hh`` when
+    ``uncertainty``; float64 CUDA tensors.  Batches as in ``total_variability_device``."""
+    C, D = _check_ubm(ubm)
+    _check_rank(F.shape[1])
+    assert F.shape[0] == C * D, "F: (C D, R)"
+    torch = _torch()
+    stat0, stat1 = _statistics(torch, stat0, stat1, C, D)
+    return _extract(stat0, stat1, _whitener(torch, ubm, stat0.device), F, uncertainty, max_workspace_bytes)
+
+
+def _read_statistics(source, prefix=''):
+    """A ``StatServer`` object, or the file of one (read with ``hdf5_lite``)"""
+    return source if isinstance(source, StatServer) else StatServer.read(source, prefix)
+
+
+def _ivector_server(stat_server, iv):
+    """The reference's i-vector ``StatServer`` (:719-725): copies of the identifiers, ones as ``stat0``"""
+    out = StatServer()
+    out.modelset, out.segset = copy.deepcopy(stat_server.modelset), copy.deepcopy(stat_server.segset)
+    out.start, out.stop = copy.deepcopy(stat_server.start), copy.deepcopy(stat_server.stop)
+    out.stat0 = numpy.ones((stat_server.modelset.shape[0], 1), dtype=STAT_TYPE)
+    out.stat1 = iv
+    return out
+
+
 class FactorAnalyser:
-    """``sidekit.FactorAnalyser`` (factor_analyser.py:208-262) for PLDA: attributes ``mean, F, G, H, Sigma``."""
+    """``sidekit.FactorAnalyser`` (factor_analyser.py:208-262) for PLDA and total variability: attributes ``mean, F, G, H, Sigma``."""
 
     def __init__(self, input_file_name=None, mean=None, F=None, G=None, H=None, Sigma=None):
         self.mean = self.F = self.G = self.H = self.Sigma = None
@@ -243,3 +440,74 @@ class FactorAnalyser:
                 self.write(output_file_name + ".h5")
 
         self.mean, self.F, self.Sigma = _em(xv, index, rank_f, nb_iter, scaling_factor, stat0_sums, save)
+
+    # ---- total variability (sidekit_amd/csrc/ivector.hip): no CPU fallback ---------------------------------------------------------------
+
+    def total_variability(self, stat_server_filename, ubm, tv_rank, nb_iter=20, min_div=True, tv_init=None, batch_size=300, save_init=False,
+                          output_file_name=None, num_thread=1):
+        """Train a total variability model (:539-686).  ``stat_server_filename``: the name of a ``StatServer`` file (read with
+        ``hdf5_lite``), a list of names, or a ``StatServer`` object; with a list the sessions of all files accumulate into one E-step and
+        ``_R`` is divided by their total, as in the reference.  The statistics are uploaded once and stay on the device over all
+        iterations (``total_variability_device``); they are not modified.  ``batch_size`` and ``num_thread`` are accepted and ignored: the
+        device batch is cut from a memory budget, not from a session count, and there are no worker processes.  Sets ``mean`` and
+        ``Sigma`` to zeros of the supervector size and ``F``; with ``output_file_name`` saves ``<output_file_name>_it-<k>.h5`` after
+        every iteration but the last and ``<output_file_name>.h5`` after the last; ``save_init`` writes ``<output_file_name>_init.h5``
+        and needs ``output_file_name`` (the reference raises a ``TypeError`` without it)."""
+        C, D = _check_ubm(ubm)
+        _check_rank(tv_rank)
+        assert isinstance(nb_iter, int) and 0 < nb_iter, "nb_iter must be a positive integer"
+        assert not save_init or output_file_name is not None, "save_init needs output_file_name"
+        torch = _torch()
+        sources = stat_server_filename if isinstance(stat_server_filename, list) else [stat_server_filename]
+        servers = [_read_statistics(src) for src in sources]
+        dev = torch.device("cuda", torch.cuda.current_device())
+        stat0, stat1 = (torch.cat([torch.as_tensor(numpy.ascontiguousarray(getattr(sv, name), dtype=STAT_TYPE)).to(dev) for sv in servers])
+                        for name in ("stat0", "stat1"))
+        self.mean = numpy.zeros(ubm.get_mean_super_vector().shape, dtype=STAT_TYPE)
+        self.Sigma = numpy.zeros(ubm.get_mean_super_vector().shape, dtype=STAT_TYPE)
+        self.F = numpy.random.randn(C * D, tv_rank).astype(STAT_TYPE) if tv_init is None else tv_init
+        if save_init:
+            self.write(output_file_name + "_init.h5")
+
+        def save(it, F):
+            self.F = F
+            if output_file_name is not None:
+                self.write(output_file_name + ("_it-{}.h5".format(it) if it < nb_iter - 1 else ".h5"))
+
+        self.F = total_variability_device(stat0, stat1, ubm, tv_rank, nb_iter, min_div, self.F, after_iteration=save)
+
+    def total_variability_single(self, stat_server_filename, ubm, tv_rank, nb_iter=20, min_div=True, tv_init=None, batch_size=300,
+                                 save_init=False, output_file_name=None):
+        """The reference's single-process variant (:433-537): here the same code as ``total_variability``"""
+        self.total_variability(stat_server_filename, ubm, tv_rank, nb_iter, min_div, tv_init, batch_size, save_init, output_file_name)
+
+    def extract_ivectors_single(self, ubm, stat_server, uncertainty=False):
+        """i-vectors of a ``StatServer`` (:688-744) -> a ``StatServer`` with the i-vectors as ``stat1``, ones as ``stat0`` and copies of
+        ``modelset``, ``segset``, ``start``, ``stop``; with ``uncertainty`` also ``iv_sigma``, the diagonal of ``E_hh``.  As in the
+        reference the caller's ``stat_server`` is left whitened in place (``whiten_stat1``)."""
+        assert isinstance(stat_server, StatServer) and stat_server.validate(), "First argument must be a proper StatServer"
+        C, D = _check_ubm(ubm)
+        _check_rank(self.F.shape[1])
+        torch = _torch()
+        stat_server.whiten_stat1(ubm.get_mean_super_vector(), 1. / ubm.get_invcov_super_vector())
+        dev = torch.device("cuda", torch.cuda.current_device())
+        stat0, stat1 = _statistics(torch, *(torch.as_tensor(numpy.ascontiguousarray(x, dtype=STAT_TYPE)).to(dev)
+                                            for x in (stat_server.stat0, stat_server.stat1)), C, D)
+        iv, iv_sigma = _extract(stat0, stat1, None, self.F, True, 1 << 30)
+        out = _ivector_server(stat_server, iv.cpu().numpy())
+        return (out, iv_sigma.cpu().numpy()) if uncertainty else out
+
+    def extract_ivectors(self, ubm, stat_server_filename, prefix='', batch_size=300, uncertainty=False, num_thread=1):
+        """i-vectors of the ``StatServer`` stored in a file (:746-828), or of a ``StatServer`` object, which is not modified -> as
+        ``extract_ivectors_single``.  ``batch_size`` and ``num_thread`` are accepted and ignored (the device batch is cut from a memory
+        budget).  One deviation on purpose: ``prefix`` applies to every dataset that is read; the reference forgets it on ``stat0`` /
+        ``stat1`` (:808)."""
+        C, D = _check_ubm(ubm)
+        _check_rank(self.F.shape[1])
+        torch = _torch()
+        server = _read_statistics(stat_server_filename, prefix)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        stat0, stat1 = (torch.as_tensor(numpy.ascontiguousarray(x, dtype=STAT_TYPE)).to(dev) for x in (server.stat0, server.stat1))
+        iv, iv_sigma = extract_ivectors_device(stat0, stat1, ubm, self.F, uncertainty=True)
+        out = _ivector_server(server, iv.cpu().numpy())
+        return (out, iv_sigma.cpu().numpy()) if uncertainty else out

@@ -6,8 +6,8 @@ the ~10 methods the x-vector scoring path calls: ``validate`` (:318-336), ``alig
 (:797-817,852-896), ``get_mean_stat1`` (:789-795), ``sum_stat_per_model`` (:1335-1355), ``mean_stat_per_model`` (:1357-1374), and the
 back-end normalisations of x-vectors, which run on the GPU through ``sidekit_amd.backend`` (``get_within_covariance_stat1`` ...
 ``get_wccn_choleski_stat1`` :940-1054, ``whiten_cholesky_stat1`` :898-918, spectral normalisation :1279-1333).  ``accumulate_stat`` (:687-739) computes the Baum-Welch
-statistics of a diagonal ``Mixture`` on the GPU (``sidekit_amd.mixture``); MAP adaptation and i-vector extraction are out of scope
-(SURVEY 2.1); ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
+statistics of a diagonal ``Mixture`` on the GPU (``sidekit_amd.mixture``), which ``FactorAnalyser.total_variability`` /
+``extract_ivectors`` consume (``sidekit_amd.factor_analyser``); MAP adaptation is out of scope; ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
 (``STAT_TYPE``, ``sidekit/__init__.py:59``); the alignments use hashed lookups instead of per-id scans.
 """
 import copy
