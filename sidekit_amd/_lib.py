@@ -110,6 +110,11 @@ MIXTURE_SIGNATURES = {
     "sc_gmm_stats": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/gmm_scoring.h (sidekit_amd/gmm_scoring.py)
+GMM_SCORING_SIGNATURES = {
+    "sc_gmm_score_models": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _I32, _P, _P, _I32, _P, _I32, _I64, _P, _P, _P]),
+}
+
 # name -> (restype, argtypes); every symbol of include/sidekit_amd/ivector.h (sidekit_amd/factor_analyser.py)
 IVECTOR_SIGNATURES = {
     "sc_tv_gram": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
@@ -133,7 +138,7 @@ def lib():
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     cdll = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()) + list(MIXTURE_SIGNATURES.items())
-                              + list(IVECTOR_SIGNATURES.items())):
+                              + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

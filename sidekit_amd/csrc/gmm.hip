@@ -13,42 +13,12 @@
 //   Ps  64 x 65        pass B: the posterior tile, [component][frame], the A operand of the second GEMM
 // pass B at D = 60: 73 KB (two workgroups per CU), at D = 128: 108 KB (one); pass A: 40 KB / 75 KB.  Pass B's accumulator is
 // 16 components x 16 NT columns per wave (NT tiles cover 2 D + 1 columns, or D + 1 for order 1): 4 NT doubles per lane, 32 at D = 60.
-#include <cmath>
-
-#include "../../include/sidekit_amd/mixture.h"
-#include "dgemm_tile.h"
+#include "gmm_tile.h"
 #include "kernels.h"
 
 namespace sk {
 
-constexpr int GT = 64;              // frames per tile, components per tile
 constexpr int PLD = GT + 1;         // row stride of the posterior tile
-
-__host__ __device__ inline int gmm_xld(int D) { return D | 1; }
-
-// The cut of a segment of `len` frames: slab i is frames [i * slab, min(len, (i + 1) * slab)) of the segment; gmm_slabs(len) of them are not empty.
-__host__ __device__ inline long gmm_slabs(long len) {
-  const long n = (len + SC_GMM_SLAB_FRAMES - 1) / SC_GMM_SLAB_FRAMES;
-  return n < 1 ? 1 : (n > SC_GMM_MAX_SLABS ? SC_GMM_MAX_SLABS : n);
-}
-__host__ __device__ inline long gmm_slab_len(long len) {
-  const long n = gmm_slabs(len), s = (len + n - 1) / n;
-  return s < GT ? GT : (s + GT - 1) / GT * GT;
-}
-
-// Frames [f0, f0 + nvalid) of X into Xs (rows beyond nvalid and the padding column: zeros, nothing is read for them).  One wave per row.
-template <typename T>
-__device__ inline void gmm_load_frames(const T* __restrict__ X, int D, long f0, int nvalid, double* Xs, int xld) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < GT; r += 4) {
-    const T* src = X + (f0 + r) * D;
-    for (int d = lane; d < xld; d += 64) {
-      double v = 0.0;
-      if (r < nvalid && d < D) v = (double)src[d];
-      Xs[r * xld + d] = v;
-    }
-  }
-}
 
 // acc[i][q] = sum_d Xs[f][d]^2 invcov[c][d] + sum_d Xs[f][d] (-2 mu[c][d] invcov[c][d]),  f = 16 i + (lane >> 4) + 4 q,  c = c0 + 16 wave + (lane & 15);
 // the squares first, then the linear half, each in chunks of 16 d (zeros beyond D and C).  Starts with a barrier (Xs is complete, Gs is free).
@@ -99,13 +69,6 @@ __device__ inline void gmm_lp_tile(const double* Xs, int xld, double* Gs, const 
       for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b, acc[i], 0, 0, 0);
     }
   }
-}
-
-// (M, S) <- the log-sum-exp state of both: sum = S exp(M); symmetric in its two states bit for bit
-__device__ inline void lse_merge(double& M, double& S, double m2, double s2) {
-  const double m = fmax(M, m2);
-  S = m == -INFINITY ? 0.0 : S * exp(M - m) + s2 * exp(m2 - m);
-  M = m;
 }
 
 // ---- pass A ------------------------------------------------------------------------------------------------------------------------
@@ -276,13 +239,6 @@ __global__ __launch_bounds__(256) void gmm_seg_llk_kernel(const double* __restri
     __syncthreads();
   }
   if (tid == 0) llk[seg] = red[0];
-}
-
-// More than 64 KB of dynamic LDS has to be allowed per kernel before the launch; below that nothing is to be done.
-template <typename K>
-static int gmm_allow_lds(K kernel, size_t bytes) {
-  if (bytes > 65536) SK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return SK_OK;
 }
 
 template <typename T>

@@ -1,0 +1,204 @@
+"""GMM-UBM verification -- mirror of ``sidekit/gmm_scoring.py``: ``gmm_scoring`` and ``gmm_scoring_singleThread`` (:53-177), the
+log-likelihood ratio between mean-adapted models of a diagonal ``Mixture`` and the mixture itself, averaged over a test segment's frames.
+
+The reference loops over segments and models in Python and forms an ``N x C`` matrix of log posteriors per pair.  Here all models of a
+batch of segments go through one kernel (``sc_gmm_score_models``, ``include/sidekit_amd/gmm_scoring.h``): float64 on the f64 matrix
+cores, the model-independent half of the exponent computed once per group of models, and only the ``M x S`` segment sums leave it.
+The ``*_device`` functions work on resident frames (float32 or float64, widened in the load) and resident models, and
+``map_adapt_device`` adapts the means from resident statistics (``gmm_stats_device``), so the path from statistics to adapted models to
+scores never leaves the device.  The UBM is scored as one more model by the same code, so a model equal to the UBM scores exactly 0.
+Full covariances raise ``NotImplementedError``; top-C (fast) scoring and ``jfa_scoring`` are not built.  There is no CPU fallback;
+importing the module needs neither a GPU nor torch.
+"""
+import logging
+
+import numpy
+
+from . import _lib, mixture
+from .bosaris import Ndx, Scores
+from .mixture import Mixture
+from .statserver import StatServer
+
+SCORING_BYTES = 1 << 30   # frames of the test segments that go to the device in one gmm_scoring batch, and the bound of its workspace
+MAX_MODELS = 65535    # SC_GMM_SCORE_MAX_M (include/sidekit_amd/gmm_scoring.h): models of one sc_gmm_score_models call
+
+
+def _device_f64(torch, a, dev):
+    if torch.is_tensor(a):
+        return a.to(device=dev, dtype=torch.float64).contiguous()
+    return torch.as_tensor(numpy.array(a, dtype=numpy.float64, order='C')).to(dev)   # a copy: the source may be read-only
+
+
+def _offsets(seg_off, N):
+    off = numpy.array([0, N], dtype=numpy.int64) if seg_off is None else numpy.asarray(seg_off, dtype=numpy.int64)
+    assert off.ndim == 1 and off.shape[0] >= 2 and numpy.all(numpy.diff(off) >= 0) and off[0] >= 0 and off[-1] <= N, \
+        "seg_off: S + 1 ascending offsets within [0, N]"
+    return off
+
+
+def gmm_llk_device(ubm, models, frames, seg_off=None, mask=None, max_workspace_bytes=1 << 30):
+    """``llk[m, s] = sum_n log sum_c w_c N(x_n; models[m, c], Sigma_c)`` over the frames of segment ``s`` (``sc_gmm_score_models``).
+    ``models``: (M, C D) or (M, C, D) means, host array or CUDA tensor; ``frames``: (N, D) CUDA tensor (float32 or float64) or host array;
+    ``seg_off``: S + 1 ascending frame offsets (host), ``None``: one segment; ``mask``: (M, S) booleans, the trials to compute (``None``:
+    all), the other entries are 0.  Returns ``(llk (M, S) float64, lengths (S,) int64)``, on the device when the frames were there.
+    Models go to the kernel in consecutive chunks whose workspace stays within ``max_workspace_bytes`` (one model at least); the
+    chunking does not change a bit."""
+    if ubm.invcov.ndim == 3:
+        raise mixture._full_covariance()
+    torch = mixture._torch()
+    x, dt, host = mixture._frames(torch, frames)
+    N, D = x.shape
+    dev = x.device
+    assert ubm.invcov.ndim == 2 and ubm.mu.shape == ubm.invcov.shape, "a diagonal mixture has (C, D) means and inverse covariances"
+    assert D == ubm.dim(), 'dimension of ubm and features differ: {:d} / {:d}'.format(ubm.dim(), D)
+    C = ubm.mu.shape[0]
+    mus = _device_f64(torch, models, dev)
+    assert mus.dim() in (2, 3) and mus.shape[0] > 0 and mus[0].numel() == C * D, "models: (M, C D) or (M, C, D) means of the mixture's shape"
+    mus = mus.reshape(mus.shape[0], C, D)
+    M = mus.shape[0]
+    off = _offsets(seg_off, N)
+    S, lens = off.shape[0] - 1, numpy.diff(off)
+    invcov = _device_f64(torch, ubm.invcov, dev)
+    B = _device_f64(torch, -2.0 * (numpy.log(ubm.w) + numpy.log(ubm.cst)), dev)
+    d_off = torch.as_tensor(off.astype(numpy.int32)).to(dev)
+    d_mask = None
+    if mask is not None:
+        d_mask = (mask.to(dev) if torch.is_tensor(mask) else torch.as_tensor(numpy.ascontiguousarray(mask)).to(dev)).ne(0).to(torch.uint8).contiguous()
+        assert d_mask.shape == (M, S), "mask: one entry per model and segment"
+    llk = torch.zeros((M, S), dtype=torch.float64, device=dev)
+    longest = int(lens.max())
+    slabs = mixture._slabs(longest)
+    per_model = 8 * (C + (slabs * S if slabs > 1 else 0))         # A and the slab partials of one model
+    step = int(min(MAX_MODELS, max(1, max_workspace_bytes // per_model)))
+    for a in range(0, M, step):
+        b = min(M, a + step)
+        _lib.launch("sc_gmm_score_models", dev, x, dt, N, D, mus[a:b], b - a, invcov, B, C, d_off, S, longest,
+                    None if d_mask is None else d_mask[a:b], llk[a:b])
+    d_lens = torch.as_tensor(lens).to(dev)
+    return (llk.cpu().numpy(), lens) if host else (llk, d_lens)
+
+
+def gmm_llr_device(ubm, models, frames, seg_off=None, mask=None, max_workspace_bytes=1 << 30):
+    """``llr[m, s] = mean_n log p(x_n | model m) - mean_n log p(x_n | ubm)`` over the frames of segment ``s`` (:96-113).  The UBM's own
+    means are stacked as one more model with every trial, so both terms come from the same code and a model equal to the UBM scores
+    exactly 0.  Entries outside ``mask`` are 0; a trial on an empty segment is ``nan`` (the reference's mean of nothing).  Arguments and
+    placement of the result as ``gmm_llk_device``."""
+    if ubm.invcov.ndim == 3:
+        raise mixture._full_covariance()
+    torch = mixture._torch()
+    x, dt, host = mixture._frames(torch, frames)
+    dev = x.device
+    C, D = ubm.mu.shape
+    mus = _device_f64(torch, models, dev)
+    mus = mus.reshape(mus.shape[0], C * D)
+    M = mus.shape[0]
+    stacked = torch.cat((mus, _device_f64(torch, ubm.mu, dev).reshape(1, C * D)))
+    d_mask = None
+    if mask is not None:
+        d_mask = (mask.to(dev) if torch.is_tensor(mask) else torch.as_tensor(numpy.ascontiguousarray(mask)).to(dev)).ne(0)
+        assert d_mask.dim() == 2 and d_mask.shape[0] == M, "mask: one entry per model and segment"
+        stacked_mask = torch.cat((d_mask, torch.ones((1, d_mask.shape[1]), dtype=torch.bool, device=dev)))
+    llk, lens = gmm_llk_device(ubm, stacked, x, seg_off, None if mask is None else stacked_mask, max_workspace_bytes)
+    mean = llk / lens.to(torch.float64)          # 0 / 0 = nan for an empty segment
+    llr = mean[:M] - mean[M]
+    if d_mask is not None:
+        llr = torch.where(d_mask, llr, torch.zeros_like(llr))
+    return llr.cpu().numpy() if host else llr
+
+
+def map_adapt_device(stat0, stat1, ubm, r=16, multisession_index=None):
+    """MAP adaptation of the UBM's means (``statserver.py:1075-1157``) from statistics that are on the device (``gmm_stats_device``):
+    ``stat0`` (S, C), ``stat1`` (S, C, D) or (S, C D) float64 CUDA tensors.  ``multisession_index=None``: one model per row, the
+    single-session form (float32 ``eps`` added to ``stat0`` inside ``alpha``); otherwise one label per row (or a ``ClassIndex``): the
+    statistics of the rows of a label are added first (``sc_class_sums``: rows of a class in row order), one model per sorted unique
+    label, the multi-session form (no ``eps``).  ``0 / 0`` is 0.  Returns the (models, C, D) float64 means on the device."""
+    torch = mixture._torch()
+    assert torch.is_tensor(stat0) and torch.is_tensor(stat1) and stat0.is_cuda and stat1.is_cuda, "statistics on the device"
+    if ubm.invcov.ndim == 3:
+        raise mixture._full_covariance()
+    C, D = ubm.mu.shape
+    dev = stat0.device
+    s0 = stat0.to(torch.float64).reshape(-1, C)
+    s1 = stat1.to(torch.float64).reshape(s0.shape[0], C * D)
+    if multisession_index is None:
+        eps = float(numpy.finfo(numpy.float32).eps)
+        alpha = (s0 + eps) / (s0 + eps + r)
+    else:
+        from .factor_analyser import class_sums_device
+        s0, s1 = class_sums_device(s0.contiguous(), multisession_index)[0], class_sums_device(s1.contiguous(), multisession_index)[0]
+        alpha = s0 / (s0 + r)
+    s1 = s1.reshape(-1, C, D)
+    mean = s1 / s0[:, :, None]
+    mean = torch.where(torch.isnan(mean), torch.zeros_like(mean), mean)
+    alpha = alpha[:, :, None]
+    return alpha * mean + (1 - alpha) * _device_f64(torch, ubm.mu, dev)[None]
+
+
+def _check_types(ubm, enroll, ndx):
+    assert isinstance(ubm, Mixture), 'First parameter should be a Mixture'
+    assert isinstance(enroll, StatServer), 'Second parameter should be a StatServer'
+    assert isinstance(ndx, Ndx), 'Third parameter should be a Ndx'
+
+
+def gmm_scoring_singleThread(ubm, enroll, ndx, feature_server, score_mat, seg_idx=None):
+    """The trials of the test segments ``seg_idx`` of ``ndx`` (all when ``None``) into ``score_mat`` (models of ``ndx`` x segments of
+    ``ndx``), :53-116.  ``enroll.stat1`` holds the mean super-vectors, ``feature_server`` is any object whose ``load(show)[0]`` is the
+    (frames, D) array of a show.  Segments are loaded in batches of at most ``SCORING_BYTES`` of frames, stacked, and a batch is one
+    ``gmm_llr_device`` call under the trial mask.  Scores are placed by model name (a name enrolled twice: its last row, as the
+    reference's dictionary has it); a model of ``ndx`` that is not enrolled keeps what ``score_mat`` holds."""
+    _check_types(ubm, enroll, ndx)
+    if ubm.invcov.ndim == 3:
+        raise mixture._full_covariance()
+    if seg_idx is None:
+        seg_idx = range(ndx.segset.shape[0])
+    seg_idx = [int(t) for t in seg_idx]
+    enrolled = {name: i for i, name in enumerate(enroll.modelset)}
+    rows = numpy.array([i for i, name in enumerate(ndx.modelset) if name in enrolled], dtype=numpy.int64)
+    if rows.shape[0] == 0 or not seg_idx:
+        return
+    torch = mixture._torch()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    models = _device_f64(torch, enroll.stat1[[enrolled[name] for name in ndx.modelset[rows]], :], dev)
+
+    def score(batch):
+        cols = numpy.array([t for t, _ in batch], dtype=numpy.int64)
+        off = numpy.concatenate(([0], numpy.cumsum([f.shape[0] for _, f in batch])))
+        mask = ndx.trialmask[rows][:, cols]
+        if off[-1] == 0:
+            llr = numpy.full(mask.shape, numpy.nan)
+        else:
+            llr = gmm_llr_device(ubm, models, numpy.concatenate([f for _, f in batch]), off, mask, SCORING_BYTES)
+        block = score_mat[numpy.ix_(rows, cols)]
+        block[mask] = llr[mask]
+        score_mat[numpy.ix_(rows, cols)] = block
+
+    batch, held = [], 0
+    for ts in seg_idx:
+        logging.info('Compute trials involving test segment %d/%d', ts + 1, ndx.segset.shape[0])
+        cep = numpy.asarray(feature_server.load(ndx.segset[ts])[0])
+        batch.append((ts, cep))
+        held += cep.nbytes
+        if held >= SCORING_BYTES:
+            score(batch)
+            batch, held = [], 0
+    if batch:
+        score(batch)
+
+
+def gmm_scoring(ubm, enroll, ndx, feature_server, num_thread=1):
+    """Log-likelihood ratios of the trials of ``ndx`` between the models of ``enroll`` (``stat1``: mean super-vectors of models that
+    differ from ``ubm`` in their means only) and ``ubm`` (:119-177) -> ``Scores`` with the models and segments of ``ndx`` that can be
+    scored (models that are enrolled), ``scoremask`` = the trial mask and 0 where there is no trial.  ``feature_server``: any object
+    whose ``load(show)[0]`` is the frames of a show; ``num_thread`` is accepted and unused."""
+    _check_types(ubm, enroll, ndx)
+    if ubm.invcov.ndim == 3:
+        raise mixture._full_covariance()
+    clean_ndx = ndx.filter(enroll.modelset, ndx.segset, True)
+    s = numpy.zeros(clean_ndx.trialmask.shape)
+    gmm_scoring_singleThread(ubm, enroll, clean_ndx, feature_server, s)
+    score = Scores()
+    score.scoremat = s
+    score.modelset = clean_ndx.modelset
+    score.segset = clean_ndx.segset
+    score.scoremask = clean_ndx.trialmask
+    return score

@@ -7,7 +7,9 @@ the ~10 methods the x-vector scoring path calls: ``validate`` (:318-336), ``alig
 back-end normalisations of x-vectors, which run on the GPU through ``sidekit_amd.backend`` (``get_within_covariance_stat1`` ...
 ``get_wccn_choleski_stat1`` :940-1054, ``whiten_cholesky_stat1`` :898-918, spectral normalisation :1279-1333).  ``accumulate_stat`` (:687-739) computes the Baum-Welch
 statistics of a diagonal ``Mixture`` on the GPU (``sidekit_amd.mixture``), which ``FactorAnalyser.total_variability`` /
-``extract_ivectors`` consume (``sidekit_amd.factor_analyser``); MAP adaptation is out of scope; ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
+``extract_ivectors`` consume (``sidekit_amd.factor_analyser``); ``adapt_mean_map`` / ``adapt_mean_map_multisession`` (:1075-1157) adapt the UBM's
+means to each session or model on the host (element-wise work on ``sessions x C D`` numbers; ``sidekit_amd.gmm_scoring.map_adapt_device`` does the
+same on resident statistics) for ``sidekit_amd.gmm_scoring``; ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
 (``STAT_TYPE``, ``sidekit/__init__.py:59``); the alignments use hashed lookups instead of per-id scans.
 """
 import copy
@@ -246,6 +248,54 @@ class StatServer:
                                                   max_workspace_bytes=self.ACCUMULATE_BYTES)
             self.stat0[rows, :] = stat0
             self.stat1[rows, :] = stat1.reshape(len(rows), ubm.sv_size())
+
+    # ---- MAP adaptation of the UBM's means (host: element-wise on sessions x C D numbers) ------------------------------------------------
+
+    @staticmethod
+    def _map_means(stat0, stat1, alpha, ubm, norm):
+        """``alpha m + (1 - alpha) mu_ubm`` per distribution with ``m = stat1 / stat0`` (0 where the occupation is 0); ``norm`` scales
+        by ``sqrt(w invcov)`` of a diagonal UBM (the KL-divergence normalisation of the super-vector kernel)"""
+        per_coefficient = numpy.repeat(numpy.arange(ubm.distrib_nb()), ubm.dim())
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            mean = stat1 / stat0[:, per_coefficient]
+        mean[numpy.isnan(mean)] = 0
+        weight = alpha[:, per_coefficient]
+        mean = weight * mean + (1 - weight) * ubm.get_mean_super_vector()[numpy.newaxis, :]
+        if norm:
+            if ubm.invcov.ndim != 2:
+                from .mixture import _full_covariance
+                raise _full_covariance()
+            mean = mean * numpy.sqrt(numpy.repeat(ubm.w, ubm.dim()) * ubm.get_invcov_super_vector())
+        return mean.astype(STAT_TYPE)
+
+    def adapt_mean_map(self, ubm, r=16, norm=False):
+        """MAP adaptation of the UBM's mean super-vector with relevance factor ``r``, one model per session (``statserver.py:1075-1113``)
+        -> a ``StatServer`` with the sessions of this one, ``stat0 = 1`` and the adapted super-vectors as ``stat1``.  As in the
+        reference, float32 ``eps`` is added to the occupations inside ``alpha`` (not in the means), so a distribution without
+        occupation gets ``1 - eps / (eps + r)`` of the UBM's mean."""
+        out = StatServer()
+        out.modelset, out.segset, out.start, out.stop = self.modelset, self.segset, self.start, self.stop
+        out.stat0 = numpy.ones((self.segset.shape[0], 1), dtype=STAT_TYPE)
+        eps = numpy.finfo(numpy.float32).eps
+        alpha = (self.stat0 + eps) / (self.stat0 + eps + r)
+        out.stat1 = self._map_means(self.stat0, self.stat1, alpha, ubm, norm)
+        out.validate()
+        return out
+
+    def adapt_mean_map_multisession(self, ubm, r=16, norm=False):
+        """MAP adaptation, one model per model id from the summed statistics of its sessions (``statserver.py:1115-1157``) -> a
+        ``StatServer`` with ``modelset = segset =`` the sorted unique model ids, ``stat0 = 1`` and the adapted super-vectors as ``stat1``
+        (no ``eps`` in this form, as in the reference)."""
+        summed = self.sum_stat_per_model()[0]
+        out = StatServer()
+        out.modelset = numpy.unique(self.modelset)
+        out.segset = numpy.unique(self.modelset)
+        out.start = numpy.empty(out.modelset.shape, dtype="|O")
+        out.stop = numpy.empty(out.modelset.shape, dtype="|O")
+        out.stat0 = numpy.ones((out.modelset.shape[0], 1), dtype=STAT_TYPE)
+        out.stat1 = self._map_means(summed.stat0, summed.stat1, summed.stat0 / (summed.stat0 + r), ubm, norm)
+        out.validate()
+        return out
 
     # ---- back-end normalisation on the GPU (sidekit_amd/backend.py): stat1 is uploaded once per call, no CPU fallback ----------------
 
