@@ -121,6 +121,15 @@ IVECTOR_SIGNATURES = {
     "sc_tv_posterior": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/features.h (sidekit_amd/features_server.py)
+FEATURES_SIGNATURES = {
+    "sc_feat_rasta": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _P, _I64, _P]),
+    "sc_feat_delta": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _I64, _P]),
+    "sc_feat_moments": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P]),
+    "sc_feat_norm": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
+}
+SC_FEAT_CENTER, SC_FEAT_CENTER_REDUCE, SC_FEAT_SLIDING_CENTER, SC_FEAT_SLIDING_CENTER_REDUCE, SC_FEAT_WARP = 0, 1, 2, 3, 4
+
 _lib = None
 
 
@@ -138,7 +147,7 @@ def lib():
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     cdll = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()) + list(MIXTURE_SIGNATURES.items())
-                              + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items())):
+                              + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
