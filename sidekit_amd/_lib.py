@@ -130,6 +130,12 @@ FEATURES_SIGNATURES = {
 }
 SC_FEAT_CENTER, SC_FEAT_CENTER_REDUCE, SC_FEAT_SLIDING_CENTER, SC_FEAT_SLIDING_CENTER_REDUCE, SC_FEAT_WARP = 0, 1, 2, 3, 4
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/cepstrum.h (sidekit_amd/features_extractor.py)
+CEPSTRUM_SIGNATURES = {
+    "sc_mfcc": (ctypes.c_int, [_P, _I32, _I64, _F64, _P, _P, _I32, _I64, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _I32, _P, _I32, _P, _I64, _P, _I64, _P]),
+}
+SC_MFCC_MAX_FILT = 128
+
 _lib = None
 
 
@@ -147,7 +153,8 @@ def lib():
         ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
     cdll = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()) + list(MIXTURE_SIGNATURES.items())
-                              + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())):
+                              + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())
+                              + list(CEPSTRUM_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,9 +1,142 @@
-"""``sidekit.frontend.features``: the part of the reference's module the feature post-processing needs, ``compute_delta``
-(``sidekit/frontend/features.py:133-166``), computed on the GPU (``sc_feat_delta``).  The reference's numpy MFCC / PLP extraction is not
+"""``sidekit.frontend.features``: ``compute_delta`` (``sidekit/frontend/features.py:133-166``, ``sc_feat_delta``) and the cepstral front
+end -- ``mfcc`` and ``power_spectrum`` (:363-477) computed on the GPU (``sc_mfcc``, csrc/cepstrum.hip) from the host-made tables of the
+reference: ``trfbank`` (:226-305), the symmetric Hann window and the orthonormal DCT-II basis.  The reference's PLP extraction is not
 built.  There is no CPU fallback; importing the module needs neither a GPU nor torch."""
 import numpy
 
 from .. import PARAM_TYPE
+
+
+def hz2mel(f, htk=True):
+    """Hertz -> mel, the HTK formula (the reference's default; Slaney's scale is not built)"""
+    if not htk:
+        raise NotImplementedError("hz2mel: htk=False (Slaney's mel scale) is not built")
+    return 2595 * numpy.log10(1 + f / 700.)
+
+
+def mel2hz(z, htk=True):
+    """mel -> Hertz, the HTK formula"""
+    if not htk:
+        raise NotImplementedError("mel2hz: htk=False (Slaney's mel scale) is not built")
+    return 700. * (10**(z / 2595.) - 1)
+
+
+def _band_edges(lowfreq, maxfreq, nlinfilt, nlogfilt, midfreq):
+    """The nfilt + 2 edge frequencies of the triangles -> ``(edges, nlinfilt, nlogfilt)``.  The precision of every step is the
+    reference's: float32 edges for the linear and the mixed bank, float64 ones for the mel bank."""
+    nfilt = nlinfilt + nlogfilt
+    if nlogfilt == 0:
+        edges = numpy.zeros(nfilt + 2, dtype=PARAM_TYPE)
+        step = (maxfreq - lowfreq) / (nlinfilt + 1)
+        edges[:] = lowfreq + numpy.arange(nlinfilt + 2) * step
+        return edges
+    if nlinfilt == 0:
+        mel_lo, mel_hi = hz2mel(lowfreq), hz2mel(maxfreq)
+        step = (mel_hi - mel_lo) / (nfilt + 1)
+        return mel2hz(mel_lo + numpy.arange(nlogfilt + 2) * step)
+    # linear triangles below midfreq, mel-spaced ones above; a linear one is added while the first mel step is narrower than the linear step
+    edges = numpy.zeros(nfilt + 2, dtype=PARAM_TYPE)
+    step = (min([midfreq, maxfreq]) - lowfreq) / (nlinfilt + 1)
+    edges[:nlinfilt] = lowfreq + numpy.arange(nlinfilt) * step
+    mel_lo, mel_hi = hz2mel(min([1000, maxfreq])), hz2mel(maxfreq)
+    mel_step = (mel_hi - mel_lo) / (nlogfilt + 1)
+    while mel2hz(mel_step) < step:
+        nlinfilt, nlogfilt = nlinfilt + 1, nlogfilt - 1
+        edges[:nlinfilt] = lowfreq + numpy.arange(nlinfilt) * step
+        mel_lo = hz2mel(edges[nlinfilt - 1] + 2 * step)
+        mel_step = (mel_hi - mel_lo) / (nlogfilt + 1)
+    mels = numpy.zeros(nlogfilt + 2, dtype=PARAM_TYPE)
+    mels[:] = mel_lo + numpy.arange(nlogfilt + 2) * mel_step
+    edges[nlinfilt:] = mel2hz(mels)
+    return edges
+
+
+def trfbank(fs, nfft, lowfreq, maxfreq, nlinfilt, nlogfilt, midfreq=1000):
+    """The triangular filter bank of the cepstral front end -> ``(fbank float32 (nfilt, nfft // 2 + 1), frequences)``: ``nlinfilt``
+    linearly spaced triangles, ``nlogfilt`` mel-spaced ones, or both (linear below ``midfreq``), each of height
+    ``2 / (upper edge - lower edge)``.  As in the reference the rising side covers the bins above the lower edge up to the centre's bin,
+    and the falling side stops one bin short of the upper edge's bin."""
+    nfilt = nlinfilt + nlogfilt
+    frequences = _band_edges(lowfreq, maxfreq, nlinfilt, nlogfilt, midfreq)
+    bank = numpy.zeros((nfilt, nfft // 2 + 1), dtype=PARAM_TYPE)
+    bin_hz = numpy.arange(nfft) / (1. * nfft) * fs
+    widths = frequences[2:] - frequences[:-2]
+    peaks = 2. / widths               # as arrays: the division stays in the precision of the edges
+    for i, (low, cen, hi) in enumerate(zip(frequences[:-2], frequences[1:-1], frequences[2:])):
+        height = peaks[i]
+        first, peak, last = (numpy.floor(edge * nfft / fs) + 1 for edge in (low, cen, hi))
+        rising = numpy.arange(first, peak, dtype=int)
+        falling = numpy.arange(peak, min(last, nfft), dtype=int)[:-1]
+        bank[i][rising] = height / (cen - low) * (bin_hz[rising] - low)
+        bank[i][falling] = height / (hi - cen) * (hi - bin_hz[falling])
+    return bank, frequences
+
+
+def dct_basis(nbasis, length):
+    """The first ``nbasis`` rows of the orthonormal DCT-II basis of ``length`` points (what the reference takes from
+    ``scipy.fftpack.idct(numpy.eye(nbasis, length), norm='ortho')``), float64"""
+    # cos(pi k / (2 length)), k = row * (2 column + 1), with k folded into the first quadrant as an integer: the zeros are exact
+    k = (numpy.arange(nbasis)[:, None] * (2 * numpy.arange(length)[None, :] + 1)) % (4 * length)
+    k = numpy.where(k > 2 * length, 4 * length - k, k)
+    sign = numpy.where(k > length, -1.0, 1.0)
+    k = numpy.where(k > length, 2 * length - k, k)
+    basis = numpy.sqrt(2. / length) * sign * numpy.where(k == length, 0.0, numpy.cos(numpy.pi * k / (2 * length)))
+    basis[:1] *= numpy.sqrt(0.5)
+    return basis
+
+
+def hann_window(length):
+    """The symmetric Hann window ``power_spectrum`` applies (``numpy.hanning``), float32 as the kernel holds it"""
+    return numpy.hanning(length).astype(PARAM_TYPE)
+
+
+def frame_shape(fs, win_time, shift):
+    """-> ``(window_length, shift in samples, n_fft)`` as ``power_spectrum`` derives them"""
+    window_length = int(round(win_time * fs))
+    return window_length, int(shift * fs), 2 ** int(numpy.ceil(numpy.log2(window_length)))
+
+
+def _signal(input_sig):
+    sig = numpy.asarray(input_sig)
+    if sig.ndim != 1:
+        raise ValueError("expected a one-dimensional signal, got shape {}".format(sig.shape))
+    return numpy.ascontiguousarray(sig if sig.dtype == numpy.int16 else sig.astype(numpy.float32))
+
+
+def power_spectrum(input_sig,
+                   fs=8000,
+                   win_time=0.025,
+                   shift=0.01,
+                   prefac=0.97):
+    """-> ``(spec float32 (frames, n_fft / 2 + 1), log_energy float32 (frames,))`` of a signal at the int16 scale: frames of
+    ``round(win_time * fs)`` samples every ``int(shift * fs)``, pre-emphasised inside the frame, the log-energy of the unwindowed frame,
+    the power spectrum of the Hann-windowed one.  Unlike the reference a signal of exactly one window gives one row."""
+    from ..features_extractor import mfcc_device, to_device
+    wav, nsamples = to_device(_signal(input_sig))
+    frames, _, spec = mfcc_device(wav, nsamples, fs=fs, lowfreq=0, maxfreq=fs / 2, nlinfilt=2, nlogfilt=0, nwin=win_time, nceps=1, shift=shift,
+                                  prefac=prefac, get_spec=True)
+    return spec.cpu().numpy().astype(PARAM_TYPE), frames[:, 0].cpu().numpy().astype(PARAM_TYPE)
+
+
+def mfcc(input_sig,
+         lowfreq=100, maxfreq=8000,
+         nlinfilt=0, nlogfilt=24,
+         nwin=0.025,
+         fs=16000,
+         nceps=13,
+         shift=0.01,
+         get_spec=False,
+         get_mspec=False,
+         prefac=0.97):
+    """-> ``[ceps (frames, nceps), log_energy (frames,), spec or None, mspec or None]``, float32: the cepstra 1 .. nceps of the log outputs
+    of the ``trfbank`` triangles on ``power_spectrum``, the log-energy, and on request the power spectrum and the log filter-bank outputs."""
+    from ..features_extractor import mfcc_device, to_device
+    wav, nsamples = to_device(_signal(input_sig))
+    got = mfcc_device(wav, nsamples, fs=fs, lowfreq=lowfreq, maxfreq=maxfreq, nlinfilt=nlinfilt, nlogfilt=nlogfilt, nwin=nwin, nceps=nceps,
+                      shift=shift, prefac=prefac, get_spec=get_spec)
+    frames = got[0].cpu().numpy().astype(PARAM_TYPE)
+    return [frames[:, 1:1 + nceps], frames[:, 0], got[2].cpu().numpy().astype(PARAM_TYPE) if get_spec else None,
+            frames[:, 1 + nceps:] if get_mspec else None]
 
 
 def compute_delta(features, win=3, method='filter', filt=numpy.array([.25, .5, .25, 0, -.25, -.5, -.25])):
