@@ -121,6 +121,12 @@ IVECTOR_SIGNATURES = {
     "sc_tv_posterior": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/jfa.h (sidekit_amd/jfa_scoring.py)
+JFA_SIGNATURES = {
+    "sc_jfa_shift": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "sc_jfa_map_acc": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+}
+
 # name -> (restype, argtypes); every symbol of include/sidekit_amd/features.h (sidekit_amd/features_server.py)
 FEATURES_SIGNATURES = {
     "sc_feat_rasta": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _P, _I64, _P]),
@@ -154,7 +160,7 @@ def lib():
     cdll = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()) + list(MIXTURE_SIGNATURES.items())
                               + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())
-                              + list(CEPSTRUM_SIGNATURES.items())):
+                              + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -7,7 +7,7 @@ cores, the model-independent half of the exponent computed once per group of mod
 The ``*_device`` functions work on resident frames (float32 or float64, widened in the load) and resident models, and
 ``map_adapt_device`` adapts the means from resident statistics (``gmm_stats_device``), so the path from statistics to adapted models to
 scores never leaves the device.  The UBM is scored as one more model by the same code, so a model equal to the UBM scores exactly 0.
-Full covariances raise ``NotImplementedError``; top-C (fast) scoring and ``jfa_scoring`` are not built.  There is no CPU fallback;
+Full covariances raise ``NotImplementedError``; top-C (fast) scoring is not built; ``jfa_scoring`` is ``sidekit_amd.jfa_scoring``.  There is no CPU fallback;
 importing the module needs neither a GPU nor torch.
 """
 import logging

@@ -9,7 +9,9 @@ back-end normalisations of x-vectors, which run on the GPU through ``sidekit_amd
 statistics of a diagonal ``Mixture`` on the GPU (``sidekit_amd.mixture``), which ``FactorAnalyser.total_variability`` /
 ``extract_ivectors`` consume (``sidekit_amd.factor_analyser``); ``adapt_mean_map`` / ``adapt_mean_map_multisession`` (:1075-1157) adapt the UBM's
 means to each session or model on the host (element-wise work on ``sessions x C D`` numbers; ``sidekit_amd.gmm_scoring.map_adapt_device`` does the
-same on resident statistics) for ``sidekit_amd.gmm_scoring``; ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
+same on resident statistics) for ``sidekit_amd.gmm_scoring``; ``factor_analysis`` with ``estimate_between_class`` / ``estimate_within_class`` /
+``estimate_map`` / ``estimate_hidden`` / ``subtract_weighted_stat1`` (:819-850, :1494-1949) train the joint factor analysis model on the GPU
+(``sidekit_amd.jfa_scoring``); ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
 (``STAT_TYPE``, ``sidekit/__init__.py:59``); the alignments use hashed lookups instead of per-id scans.
 """
 import copy
@@ -396,6 +398,74 @@ class StatServer:
             out.stat0[idx, :] = self.stat0[sel, :].mean(axis=0)
             out.stat1[idx, :] = self.stat1[sel, :].mean(axis=0)
         return out
+
+    # ---- joint factor analysis on the GPU (sidekit_amd/jfa_scoring.py): no CPU fallback; the caller's statistics are left as they are ---------
+
+    def subtract_weighted_stat1(self, sts):
+        """A copy of this server whose ``stat1`` is ``stat1 - stat0[:, index_map] * sts.stat1``, the sessions of ``sts`` matched to these by
+        sorted ``segset`` (``statserver.py:819-850``).  Any mismatch of the model sets, the segment sets or the shapes raises."""
+        if not (self.modelset.shape == sts.modelset.shape and self.segset.shape == sts.segset.shape
+                and all(numpy.sort(sts.modelset) == numpy.sort(self.modelset)) and all(numpy.sort(sts.segset) == numpy.sort(self.segset))
+                and sts.stat0.shape == self.stat0.shape and sts.stat1.shape == self.stat1.shape):
+            raise Exception('Statserver are not compatible')
+        new_sts = copy.deepcopy(self)
+        aligned = numpy.empty(self.stat1.shape, dtype=STAT_TYPE)
+        aligned[self.segset.argsort(), :] = sts.stat1[sts.segset.argsort(), :]
+        n, n_distrib = self.stat0.shape
+        new_sts.stat1 = (self._blocks() - self.stat0[:, :, numpy.newaxis] * aligned.reshape(n, n_distrib, -1)).reshape(self.stat1.shape)
+        return new_sts
+
+    def estimate_between_class(self, itNb, V, mean, sigma_obs, batch_size=100, Ux=None, Dz=None, minDiv=True, num_thread=1,
+                               re_estimate_residual=False, save_partial=False):
+        """``itNb`` EM iterations of the eigenvoice matrix ``V`` from the statistics (less ``stat0 * Ux`` when given) summed per model
+        (``statserver.py:1494-1567``) -> ``(V, sigma_obs)``.  ``Dz`` is refused: the reference calls a ``subtract`` it does not have.
+        ``batch_size`` and ``num_thread`` are accepted and unused."""
+        from . import jfa_scoring
+        jfa_scoring._refuse(save_partial, re_estimate_residual)
+        if Dz is not None:
+            raise NotImplementedError("estimate_between_class with Dz is not built (the reference's own call fails: StatServer has no subtract)")
+        shifted = self if Ux is None else self.subtract_weighted_stat1(Ux)
+        return jfa_scoring.server_estimate_subspace(shifted, itNb, V, mean, sigma_obs, minDiv, per_model=True), sigma_obs
+
+    def estimate_within_class(self, it_nb, U, mean, sigma_obs, batch_size=100, Vy=None, Dz=None, min_div=True, num_thread=1, save_partial=False):
+        """``it_nb`` EM iterations of the eigenchannel matrix ``U`` from the sessions less ``stat0 * Vy`` and ``stat0 * Dz`` when given
+        (``statserver.py:1569-1628``) -> ``U``.  ``batch_size`` and ``num_thread`` are accepted and unused."""
+        from . import jfa_scoring
+        jfa_scoring._refuse(save_partial)
+        shifted = self
+        for shift in (Vy, Dz):
+            if shift is not None:
+                shifted = shifted.subtract_weighted_stat1(shift)
+        return jfa_scoring.server_estimate_subspace(shifted, it_nb, U, mean, sigma_obs, min_div, per_model=False)
+
+    def estimate_map(self, itNb, D, mean, Sigma, Vy=None, Ux=None, num_thread=1, save_partial=False):
+        """``itNb`` EM iterations of the diagonal MAP term ``D`` from the statistics centred on ``mean``, less ``stat0 * Vy`` and
+        ``stat0 * Ux`` when given, summed per model (``statserver.py:1630-1685``) -> ``D``.  ``num_thread`` is accepted and unused."""
+        from . import jfa_scoring
+        jfa_scoring._refuse(save_partial)
+        shifted = self
+        for shift in (Vy, Ux):
+            if shift is not None:
+                shifted = shifted.subtract_weighted_stat1(shift)
+        return jfa_scoring.server_estimate_map(shifted, itNb, D, mean, Sigma)
+
+    def estimate_hidden(self, mean, sigma, V=None, U=None, D=None, batch_size=100, num_thread=1):
+        """Point estimates ``(y, x, z)`` of the hidden variables of every session under ``M = mean + V y + U x + D z``, ``(y, x)`` jointly
+        (``statserver.py:1687-1796``) -> three ``StatServer`` objects (``z`` is an empty one without ``D``).  The statistics are not
+        whitened by the caller and, unlike in the reference, not whitened here either.  ``batch_size`` and ``num_thread`` are accepted
+        and unused."""
+        from . import jfa_scoring
+        return jfa_scoring.server_estimate_hidden(self, mean, sigma, V, U, D)
+
+    def factor_analysis(self, rank_f, rank_g=0, rank_h=None, re_estimate_residual=False, it_nb=(10, 10, 10), min_div=True, ubm=None,
+                        batch_size=100, num_thread=1, save_partial=False, init_matrices=(None, None, None)):
+        """Train the JFA model ``(mean, F, G, H, sigma)`` on these statistics with ``ubm`` as the origin (``statserver.py:1798-1949``;
+        ``sidekit_amd.jfa_scoring.factor_analysis_device``).  ``ubm=None``, ``re_estimate_residual`` and ``save_partial`` are refused;
+        ``batch_size`` and ``num_thread`` are accepted and unused."""
+        from . import jfa_scoring
+        if ubm is not None:
+            jfa_scoring._refuse(save_partial, re_estimate_residual)
+        return jfa_scoring.server_factor_analysis(self, rank_f, rank_g, rank_h, it_nb, min_div, ubm, init_matrices)
 
     @staticmethod
     def from_arrays(modelset, segset, stat1, start=None, stop=None):
