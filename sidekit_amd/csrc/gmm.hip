@@ -3,8 +3,12 @@
 //   sc_gmm_frame_loglik   pass A: lse[n] = log sum_c exp lp[n][c] (and lp itself on request)
 //   sc_gmm_stats          pass B: per segment, stat0 / stat1 / stat2 = pp' . [1, X, X^2] with pp = exp(lp - lse), and the sum of lse
 // Both form lp = -0.5 ([X^2, X] . [invcov, -2 mu invcov]' + A) tile by tile on v_mfma_f64_16x16x4_f64 (one GEMM with K = 2 D), by the
-// same function in the same order, so pass B recomputes the bits pass A saw.  Recomputing costs 4 C D of the 12 C D FLOP per frame;
-// storing lp would cost N C 8 bytes.  float64 throughout, no floating-point atomics, every sum in a fixed order.
+// same function in the same order (gmm_lp_tile), so pass B recomputes the bits pass A saw.  Recomputing costs 4 C D of the 12 C D FLOP
+// per frame; storing lp would cost N C 8 bytes.  float64 throughout, no floating-point atomics, every sum in a fixed order.
+// gmm_tile.h holds what this file shares with gmm_score.hip, one copy each: the frame load, a segment's rows and slabs (the one place
+// seg_off is read), the log-sum-exp update and merge, the argument checks.  The chunk loop of gmm_lp_tile and the join of a tile's frames
+// at the end of pass A exist a second time in gmm_score.hip, by copy: as shared functions they cost the scoring kernel 0.5 - 1.1 % (DESIGN
+// section 4 "GMM-UBM scoring"), so a change to either is made in both files.
 //
 // One workgroup = 256 threads = 4 waves works on a tile of GT = 64 frames x 64 components; wave w owns components 16 w .. 16 w + 15 of
 // the tile and all 64 frames (four 16 x 16 MFMA tiles, 16 accumulator doubles per lane).  LDS per workgroup, in doubles:
@@ -73,8 +77,8 @@ __device__ inline void gmm_lp_tile(const double* Xs, int xld, double* Gs, const 
 
 // ---- pass A ------------------------------------------------------------------------------------------------------------------------
 // grid: x = frame tile.  The workgroup walks the component tiles in ascending order; a lane keeps an online log-sum-exp state for each of
-// its 16 frames over the components it sees (c = lane & 15 + 16 wave mod 64), then the 16 lanes of a frame are joined by a butterfly
-// (every lane ends with the same state), the four waves through LDS in wave order.  The order depends on C alone.
+// its 16 frames over the components it sees (c = lane & 15 + 16 wave mod 64; lse_add), then the 16 lanes of a frame are joined by a
+// butterfly (every lane ends with the same state), the four waves through LDS in wave order.  The order depends on C alone.
 // Bounds: frames beyond N are zero rows whose lse is not stored; components beyond C are skipped; lp stores are guarded by both.
 template <typename T>
 __global__ __launch_bounds__(256, 2) void gmm_loglik_kernel(const T* __restrict__ X, long N, int D, const double* __restrict__ mu,
@@ -108,8 +112,7 @@ __global__ __launch_bounds__(256, 2) void gmm_loglik_kernel(const T* __restrict_
           const double v = -0.5 * (acc[i][q] + a);
           const int fr = i * 16 + lk + 4 * q;
           if (lp && fr < nvalid) lp[(f0 + fr) * C + c] = v;
-          if (v > M[i][q]) { S[i][q] = S[i][q] * exp(M[i][q] - v) + 1.0; M[i][q] = v; }
-          else if (v > -INFINITY) S[i][q] += exp(v - M[i][q]);
+          lse_add(M[i][q], S[i][q], v);
         }
     }
   }
@@ -143,8 +146,8 @@ __global__ __launch_bounds__(256, 2) void gmm_loglik_kernel(const T* __restrict_
 // Xs (ncols = 2 D + 1, or D + 1 for order 1; NT 16-column tiles cover it).  The partial goes to part0/1/2 at (slab * S + segment): with one
 // slab per segment these are the outputs themselves, otherwise workspace that slab_reduce joins in slab order.  A slab beyond the
 // segment's own cut (the grid is sized for the longest segment) multiplies nothing and stores zeros.
-// Bounds: offsets are clamped to [0, N] and to each other and the length to max_len; frames beyond the slab's end are zero rows; stores
-// are guarded by c < C and the column's range.
+// Bounds: the slab's rows lie within [0, N] (gmm_segment, gmm_slab); frames beyond the slab's end are zero rows; stores are guarded by
+// c < C and the column's range.
 template <int NT, typename T>
 __global__ __launch_bounds__(256, NT <= 8 ? 2 : 1) void gmm_stats_kernel(const T* __restrict__ X, long N, int D, const double* __restrict__ mu,
                                                                          const double* __restrict__ invcov, const double* __restrict__ A, int C,
@@ -159,14 +162,8 @@ __global__ __launch_bounds__(256, NT <= 8 ? 2 : 1) void gmm_stats_kernel(const T
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, lk = lane >> 4;
   const int seg = blockIdx.x / nslab, slab = blockIdx.x % nslab, c0 = blockIdx.y * GT;
-  long r0 = seg_off[seg], r1 = seg_off[seg + 1];
-  r0 = r0 < 0 ? 0 : (r0 > N ? N : r0);
-  r1 = r1 < r0 ? r0 : (r1 > N ? N : r1);
-  const long len = r1 - r0 < max_len ? r1 - r0 : max_len;
-  const long sl = gmm_slab_len(len);
-  const long k_begin = r0 + slab * sl;
-  long k_end = k_begin + sl;
-  if (k_end > r0 + len) k_end = r0 + len;
+  const GmmRows rows = gmm_slab(gmm_segment(seg_off, seg, N, max_len), slab);
+  const long k_begin = rows.begin, k_end = rows.end;
   f64x4 st[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) st[j] = f64x4{0.0, 0.0, 0.0, 0.0};
@@ -226,12 +223,9 @@ __global__ __launch_bounds__(256) void gmm_seg_llk_kernel(const double* __restri
                                                           double* __restrict__ llk) {
   __shared__ double red[256];
   const int tid = threadIdx.x, seg = blockIdx.x;
-  long r0 = seg_off[seg], r1 = seg_off[seg + 1];
-  r0 = r0 < 0 ? 0 : (r0 > N ? N : r0);
-  r1 = r1 < r0 ? r0 : (r1 > N ? N : r1);
-  const long len = r1 - r0 < max_len ? r1 - r0 : max_len;
+  const GmmRows rows = gmm_segment(seg_off, seg, N, max_len);
   double s = 0.0;
-  for (long i = tid; i < len; i += 256) s += lse[r0 + i];
+  for (long i = rows.begin + tid; i < rows.end; i += 256) s += lse[i];
   red[tid] = s;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -298,15 +292,6 @@ static int launch_gmm_stats(const T* X, long N, int D, const double* mu, const d
   return SK_OK;
 }
 
-static int gmm_check_common(const char* who, const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const double* d_mu, const double* d_invcov,
-                            const double* d_A, int32_t C) {
-  SK_CHECK(d_X && d_mu && d_invcov && d_A, SK_EARG, "%s: null argument", who);
-  SK_CHECK(x_dtype == XT_F32 || x_dtype == XT_F64, SK_EARG, "%s: X must be XT_F32 or XT_F64 (got %d)", who, x_dtype);
-  SK_CHECK(N >= 1 && N <= 0x7fffffffLL && D >= 1 && D <= SC_GMM_MAX_D && C >= 1 && C <= SC_GMM_MAX_C, SK_EARG,
-           "%s: bad sizes (N=%lld, D=%d with at most %d, C=%d with at most %d)", who, (long long)N, D, SC_GMM_MAX_D, C, SC_GMM_MAX_C);
-  return SK_OK;
-}
-
 }  // namespace sk
 
 using namespace sk;
@@ -327,8 +312,7 @@ int sc_gmm_stats(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const d
   SK_TRY(gmm_check_common("sc_gmm_stats", d_X, x_dtype, N, D, d_mu, d_invcov, d_A, C));
   SK_CHECK(order == 1 || order == 2, SK_EARG, "sc_gmm_stats: order must be 1 or 2 (got %d)", order);
   SK_CHECK(d_lse && d_seg_off && d_stat0 && d_stat1 && (order == 1 || d_stat2), SK_EARG, "sc_gmm_stats: null argument");
-  SK_CHECK(S >= 1 && max_len >= 0 && max_len <= N && (long long)S * gmm_slabs(max_len) <= 0x7fffffffLL, SK_EARG,
-           "sc_gmm_stats: bad sizes (S=%d, max_len=%lld, N=%lld)", S, (long long)max_len, (long long)N);
+  SK_TRY(gmm_check_segments("sc_gmm_stats", N, S, max_len));
   if (x_dtype == XT_F32)
     return launch_gmm_stats((const float*)d_X, (long)N, D, d_mu, d_invcov, d_A, C, d_lse, d_seg_off, S, (long)max_len, order, d_stat0, d_stat1, d_stat2,
                             d_llk, (hipStream_t)stream);

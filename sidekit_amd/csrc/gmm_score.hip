@@ -1,6 +1,8 @@
 // GMM-UBM scoring (sidekit/gmm_scoring.py:53-116): the log-likelihood of every test segment under M mean-adapted models of one diagonal
 // mixture, llk[m][s] = sum_n log sum_c exp lp_m[n][c] (include/sidekit_amd/gmm_scoring.h).  The body is pass A of gmm.hip with a model
-// dimension: lp_m = -0.5 ([X^2, X] . [invcov, -2 mu_m invcov]' + A_m) tile by tile on v_mfma_f64_16x16x4_f64.  The squares' half of that
+// dimension; the frame load, the segment and its slab, the log-sum-exp update and merge and the argument checks are gmm_tile.h's, the same
+// functions gmm.hip calls; half_gemm and the join of a tile's frames below are copies of gmm.hip's (gmm_lp_tile's chunk loop, pass A's
+// end), kept identical by hand: lp_m = -0.5 ([X^2, X] . [invcov, -2 mu_m invcov]' + A_m) tile by tile on v_mfma_f64_16x16x4_f64.  The squares' half of that
 // GEMM does not depend on the model, so a workgroup computes it once per component tile for a group of G consecutive models and every
 // model's accumulator starts from it: (1 + G) / 2 G of the FLOP of G separate passes.  float64, no floating-point atomics.
 //
@@ -46,8 +48,8 @@ __host__ __device__ inline size_t gmm_score_lds(int G, int D) {
   return (size_t)(GT * gmm_xld(D) + GT * DLD + 8 * GT + G * GT + (gmm_score_qlds(G) ? 16 * 256 : 0)) * 8;
 }
 
-// Bounds: segment offsets are clamped to [0, N] and to each other and the length to max_len; frames beyond the slab's end are zero rows
-// that are not added; components beyond C are zero operand rows that are skipped in the fold; models beyond M are neither computed nor
+// Bounds: the slab's rows lie within [0, N] (gmm_segment, gmm_slab); frames beyond the slab's end are zero rows that are not added;
+// components beyond C are zero operand rows that are skipped in the fold; models beyond M are neither computed nor
 // stored; mask and part are indexed with m < M and seg < S only.
 template <int G, typename T>
 __global__ __launch_bounds__(256, G <= 2 ? 2 : 1) void gmm_score_kernel(const T* __restrict__ X, long N, int D, const double* __restrict__ mus,
@@ -71,15 +73,10 @@ __global__ __launch_bounds__(256, G <= 2 ? 2 : 1) void gmm_score_kernel(const T*
     for (int j = 0; j < nmod; ++j) any = any || mask[(long)(m0 + j) * S + seg] != 0;
     if (!any) return;
   }
-  long r0 = seg_off[seg], r1 = seg_off[seg + 1];
-  r0 = r0 < 0 ? 0 : (r0 > N ? N : r0);
-  r1 = r1 < r0 ? r0 : (r1 > N ? N : r1);
-  const long len = r1 - r0 < max_len ? r1 - r0 : max_len;
-  if (slab >= gmm_slabs(len)) return;   // the grid is sized for the longest segment
-  const long sl = gmm_slab_len(len);
-  const long k_begin = r0 + slab * sl;
-  long k_end = k_begin + sl;
-  if (k_end > r0 + len) k_end = r0 + len;
+  const GmmRows segment = gmm_segment(seg_off, seg, N, max_len);
+  if (slab >= gmm_slabs(segment.len())) return;   // the grid is sized for the longest segment
+  const GmmRows rows = gmm_slab(segment, slab);
+  const long k_begin = rows.begin, k_end = rows.end;
 
   const int sr = tid >> 2, sd = (tid & 3) * 4;   // staging: component row sr, four consecutive d from sd
   const int nchunk = (D + DK - 1) / DK, nhalf = 1 + nmod;
@@ -176,16 +173,7 @@ __global__ __launch_bounds__(256, G <= 2 ? 2 : 1) void gmm_score_kernel(const T*
 #pragma unroll
           for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const double v = -0.5 * (acc[i][q] + a);
-              // pass A's update (S exp(M - v) + 1 for a new maximum, S + exp(v - M) otherwise) with one exp for both cases: the same bits
-              if (v > -INFINITY) {
-                const bool top = v > Mx[j][i][q];
-                const double e = exp(top ? Mx[j][i][q] - v : v - Mx[j][i][q]);
-                Sx[j][i][q] = top ? Sx[j][i][q] * e + 1.0 : Sx[j][i][q] + e;
-                Mx[j][i][q] = top ? v : Mx[j][i][q];
-              }
-            }
+            for (int q = 0; q < 4; ++q) lse_add(Mx[j][i][q], Sx[j][i][q], -0.5 * (acc[i][q] + a));
         }
       }
     }
@@ -233,11 +221,7 @@ __global__ __launch_bounds__(256) void gmm_score_join_kernel(const double* __res
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= MS || (mask && !mask[i])) return;
   const int seg = (int)(i % S);
-  long r0 = seg_off[seg], r1 = seg_off[seg + 1];
-  r0 = r0 < 0 ? 0 : (r0 > N ? N : r0);
-  r1 = r1 < r0 ? r0 : (r1 > N ? N : r1);
-  const long len = r1 - r0 < max_len ? r1 - r0 : max_len;
-  const long n = gmm_slabs(len);
+  const long n = gmm_slabs(gmm_segment(seg_off, seg, N, max_len).len());   // the slots gmm_score_kernel wrote
   double s = part[i];
   for (long k = 1; k < n; ++k) s += part[k * MS + i];
   llk[i] = s;
@@ -278,13 +262,10 @@ extern "C" {
 int sc_gmm_score_models(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const double* d_mus, int32_t M, const double* d_invcov,
                         const double* d_B, int32_t C, const int32_t* d_seg_off, int32_t S, int64_t max_len, const uint8_t* d_mask, double* d_llk,
                         void* stream) {
-  SK_CHECK(d_X && d_mus && d_invcov && d_B && d_seg_off && d_llk, SK_EARG, "sc_gmm_score_models: null argument");
-  SK_CHECK(x_dtype == XT_F32 || x_dtype == XT_F64, SK_EARG, "sc_gmm_score_models: X must be XT_F32 or XT_F64 (got %d)", x_dtype);
-  SK_CHECK(N >= 1 && N <= 0x7fffffffLL && D >= 1 && D <= SC_GMM_MAX_D && C >= 1 && C <= SC_GMM_MAX_C && M >= 1 && M <= SC_GMM_SCORE_MAX_M, SK_EARG,
-           "sc_gmm_score_models: bad sizes (N=%lld, D=%d with at most %d, C=%d with at most %d, M=%d with at most %d)", (long long)N, D, SC_GMM_MAX_D, C,
-           SC_GMM_MAX_C, M, SC_GMM_SCORE_MAX_M);
-  SK_CHECK(S >= 1 && max_len >= 0 && max_len <= N && (long long)S * gmm_slabs(max_len) <= 0x7fffffffLL, SK_EARG,
-           "sc_gmm_score_models: bad sizes (S=%d, max_len=%lld, N=%lld)", S, (long long)max_len, (long long)N);
+  SK_TRY(gmm_check_common("sc_gmm_score_models", d_X, x_dtype, N, D, d_mus, d_invcov, d_B, C));
+  SK_CHECK(d_seg_off && d_llk, SK_EARG, "sc_gmm_score_models: null argument");
+  SK_CHECK(M >= 1 && M <= SC_GMM_SCORE_MAX_M, SK_EARG, "sc_gmm_score_models: bad sizes (M=%d with at most %d)", M, SC_GMM_SCORE_MAX_M);
+  SK_TRY(gmm_check_segments("sc_gmm_score_models", N, S, max_len));
   if (x_dtype == XT_F32)
     return launch_gmm_score((const float*)d_X, (long)N, D, d_mus, M, d_invcov, d_B, C, d_seg_off, S, (long)max_len, d_mask, d_llk, (hipStream_t)stream);
   return launch_gmm_score((const double*)d_X, (long)N, D, d_mus, M, d_invcov, d_B, C, d_seg_off, S, (long)max_len, d_mask, d_llk, (hipStream_t)stream);

@@ -1,6 +1,6 @@
-// What the diagonal-GMM kernels share (gmm.hip: frame log-likelihoods and statistics; gmm_score.hip: GMM-UBM scoring): the frame tile and
-// its load, the cut of a segment into slabs, and the merge of two log-sum-exp states.  One copy of each, so that both files cut a
-// segment the same way and see the same bits.
+// What the diagonal-GMM kernels share (gmm.hip: frame log-likelihoods and statistics; gmm_score.hip: GMM-UBM scoring), one copy of each:
+// the frame tile and its load; a segment's rows and its cut into slabs (the one place seg_off is read, so a join reads the workspace slots
+// its producer's cut says were written); the online log-sum-exp update and the merge of two states; the argument checks.
 #pragma once
 #include <cmath>
 
@@ -23,6 +23,24 @@ __host__ __device__ inline long gmm_slab_len(long len) {
   return s < GT ? GT : (s + GT - 1) / GT * GT;
 }
 
+struct GmmRows {
+  long begin, end;   // rows [begin, end) of X
+  __device__ long len() const { return end - begin; }
+};
+// Segment seg's rows.  Bounds: the offsets are clamped to [0, N] and to each other and the length to max_len, so whatever seg_off holds,
+// 0 <= begin <= end <= N.
+__device__ inline GmmRows gmm_segment(const int* __restrict__ seg_off, int seg, long N, long max_len) {
+  long r0 = seg_off[seg], r1 = seg_off[seg + 1];
+  r0 = r0 < 0 ? 0 : (r0 > N ? N : r0);
+  r1 = r1 < r0 ? r0 : (r1 > N ? N : r1);
+  return {r0, r0 + (r1 - r0 < max_len ? r1 - r0 : max_len)};
+}
+// Slab i's rows of a segment, within the segment's own; empty (begin >= end) for i >= gmm_slabs(seg.len()): a grid is sized for the longest segment.
+__device__ inline GmmRows gmm_slab(GmmRows seg, int i) {
+  const long sl = gmm_slab_len(seg.len()), b = seg.begin + i * sl;
+  return {b, b + sl < seg.end ? b + sl : seg.end};
+}
+
 // Frames [f0, f0 + nvalid) of X into Xs (rows beyond nvalid and the padding column: zeros, nothing is read for them).  One wave per row.
 template <typename T>
 __device__ inline void gmm_load_frames(const T* __restrict__ X, int D, long f0, int nvalid, double* Xs, int xld) {
@@ -37,6 +55,17 @@ __device__ inline void gmm_load_frames(const T* __restrict__ X, int D, long f0, 
   }
 }
 
+// (M, S) <- the log-sum-exp state with v added: sum = S exp(M).  S exp(M - v) + 1 for a new maximum, S + exp(v - M) otherwise, with one
+// exp for both cases (its argument is -|v - M| either way); v = -inf and nan add nothing.
+__device__ inline void lse_add(double& M, double& S, double v) {
+  if (v > -INFINITY) {
+    const bool top = v > M;
+    const double e = exp(top ? M - v : v - M);
+    S = top ? S * e + 1.0 : S + e;
+    M = top ? v : M;
+  }
+}
+
 // (M, S) <- the log-sum-exp state of both: sum = S exp(M); symmetric in its two states bit for bit
 __device__ inline void lse_merge(double& M, double& S, double m2, double s2) {
   const double m = fmax(M, m2);
@@ -48,6 +77,22 @@ __device__ inline void lse_merge(double& M, double& S, double m2, double s2) {
 template <typename K>
 static int gmm_allow_lds(K kernel, size_t bytes) {
   if (bytes > 65536) SK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return SK_OK;
+}
+
+// The checks every entry point makes before anything is enqueued: the frames, the mixture's three operands and their sizes ...
+static int gmm_check_common(const char* who, const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const double* d_mu, const double* d_invcov,
+                            const double* d_A, int32_t C) {
+  SK_CHECK(d_X && d_mu && d_invcov && d_A, SK_EARG, "%s: null argument", who);
+  SK_CHECK(x_dtype == XT_F32 || x_dtype == XT_F64, SK_EARG, "%s: X must be XT_F32 or XT_F64 (got %d)", who, x_dtype);
+  SK_CHECK(N >= 1 && N <= 0x7fffffffLL && D >= 1 && D <= SC_GMM_MAX_D && C >= 1 && C <= SC_GMM_MAX_C, SK_EARG,
+           "%s: bad sizes (N=%lld, D=%d with at most %d, C=%d with at most %d)", who, (long long)N, D, SC_GMM_MAX_D, C, SC_GMM_MAX_C);
+  return SK_OK;
+}
+// ... and of the entry points that take segments, that the grid's x = segment * slabs + slab fits.
+static int gmm_check_segments(const char* who, int64_t N, int32_t S, int64_t max_len) {
+  SK_CHECK(S >= 1 && max_len >= 0 && max_len <= N && (long long)S * gmm_slabs(max_len) <= 0x7fffffffLL, SK_EARG,
+           "%s: bad sizes (S=%d, max_len=%lld, N=%lld)", who, S, (long long)max_len, (long long)N);
   return SK_OK;
 }
 

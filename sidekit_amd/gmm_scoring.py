@@ -23,17 +23,11 @@ SCORING_BYTES = 1 << 30   # frames of the test segments that go to the device in
 MAX_MODELS = 65535    # SC_GMM_SCORE_MAX_M (include/sidekit_amd/gmm_scoring.h): models of one sc_gmm_score_models call
 
 
-def _device_f64(torch, a, dev):
-    if torch.is_tensor(a):
-        return a.to(device=dev, dtype=torch.float64).contiguous()
-    return torch.as_tensor(numpy.array(a, dtype=numpy.float64, order='C')).to(dev)   # a copy: the source may be read-only
-
-
-def _offsets(seg_off, N):
-    off = numpy.array([0, N], dtype=numpy.int64) if seg_off is None else numpy.asarray(seg_off, dtype=numpy.int64)
-    assert off.ndim == 1 and off.shape[0] >= 2 and numpy.all(numpy.diff(off) >= 0) and off[0] >= 0 and off[-1] <= N, \
-        "seg_off: S + 1 ascending offsets within [0, N]"
-    return off
+def _device_mask(torch, mask, dev):
+    """``mask`` (host array or tensor, ``None`` stays ``None``) -> booleans on ``dev``"""
+    if mask is None:
+        return None
+    return (mask.to(dev) if torch.is_tensor(mask) else torch.as_tensor(numpy.ascontiguousarray(mask)).to(dev)).ne(0)
 
 
 def gmm_llk_device(ubm, models, frames, seg_off=None, mask=None, max_workspace_bytes=1 << 30):
@@ -52,18 +46,18 @@ def gmm_llk_device(ubm, models, frames, seg_off=None, mask=None, max_workspace_b
     assert ubm.invcov.ndim == 2 and ubm.mu.shape == ubm.invcov.shape, "a diagonal mixture has (C, D) means and inverse covariances"
     assert D == ubm.dim(), 'dimension of ubm and features differ: {:d} / {:d}'.format(ubm.dim(), D)
     C = ubm.mu.shape[0]
-    mus = _device_f64(torch, models, dev)
+    mus = mixture._device_f64(torch, models, dev)
     assert mus.dim() in (2, 3) and mus.shape[0] > 0 and mus[0].numel() == C * D, "models: (M, C D) or (M, C, D) means of the mixture's shape"
     mus = mus.reshape(mus.shape[0], C, D)
     M = mus.shape[0]
-    off = _offsets(seg_off, N)
+    off = mixture._offsets(seg_off, N)
     S, lens = off.shape[0] - 1, numpy.diff(off)
-    invcov = _device_f64(torch, ubm.invcov, dev)
-    B = _device_f64(torch, -2.0 * (numpy.log(ubm.w) + numpy.log(ubm.cst)), dev)
+    invcov = mixture._device_f64(torch, ubm.invcov, dev)
+    B = mixture._device_f64(torch, -2.0 * (numpy.log(ubm.w) + numpy.log(ubm.cst)), dev)
     d_off = torch.as_tensor(off.astype(numpy.int32)).to(dev)
-    d_mask = None
-    if mask is not None:
-        d_mask = (mask.to(dev) if torch.is_tensor(mask) else torch.as_tensor(numpy.ascontiguousarray(mask)).to(dev)).ne(0).to(torch.uint8).contiguous()
+    d_mask = _device_mask(torch, mask, dev)
+    if d_mask is not None:
+        d_mask = d_mask.to(torch.uint8).contiguous()
         assert d_mask.shape == (M, S), "mask: one entry per model and segment"
     llk = torch.zeros((M, S), dtype=torch.float64, device=dev)
     longest = int(lens.max())
@@ -89,13 +83,12 @@ def gmm_llr_device(ubm, models, frames, seg_off=None, mask=None, max_workspace_b
     x, dt, host = mixture._frames(torch, frames)
     dev = x.device
     C, D = ubm.mu.shape
-    mus = _device_f64(torch, models, dev)
+    mus = mixture._device_f64(torch, models, dev)
     mus = mus.reshape(mus.shape[0], C * D)
     M = mus.shape[0]
-    stacked = torch.cat((mus, _device_f64(torch, ubm.mu, dev).reshape(1, C * D)))
-    d_mask = None
-    if mask is not None:
-        d_mask = (mask.to(dev) if torch.is_tensor(mask) else torch.as_tensor(numpy.ascontiguousarray(mask)).to(dev)).ne(0)
+    stacked = torch.cat((mus, mixture._device_f64(torch, ubm.mu, dev).reshape(1, C * D)))
+    d_mask = _device_mask(torch, mask, dev)
+    if d_mask is not None:
         assert d_mask.dim() == 2 and d_mask.shape[0] == M, "mask: one entry per model and segment"
         stacked_mask = torch.cat((d_mask, torch.ones((1, d_mask.shape[1]), dtype=torch.bool, device=dev)))
     llk, lens = gmm_llk_device(ubm, stacked, x, seg_off, None if mask is None else stacked_mask, max_workspace_bytes)
@@ -131,7 +124,7 @@ def map_adapt_device(stat0, stat1, ubm, r=16, multisession_index=None):
     mean = s1 / s0[:, :, None]
     mean = torch.where(torch.isnan(mean), torch.zeros_like(mean), mean)
     alpha = alpha[:, :, None]
-    return alpha * mean + (1 - alpha) * _device_f64(torch, ubm.mu, dev)[None]
+    return alpha * mean + (1 - alpha) * mixture._device_f64(torch, ubm.mu, dev)[None]
 
 
 def _check_types(ubm, enroll, ndx):
@@ -158,7 +151,7 @@ def gmm_scoring_singleThread(ubm, enroll, ndx, feature_server, score_mat, seg_id
         return
     torch = mixture._torch()
     dev = torch.device("cuda", torch.cuda.current_device())
-    models = _device_f64(torch, enroll.stat1[[enrolled[name] for name in ndx.modelset[rows]], :], dev)
+    models = mixture._device_f64(torch, enroll.stat1[[enrolled[name] for name in ndx.modelset[rows]], :], dev)
 
     def score(batch):
         cols = numpy.array([t for t, _ in batch], dtype=numpy.int64)

@@ -49,6 +49,21 @@ def _frames(torch, frames):
     return frames.contiguous(), (_lib.XT_F32 if frames.dtype == torch.float32 else _lib.XT_F64), host
 
 
+def _device_f64(torch, a, dev):
+    """A host array or a tensor -> a contiguous float64 tensor on ``dev``"""
+    if torch.is_tensor(a):
+        return a.to(device=dev, dtype=torch.float64).contiguous()
+    return torch.as_tensor(numpy.array(a, dtype=numpy.float64, order='C')).to(dev)   # a copy: the source may be read-only
+
+
+def _offsets(seg_off, N):
+    """``seg_off`` (``None``: one segment, all frames) -> the S + 1 offsets as int64, checked"""
+    off = numpy.array([0, N], dtype=numpy.int64) if seg_off is None else numpy.asarray(seg_off, dtype=numpy.int64)
+    assert off.ndim == 1 and off.shape[0] >= 2 and numpy.all(numpy.diff(off) >= 0) and off[0] >= 0 and off[-1] <= N, \
+        "seg_off: S + 1 ascending offsets within [0, N]"
+    return off
+
+
 def _model(torch, ubm, dev, mu=None):
     """The device operands of a diagonal mixture: ``(mu, invcov, A)``; a replaced ``mu`` comes with its own ``A`` (:526-528)"""
     if ubm.invcov.ndim == 3:
@@ -61,8 +76,7 @@ def _model(torch, ubm, dev, mu=None):
         mu = numpy.asarray(mu, dtype=numpy.float64).reshape(ubm.mu.shape)
         A = (numpy.square(mu) * ubm.invcov).sum(1) - 2.0 * (numpy.log(ubm.w) + numpy.log(ubm.cst))
     A = numpy.broadcast_to(numpy.asarray(A, dtype=numpy.float64), ubm.w.shape)
-    up = lambda a: torch.as_tensor(numpy.array(a, dtype=numpy.float64, order='C')).to(dev)   # noqa: E731  (a copy: the source may be read-only)
-    return up(mu), up(ubm.invcov), up(A)
+    return _device_f64(torch, mu, dev), _device_f64(torch, ubm.invcov, dev), _device_f64(torch, A, dev)
 
 
 def _loglik(torch, ubm, x, dt, mu=None, want_lp=False):
@@ -114,9 +128,7 @@ def gmm_stats_device(ubm, frames, seg_off=None, order=2, max_workspace_bytes=1 <
     x, dt, host = _frames(torch, frames)
     N, D = x.shape
     dev = x.device
-    off = numpy.array([0, N], dtype=numpy.int64) if seg_off is None else numpy.asarray(seg_off, dtype=numpy.int64)
-    assert off.ndim == 1 and off.shape[0] >= 2 and numpy.all(numpy.diff(off) >= 0) and off[0] >= 0 and off[-1] <= N, \
-        "seg_off: S + 1 ascending offsets within [0, N]"
+    off = _offsets(seg_off, N)
     S, lens = off.shape[0] - 1, numpy.diff(off)
     lse, _, (m, ic, A) = _loglik(torch, ubm, x, dt)
     C = m.shape[0]
