@@ -702,17 +702,20 @@ static int frontend_rows(xt_handle* h, Lane& ln, const void* d_wav, int pcm16, i
   }
   { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_stft_power_fft(fa, st)); }
   if (!h->mel_fused) {  // 2) power x mel filterbank, log(. + 1e-6)
+    SK_TRY(tap(h, "power", ln.ws[WS_S].p, (size_t)M * h->nbp * 4, st));
     GemmArgs p = gemm_args();
     p.A = ln.ws[WS_S].p; p.lda = h->nbp; p.a_rows = M;
     p.W = h->d_fbT; p.ldw = h->nbp; p.M = M; p.N = f.n_mels; p.K = h->nbp; p.act = ACT_LOG_EPS;
     p.C = logmel; p.ldc = f.n_mels;
     { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_gemm(p, st)); }
   }
+  SK_TRY(tap(h, "logmel", logmel, (size_t)M * f.n_mels * 4, st));
   if (mfcc) {  // 3) DCT-II (ortho) 100 -> 80
     GemmArgs d = gemm_args();
     d.A = logmel; d.lda = f.n_mels; d.a_rows = M; d.W = h->d_dctT; d.ldw = f.n_mels;
     d.C = d_feat_rows; d.ldc = f.n_out; d.M = M; d.N = f.n_out; d.K = f.n_mels;
     { ProfScope ps(h, XT_PROF_FRONTEND, st); SK_TRY(launch_gemm(d, st)); }
+    SK_TRY(tap(h, "mfcc", d_feat_rows, (size_t)M * f.n_out * 4, st));
   }
   // 4) CMVN over the utterance's own frames
   RowSpan rs{m.d_offsets, m.T, m.lens, 0, 0};
