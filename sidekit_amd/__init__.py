@@ -3,7 +3,8 @@
 Sub-modules mirror the reference package layout for the hot path only:
 ``sidekit_amd.nnet.xvector.Xtractor``, ``sidekit_amd.iv_scoring``, ``sidekit_amd.factor_analyser``, ``sidekit_amd.statserver``,
 ``sidekit_amd.bosaris``, ``sidekit_amd.score_normalization``, ``sidekit_amd.lid_utils``, ``sidekit_amd.mixture``, ``sidekit_amd.gmm_scoring``, ``sidekit_amd.jfa_scoring``, ``sidekit_amd.sidekit_io``, ``sidekit_amd.frontend.vad``,
-``sidekit_amd.features_server``, ``sidekit_amd.frontend.normfeat``, ``sidekit_amd.frontend.features``, ``sidekit_amd.features_extractor``.
+``sidekit_amd.features_server``, ``sidekit_amd.frontend.normfeat``, ``sidekit_amd.frontend.features``, ``sidekit_amd.features_extractor``,
+``sidekit_amd.svm_training``, ``sidekit_amd.svm_scoring``, ``sidekit_amd.sv_utils``.
 ``install_as_sidekit()`` registers them under the ``sidekit`` names so that reference-style drivers
 (``extract_xvectors.py``, scoring scripts) import them unchanged.
 """
@@ -45,7 +46,7 @@ _LAZY = {
 # every module of the mirror, by its reference name
 SUBMODULES = ("bosaris", "bosaris.idmap", "bosaris.ndx", "bosaris.key", "bosaris.scores", "bosaris.detplot", "statserver", "iv_scoring", "factor_analyser",
               "score_normalization", "lid_utils", "mixture", "gmm_scoring", "jfa_scoring", "sidekit_io", "nnet", "nnet.xvector", "nnet.preprocessor", "frontend", "frontend.vad",
-              "features_server", "frontend.normfeat", "frontend.features", "features_extractor")
+              "features_server", "frontend.normfeat", "frontend.features", "features_extractor", "sv_utils", "svm_training", "svm_scoring")
 
 
 def __getattr__(name):

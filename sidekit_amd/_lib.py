@@ -127,6 +127,13 @@ JFA_SIGNATURES = {
     "sc_jfa_map_acc": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/svm.h (sidekit_amd/svm_training.py)
+SVM_SIGNATURES = {
+    "sc_svm_train": (ctypes.c_int, [_P, _I32, _P, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _F64, _I32, _P, _P, _P, _P, _P, _P]),
+}
+SC_SVM_MAX_N = (163840 - 1024) // 24   # include/sidekit_amd/svm.h: the points of one problem (three doubles each in the LDS of one workgroup)
+SC_SVM_CONVERGED, SC_SVM_MAX_ITER, SC_SVM_BAD_OFFSETS = 0, 1, 2
+
 # name -> (restype, argtypes); every symbol of include/sidekit_amd/features.h (sidekit_amd/features_server.py)
 FEATURES_SIGNATURES = {
     "sc_feat_rasta": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _P, _I64, _P]),
@@ -160,7 +167,7 @@ def lib():
     cdll = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()) + list(MIXTURE_SIGNATURES.items())
                               + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())
-                              + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items())):
+                              + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items()) + list(SVM_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -11,7 +11,8 @@ statistics of a diagonal ``Mixture`` on the GPU (``sidekit_amd.mixture``), which
 means to each session or model on the host (element-wise work on ``sessions x C D`` numbers; ``sidekit_amd.gmm_scoring.map_adapt_device`` does the
 same on resident statistics) for ``sidekit_amd.gmm_scoring``; ``factor_analysis`` with ``estimate_between_class`` / ``estimate_within_class`` /
 ``estimate_map`` / ``estimate_hidden`` / ``subtract_weighted_stat1`` (:819-850, :1494-1949) train the joint factor analysis model on the GPU
-(``sidekit_amd.jfa_scoring``); ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
+(``sidekit_amd.jfa_scoring``); ``precompute_svm_kernel_stat1`` (:1159-1168), ``get_nap_matrix_stat1`` (:1056-1073) and ``get_model_segments``
+(:635-643) serve the SVM back end (``sidekit_amd.svm_training``); ``read`` / ``write`` (:392-489) exchange HDF5 files with the reference through ``sidekit_amd.hdf5_lite``.  Values are float64
 (``STAT_TYPE``, ``sidekit/__init__.py:59``); the alignments use hashed lookups instead of per-id scans.
 """
 import copy
@@ -140,6 +141,10 @@ class StatServer:
 
     def get_segment_stat1(self, seg_id):
         return self.stat1[self.segset == seg_id, :]
+
+    def get_model_segments(self, mod_id):
+        """The segments of model ``mod_id`` (``statserver.py:635-643``)."""
+        return self.segset[self.modelset == mod_id]
 
     def get_mean_stat1(self):
         return numpy.mean(self.stat1, axis=0)
@@ -298,6 +303,29 @@ class StatServer:
         out.stat1 = self._map_means(summed.stat0, summed.stat1, summed.stat0 / (summed.stat0 + r), ubm, norm)
         out.validate()
         return out
+
+    # ---- the SVM back end (sidekit_amd/svm_training.py): float64 on the GPU, host arrays in and out, no CPU fallback ------------------
+
+    def _device_stat1(self):
+        from .svm_training import _rows, _torch
+        torch = _torch()
+        return torch, _rows(torch, self.stat1)[0]
+
+    def precompute_svm_kernel_stat1(self):
+        """The background's part of the SVM Gram matrix, ``stat1 . stat1'`` (``statserver.py:1159-1168``): one float64 GEMM."""
+        torch, s = self._device_stat1()
+        return torch.matmul(s, s.t()).cpu().numpy()
+
+    def get_nap_matrix_stat1(self, co_rank):
+        """The Nuisance Attribute Projection matrix of co-rank ``co_rank`` (``statserver.py:1056-1073``) -> (D, co_rank): the leading
+        eigenvectors of ``stat1 . stat1' / D`` mapped back through ``stat1'`` and scaled to unit length, columns by descending
+        eigenvalue.  The eigen-decomposition is ``torch.linalg.eigh`` on the device in float64; a column is defined up to its sign."""
+        torch, s = self._device_stat1()
+        vect_size = s.shape[1]
+        assert 0 < co_rank <= s.shape[0], "co_rank must be in [1, number of sessions]"
+        lam, vec = torch.linalg.eigh(torch.matmul(s, s.t()) / vect_size)     # ascending
+        lam, vec = torch.flip(lam[-co_rank:], (0,)), torch.flip(vec[:, -co_rank:], (1,))
+        return (torch.matmul(s.t(), vec) / torch.sqrt(vect_size * lam)[None, :]).cpu().numpy()
 
     # ---- back-end normalisation on the GPU (sidekit_amd/backend.py): stat1 is uploaded once per call, no CPU fallback ----------------
 
