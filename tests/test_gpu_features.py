@@ -4,7 +4,7 @@ reference's own output (tests/golden/features.npz).
 
 One stacked batch of D = 5: the fixture's sixteen streams plus an empty, a 1-row and a 2-row segment and the lengths TILE - 1, TILE,
 TILE + 1 and 2 TILE + h + 1 (TILE = 256 rows, h = 150 for the window of 301); a second one of D = 17 (the column chunk is 16) with the
-lengths that matter for a tile.  Bound against the restatement r on the same float32 inputs: |gpu - r| <= 2^-23 |r| + 1e-10 max|x| (one
+lengths that matter for a tile; a third pair (``long_segments``) of segments longer than the 2048 rows one round of the tile lanes covers.  Bound against the restatement r on the same float32 inputs: |gpu - r| <= 2^-23 |r| + 1e-10 max|x| (one
 rounding to float32, 2^-24 |r|, doubled; float64 summation-order differences over at most 1001 terms, for window standard deviations of
 order 1, asserted > 0.1 on the restatement's side; among thousands of windows of 5 random values a few are narrower, so at window 5
 cmvn_sliding is held to the bound on every value but those of such a window, under 0.1 % of them and no whole row).
@@ -20,9 +20,13 @@ from scipy.special import ndtr
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 import normfeat_numpy as nfn  # noqa: E402
+import second_trips as st  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TILE, H = 256, 150
+PASS = st.FEAT_PASS        # FZ * SC_FEAT_TILE = 2048 rows: what the FZ = 8 workgroups of a segment cover before each takes another tile
+LONG = [PASS, 0, PASS + 1, 7, PASS + TILE + H + 1, 2 * PASS + 7]
+LONG_WIDE = [0, PASS + 1]
 KEYS = [str(n) for n in (3, 4, 5, 6, 7, 8, 9, 299, 300, 301, 302, 303, 650, 900)] + ["s301", "s302"]
 EXTRA = [0, 1, 2, TILE - 1, TILE, TILE + 1, 2 * TILE + H + 1]
 WIDE = [0, 1, 2, 7, TILE - 1, TILE, TILE + 1, 2 * TILE + H + 1, 302]
@@ -287,6 +291,60 @@ def test_a_segment_has_the_same_bits_alone_and_anywhere_in_the_batch(gpu, batche
             s, l = b.segments[i], b.labels[i]
             alone = _post(fs, b, gpu, x=s, off=numpy.array([0, s.shape[0]]), lab=l, **kw)[0] if s.shape[0] else out[:0]
             assert _same(alone, out[int(off[i]):int(off[i + 1])]), f"post {norm}: segment {i}"
+
+
+# ---- segments longer than one round of the tile lanes ----------------------------------------------------------------------------------
+def long_segments():
+    """The third batch (D = 5): 2048 rows (one full round of the FZ = 8 tile lanes, no second pass), an empty segment, 2049 rows, a short
+    one, 2048 + 256 + 150 + 1 rows (the second pass's window of 301 reaches into rows of the first round) and 2 * 2048 + 7 rows (a third
+    pass); and one of D = 17 with 2049 rows.  Every row is labelled but five of the longest segment, two of them either side of row 2048:
+    4098 speech rows, still three passes."""
+    rs = numpy.random.RandomState(78)
+    out = []
+    for lengths, d in ((LONG, 5), (LONG_WIDE, 17)):
+        segs, labs = [], []
+        for n in lengths:
+            x, _ = _draw(rs, n, d)
+            lab = numpy.ones(n, dtype=bool)
+            if n == 2 * PASS + 7:
+                lab[[10, 1000, PASS - 1, PASS, 3000]] = False
+            segs.append(x)
+            labs.append(lab)
+        out.append(Batch(segs, labs))
+    return tuple(out)
+
+
+@pytest.fixture(scope="module")
+def long_batches():
+    narrow, wide = long_segments()
+    assert st.FZ * st.SC_FEAT_TILE == PASS == 2048 and TILE == st.SC_FEAT_TILE
+    assert max(s.shape[0] for s in narrow.segments) > 2 * PASS and max(s.shape[0] for s in wide.segments) > PASS   # a third pass; a second one
+    assert int(narrow.labels[-1].sum()) > 2 * PASS
+    return narrow, wide
+
+
+def test_long_segments_delta_and_moments_against_the_restatement(gpu, long_batches):
+    """feat_delta_kernel's second and third ``t0 += FZ * FT`` pass (a segment longer than FZ * FT = 2048 rows): RASTA, every filter and
+    the moments on the third batch, every row compared, under the criteria of the first two batches."""
+    test_rasta_delta_and_moments_against_the_restatement(gpu, long_batches)
+
+
+@pytest.mark.parametrize("win", [301, 5])
+def test_long_segments_normalisations_against_the_restatement(gpu, long_batches, win):
+    """feat_norm_kernel<MODE> past FZ * FT = 2048 rows: the barrier between two tiles of one workgroup and the staging window
+    ``slo..shi`` counted from a later tile, all five modes, warp ranks exact.  The restatement is of every row (100 % compared; at
+    window 5 cmvn_sliding leaves out what the first two batches leave out, windows narrower than 0.1, under 0.1 % of the values)."""
+    test_normalisations_against_the_restatement(gpu, long_batches, win)
+
+
+def test_long_segments_post_process_with_warping(gpu, long_batches):
+    """``post_process_device`` (RASTA, deltas, double deltas, feature warping over the labelled rows) on the third batch."""
+    test_post_process_device_against_the_restatement(gpu, long_batches, "stg")
+
+
+def test_long_segments_have_the_same_bits_alone_and_anywhere_in_the_batch(gpu, long_batches):
+    """A segment of two or three passes alone, inside the batch and inside the mirrored batch: the same bits, every operation."""
+    test_a_segment_has_the_same_bits_alone_and_anywhere_in_the_batch(gpu, long_batches)
 
 
 def _close_to_golden(what, got, want, extra=1e-6):

@@ -9,6 +9,8 @@ D = 256, noise 1.7, unit rows) with a cohort built the same way (RandomState(12)
 1.74 %, binned 1.7e-5 away; no score in an end bin."""
 import ctypes
 import json
+import os
+import sys
 
 import numpy
 import pytest
@@ -18,6 +20,9 @@ from oracle import scoring as osc
 from sidekit_amd import _lib, iv_scoring
 from sidekit_amd import score_normalization as sn
 from sidekit_amd.bosaris import eer_from_histograms
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import second_trips as st  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NB = iv_scoring.HIST_BINS
@@ -126,6 +131,44 @@ def test_ragged_and_small_shapes(gpu, ne, nt, dim):
     bins, tar = _bins(z, lo, hi), le[:, None] == lt[None, :]
     assert int(ht.sum() + hn.sum()) == ne * nt
     assert numpy.array_equal(ht, _count(bins, tar)) and numpy.array_equal(hn, _count(bins, ~tar))
+
+
+@pytest.fixture(scope="module")
+def walk(gpu):
+    """A set whose 256 x 256 tiles outnumber the compute units (tests/tools/second_trips.py: D = 8, 40 speakers), and a cohort of 300."""
+    cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    n, t = st.hist_side(cus, st.HT)
+    x, lab = st.cosine_corpus(n)
+    c, _ = st.cosine_corpus(300, seed=26)
+    return {"cus": cus, "n": n, "t": t, "X": torch.from_numpy(x).to(gpu), "C": torch.from_numpy(c).to(gpu), "lab": lab}
+
+
+@pytest.mark.parametrize("name", list(KINDS))
+def test_counts_when_the_tiles_outnumber_the_compute_units(walk, name):
+    """cosine_hist_kernel<HN_ENROL | HN_TEST | HN_BOTH> walks ``tile += gridDim.x`` with one workgroup per compute unit; past CU-count
+    tiles a workgroup takes a second one and stages that tile's 512 (mean, std) in ``stat`` behind the k loop's barriers, over the ones
+    the first tile's epilogue read.  N = (t - 1) 256 + 3 with t x t > CUs (4099 at 256 CUs: 289 tiles), both edges ragged, the set
+    against itself, every kind: the counts are those of the materialised path (sc_cosine, the normalisation, then this module's
+    ``_bins`` -- evaluated on the device, every 97th row also by ``_bins`` itself)."""
+    kind, topk = KINDS[name]
+    X, C, lab, n, t = walk["X"], walk["C"], walk["lab"], walk["n"], walk["t"]
+    assert ((n + st.HT - 1) // st.HT) ** 2 == t * t > walk["cus"]
+    z = iv_scoring.cosine_matrix_device(X, X)
+    if kind == "z":
+        sn.znorm_device(z, X, C)
+    elif kind == "t":
+        sn.tnorm_device(z, X, C)
+    else:
+        sn.snorm_device(z, X, X, C, topk=topk)
+    assert bool(torch.isfinite(z).all())
+    lo, hi = _range(z)
+    want_t, want_n, bins = st.device_counts(z, lo, hi, NB, lab, lab, 0)
+    rows = slice(None, None, 97)
+    assert numpy.array_equal(bins[rows].cpu().numpy(), _bins(z[rows].cpu().numpy(), lo, hi))
+    ht, hn = sn.normalised_histograms(X, X, lab, lab, C, kind=kind, topk=topk, self_offset=0, lo=lo, hi=hi)
+    assert ht.dtype == hn.dtype == numpy.uint64 and int(ht.sum() + hn.sum()) == n * n - n
+    assert numpy.array_equal(ht, want_t) and numpy.array_equal(hn, want_n)
+    assert int(ht[0] + hn[0] + ht[-1] + hn[-1]) == 0 and int((ht + hn > 0).sum()) > 1000   # every score inside the range, spread over it
 
 
 def test_disjoint_sets_drop_nothing(corpus):

@@ -9,6 +9,7 @@ score lies in an end bin."""
 import ctypes
 import json
 import os
+import sys
 
 import numpy
 import pytest
@@ -18,6 +19,9 @@ from oracle import scoring as osc
 from sidekit_amd import _lib, iv_scoring
 from sidekit_amd.bosaris import Ndx, eer_from_histograms
 from sidekit_amd.statserver import StatServer
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import second_trips as st  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NB = iv_scoring.HIST_BINS
@@ -112,6 +116,37 @@ def test_odd_shapes(odd):
     got = iv_scoring.plda_histograms(*args, self_offset=57, lo=odd["lo"], hi=odd["hi"])
     _same(got, bins, odd["tar"], odd["keep"])
     assert int(got[0].sum() + got[1].sum()) == 130 * 257 - 130
+
+
+def test_counts_when_the_tiles_outnumber_the_compute_units(gpu, golden_dir):
+    """plda_hist_kernel<HN_NONE> walks ``tile += gridDim.x`` with one workgroup per compute unit; past CU-count tiles a workgroup takes a
+    second one and writes that tile's row and column terms into ``term`` behind dgemm_tile's barriers, over the ones the first tile's
+    epilogue read.  N = (t - 1) 128 + 3 with t x t > CUs (2051 at 256 CUs: 289 tiles), both edges ragged, D = 10 (a partial k-tile of 16),
+    the model of the ``odd`` fixture cut to 10 dimensions, 40 speakers, the set against itself: the counts are those of binning
+    plda_matrix_device's matrix with ``_bins`` (on the device; every 97th row also by ``_bins`` itself).  A row shard of 16 x 17 tiles
+    -- still more than CUs -- starts on another row of the tile."""
+    cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    n, t = st.hist_side(cus, st.PT)
+    assert ((n + st.PT - 1) // st.PT) ** 2 == t * t > cus
+    model = st.plda_model(golden_dir, 10)
+    x, lab = st.plda_corpus(model, n)
+    X = torch.as_tensor(x).to(gpu)
+    Xc = (X - torch.as_tensor(model[0]).to(gpu)).contiguous()
+    mat = iv_scoring.plda_matrix_device(Xc, Xc, *iv_scoring.plda_parameters(*model))
+    lo, hi = _range(mat[~torch.eye(n, dtype=torch.bool, device=gpu)])               # without the self-trials, as the ``big`` fixture's
+    want_t, want_n, bins = st.device_counts(mat, lo, hi, NB, lab, lab, 0)
+    rows = slice(None, None, 97)
+    assert numpy.array_equal(bins[rows].cpu().numpy(), _bins(mat[rows].cpu().numpy(), lo, hi))
+    ht, hn = iv_scoring.plda_histograms(X, X, lab, lab, *model, self_offset=0, lo=lo, hi=hi)
+    assert ht.dtype == hn.dtype == numpy.uint64 and int(ht.sum() + hn.sum()) == n * n - n
+    assert numpy.array_equal(ht, want_t) and numpy.array_equal(hn, want_n)
+    assert int(ht[0] + hn[0] + ht[-1] + hn[-1]) == 0 and int((ht + hn > 0).sum()) > 1000   # every score inside the range, spread over it
+    a = 67
+    assert ((n - a + st.PT - 1) // st.PT) * t > cus
+    want_t, want_n, _ = st.device_counts(mat[a:], lo, hi, NB, lab[a:], lab, a)
+    ht, hn = iv_scoring.plda_histograms(X[a:], X, lab[a:], lab, *model, self_offset=a, lo=lo, hi=hi)
+    assert int(ht.sum() + hn.sum()) == (n - a) * (n - 1)
+    assert numpy.array_equal(ht, want_t) and numpy.array_equal(hn, want_n)
 
 
 def _obj(a):

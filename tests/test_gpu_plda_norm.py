@@ -16,6 +16,7 @@ the one-pass cancellation adds about eps * mean^2 / var <= 4 eps here)."""
 import ctypes
 import json
 import os
+import sys
 
 import numpy
 import pytest
@@ -25,6 +26,9 @@ from oracle import scoring as osc
 from sidekit_amd import _lib, iv_scoring
 from sidekit_amd import score_normalization as sn
 from sidekit_amd.bosaris import eer_from_histograms
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import second_trips as st  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NB = iv_scoring.HIST_BINS
@@ -176,6 +180,86 @@ def test_statistics_do_not_depend_on_the_launch(gpu, odd):
     assert float(keepsake[0]) == -7.0
 
 
+_LONG = {}
+
+
+def _long_cohort(gpu, golden_dir, d):
+    """33 000 rows drawn from the fixture's model cut to ``d`` dimensions (tests/tools/second_trips.py), raw and centred, on the device."""
+    if d not in _LONG:
+        model = st.plda_model(golden_dir, d)
+        C = torch.as_tensor(st.plda_corpus(model, st.COHORT_M, seed=25 + d)[0]).to(gpu)
+        Phi, Psi, cst = iv_scoring.plda_parameters(*model)
+        _LONG[d] = {"model": model, "C": C, "Cc": (C - torch.as_tensor(model[0]).to(gpu)).contiguous(), "params": (Phi, Psi, cst),
+                    "phi": torch.as_tensor(Phi).to(gpu).contiguous(), "psi": torch.as_tensor(Psi).to(gpu).contiguous()}
+    return _LONG[d]
+
+
+def _moments_direct(gpu, k, x, c, self_offset):
+    """sc_plda_cohort_moments itself on centred rows; the outputs start at -7."""
+    mean = torch.full((x.shape[0],), -7.0, dtype=torch.float64, device=gpu)
+    std = torch.full((x.shape[0],), -7.0, dtype=torch.float64, device=gpu)
+    rc = _lib.lib().sc_plda_cohort_moments(x.data_ptr(), x.shape[0], c.data_ptr(), c.shape[0], x.shape[1], k["phi"].data_ptr(), k["psi"].data_ptr(),
+                                           float(k["params"][2]), 1.0, self_offset, mean.data_ptr(), std.data_ptr(),
+                                           ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream))
+    assert rc == _lib.SK_OK, _lib.last_error()
+    return mean, std
+
+
+def _host_moments_of_own_matrix(k, x, c, drop):
+    """The module's yardstick: two-pass float64 statistics of the device's own materialised scores, and 1e-9 of the largest of them."""
+    s = iv_scoring.plda_matrix_device(x, c, *k["params"]).cpu().numpy()
+    return st.kept_moments(s, drop) + (1e-9 * float(numpy.abs(s).max()),)
+
+
+@pytest.mark.parametrize("d", [4, 5])
+def test_moments_past_the_row_block(gpu, golden_dir, d, monkeypatch):
+    """sc_plda_cohort_moments launches ROWS = 32 768 rows of X at a time and gives a slab more than two cohort tiles once M > 16 384
+    (``tiles_m > 128``).  X = C[r : r + N] with N = 32 768 + 130, M = 33 000 and self_offset = r crosses both in one call: the second
+    launch reads ``w.epsi + r0 * D`` and ``w.qe + r0`` (with ``x_stride = N``), drops the pair ``i + self_offset + r0``, writes
+    ``d_mean + r0`` and reuses the first launch's partials; a slab holds 5 tiles, 52 partials are joined.  D = 4 (16-byte loads) and D = 5
+    (the scalar-load path).  (a) Rows [32 766, N) against the host's statistics of the device's own matrix of those rows at this module's
+    1e-9 of the largest score.  (b) The same rows, and four ranges of the first block, against calls of their own on those rows alone:
+    bit for bit (a row's additions do not depend on N or on the launch)."""
+    k = _long_cohort(gpu, golden_dir, d)
+    M, r, N = st.COHORT_M, st.COHORT_R, st.ROWS + st.COHORT_EXTRA
+    tiles_m, per, slabs = st.slab_rule(M)
+    assert N > st.ROWS and M > st.SLAB_TILES * st.COHORT_TILE and tiles_m > st.SLAB_TILES and per > st.MIN_PER and r + N <= M
+    c = k["Cc"]
+    x = c[r:r + N].contiguous()
+    mean, std = _moments_direct(gpu, k, x, c, r)
+    assert bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all()) and float(std.min()) > 0.0
+    reached, lib = [], _lib.lib()
+    monkeypatch.setattr(_lib, "lib", lambda: _Spy(lib, reached))
+    m2, s2 = sn.plda_cohort_stats_device(k["C"][r:r + N], k["C"], *k["model"], self_offset=r)   # the Python entry: ONE call carries the whole N
+    monkeypatch.undo()
+    assert reached.count("sc_plda_cohort_moments") == 1 and m2.shape == (N,) and torch.equal(m2, mean) and torch.equal(s2, std)
+    a = st.ROWS - 2
+    want_mean, want_std, bound = _host_moments_of_own_matrix(k, x[a:].contiguous(), c, numpy.arange(a, N) + r)
+    em, es = float(numpy.abs(mean[a:].cpu().numpy() - want_mean).max()), float(numpy.abs(std[a:].cpu().numpy() - want_std).max())
+    print(f"D = {d}: mean off by {em:.2e}, std by {es:.2e} (bound {bound:.2e})")
+    assert em <= bound and es <= bound
+    for a0, a1 in st.first_block_samples() + [(st.ROWS - 128, N)]:
+        part = _moments_direct(gpu, k, x[a0:a1].contiguous(), c, r + a0)
+        assert torch.equal(part[0], mean[a0:a1]) and torch.equal(part[1], std[a0:a1]), (a0, a1)
+
+
+@pytest.mark.parametrize("M", st.SLAB_M)
+def test_moments_at_and_past_the_slab_limit(gpu, golden_dir, M):
+    """M = 16 384: the last cohort whose slabs hold two tiles (64 slabs of 2); M = 16 385 + 100: 129 tiles, 3 to a slab, 43 partials.
+    N = 130 rows, X = C[100 : 230] with its self-pairs dropped, D = 6: the module's bound, and the bits of a call on the last 53 rows."""
+    k = _long_cohort(gpu, golden_dir, 6)
+    tiles_m, per, slabs = st.slab_rule(M)
+    assert (tiles_m, per, slabs) == ((128, 2, 64) if M == st.SLAB_TILES * st.COHORT_TILE else (129, 3, 43))
+    r, n = st.COHORT_R, st.COHORT_EXTRA
+    c = k["Cc"][:M].contiguous()
+    x = c[r:r + n].contiguous()
+    mean, std = _moments_direct(gpu, k, x, c, r)
+    want_mean, want_std, bound = _host_moments_of_own_matrix(k, x, c, numpy.arange(n) + r)
+    assert float(numpy.abs(mean.cpu().numpy() - want_mean).max()) <= bound and float(numpy.abs(std.cpu().numpy() - want_std).max()) <= bound
+    part = _moments_direct(gpu, k, x[77:].contiguous(), c, r + 77)
+    assert torch.equal(part[0], mean[77:]) and torch.equal(part[1], std[77:])
+
+
 def test_scaling_factor_and_channel_subspace(gpu, golden_dir):
     """The model arguments of plda_histograms: a scaling factor, and with G both sides projected by B (the route of full_PLDA_scoring)."""
     fx = numpy.load(os.path.join(golden_dir, "scoring.npz"))
@@ -282,6 +366,41 @@ def test_odd_counts_are_those_of_the_materialised_path(odd, kind):
         raw = odd["mat"].cpu().numpy()
         rlo, rhi = _range(raw)
         _same(iv_scoring.plda_norm_histograms(e, t, odd["le"], odd["lt"], *model, lo=rlo, hi=rhi), _bins(raw, rlo, rhi), odd["tar"], odd["all"])
+
+
+@pytest.fixture(scope="module")
+def walk(gpu, golden_dir):
+    """A set whose 128 x 128 tiles outnumber the compute units (tests/tools/second_trips.py: D = 10, the fixture's model cut to 10
+    dimensions, 40 speakers), a cohort of 300 from the same model, and the device's own raw matrix."""
+    cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    n, t = st.hist_side(cus, st.PT)
+    model = st.plda_model(golden_dir, 10)
+    x, lab = st.plda_corpus(model, n)
+    X, C = torch.as_tensor(x).to(gpu), torch.as_tensor(st.plda_corpus(model, 300, seed=27, n_spk=60)[0]).to(gpu)
+    Xc = (X - torch.as_tensor(model[0]).to(gpu)).contiguous()
+    mat = iv_scoring.plda_matrix_device(Xc, Xc, *iv_scoring.plda_parameters(*model))
+    return {"cus": cus, "n": n, "t": t, "X": X, "C": C, "lab": lab, "model": model, "mat": mat, "off": ~torch.eye(n, dtype=torch.bool, device=gpu)}
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_counts_when_the_tiles_outnumber_the_compute_units(walk, kind):
+    """plda_hist_kernel<HN_ENROL | HN_TEST | HN_BOTH> walks ``tile += gridDim.x`` with one workgroup per compute unit; past CU-count
+    tiles a workgroup takes a second one and rewrites ``term`` and ``stat`` for it behind dgemm_tile's barriers.  N = (t - 1) 128 + 3
+    with t x t > CUs (2051 at 256 CUs: 289 tiles), both edges ragged, D = 10, the set against itself, every kind: the counts are those of
+    the materialised path (plda_matrix_device, plda_{z,t,s}norm_device, then ``_bins`` -- evaluated on the device, every 97th row also
+    by ``_bins`` itself)."""
+    X, C, lab, model, n, t = walk["X"], walk["C"], walk["lab"], walk["model"], walk["n"], walk["t"]
+    assert ((n + st.PT - 1) // st.PT) ** 2 == t * t > walk["cus"]
+    z = _device_norm(kind, walk["mat"], X, X, C, model, K)
+    assert bool(torch.isfinite(z).all())
+    lo, hi = _range(z[walk["off"]])
+    want_t, want_n, bins = st.device_counts(z, lo, hi, NB, lab, lab, 0)
+    rows = slice(None, None, 97)
+    assert numpy.array_equal(bins[rows].cpu().numpy(), _bins(z[rows].cpu().numpy(), lo, hi))
+    ht, hn = sn.plda_normalised_histograms(X, X, lab, lab, C, *model, self_offset=0, lo=lo, hi=hi, **_hist_kw(kind, K))
+    assert ht.dtype == hn.dtype == numpy.uint64 and int(ht.sum() + hn.sum()) == n * n - n
+    assert numpy.array_equal(ht, want_t) and numpy.array_equal(hn, want_n)
+    assert int(ht[0] + hn[0] + ht[-1] + hn[-1]) == 0 and int((ht + hn > 0).sum()) > 1000   # every score inside the range, spread over it
 
 
 class _Spy:

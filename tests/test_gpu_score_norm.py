@@ -14,6 +14,9 @@ from sidekit_amd.bosaris import Scores
 
 from test_gpu_plda_norm import _Spy
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import second_trips as st  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 TOL = dict(rtol=5e-5, atol=5e-5)      # normalised scores: the tolerance of the asnorm tests (same arithmetic, same 1 / std amplification)
 
@@ -161,6 +164,75 @@ def test_cohort_moments_bits_do_not_depend_on_stream_or_on_n(gpu):
     assert torch.equal(torch.cat((lo[0], hi[0])), whole[0]) and torch.equal(torch.cat((lo[1], hi[1])), whole[1])
     odd = _moments(x[77:].contiguous(), c, self_offset=177)                            # another place in the tile, the same bits
     assert torch.equal(odd[0], whole[0][77:]) and torch.equal(odd[1], whole[1][77:])
+
+
+@pytest.fixture(scope="module")
+def long_cohort(gpu):
+    """33 000 unit rows of D = 4 (tests/tools/second_trips.py): 258 cohort tiles, and room for X = C[100 : 100 + 32 768 + 130]."""
+    return torch.from_numpy(st.cohort_cosine()).to(gpu)
+
+
+@pytest.mark.parametrize("affine", [False, True])
+def test_cohort_moments_past_the_row_block(gpu, long_cohort, affine, monkeypatch):
+    """sc_cohort_moments launches ROWS = 32 768 rows of X at a time and gives a slab more than two cohort tiles once M > 16 384
+    (``tiles_m > 128``).  X = C[r : r + N] with N = 32 768 + 130, M = 33 000 and self_offset = r crosses both in one call: the second
+    launch reads ``d_X + r0 * D``, drops the pair ``i + self_offset + r0``, writes ``d_mean + r0`` and reuses the first launch's workspace;
+    a slab holds 5 tiles and 52 partials are joined.  With and without col_shift / col_scale.  (a) Rows [32 766, N), either side of the
+    block edge, against float64 numpy on sc_cosine's products of those rows: 2e-6 absolute (test_cohort_moments_ragged_shapes), with the
+    affine form the bound of test_cohort_moments_col_shift_and_scale.  (b) The same rows, and four ranges of the first block, against
+    calls of their own on those rows alone: bit for bit, the property the kernel documents (a row's additions depend on M alone)."""
+    M, r, N = st.COHORT_M, st.COHORT_R, st.ROWS + st.COHORT_EXTRA
+    tiles_m, per, slabs = st.slab_rule(M)
+    assert N > st.ROWS and M > st.SLAB_TILES * st.COHORT_TILE and tiles_m > st.SLAB_TILES and per > st.MIN_PER and r + N <= M
+    c = long_cohort
+    x = c[r:r + N].contiguous()
+    shift = scale = None
+    if affine:
+        rs = numpy.random.RandomState(24)
+        shift = torch.from_numpy((0.1 * rs.randn(M)).astype(numpy.float32)).to(gpu)
+        scale = torch.from_numpy(rs.uniform(0.5, 20.0, M).astype(numpy.float32)).to(gpu)
+    mean, std = _moments(x, c, shift, scale, self_offset=r)
+    assert bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all()) and float(std.min()) > 0.0
+    reached, lib = [], _lib.lib()
+    monkeypatch.setattr(_lib, "lib", lambda: _Spy(lib, reached))
+    m2, s2 = sn.cohort_stats_device(x, c, self_offset=r, col_shift=shift, col_scale=scale)      # the Python entry: ONE call carries the whole N
+    monkeypatch.undo()
+    assert reached.count("sc_cohort_moments") == 1 and m2.shape == (N,) and torch.equal(m2, mean) and torch.equal(s2, std)
+    # (a) float64 numpy on the rows around the block edge
+    a = st.ROWS - 2
+    s = _cosine(x[a:].contiguous(), c)
+    drop = numpy.arange(a, N) + r
+    assert numpy.all(s[numpy.arange(N - a), drop] > 0.999)                             # the dropped pairs are the self-scores
+    if affine:
+        s = (s - shift.cpu().numpy().astype(numpy.float64)) * scale.cpu().numpy().astype(numpy.float64)
+    want_mean, want_std = st.kept_moments(s, drop)
+    tol = dict(rtol=1.2e-7, atol=1e-9) if affine else dict(rtol=0, atol=2e-6)
+    got_mean, got_std = mean[a:].cpu().numpy(), std[a:].cpu().numpy()
+    print(f"affine {affine}: mean off by {numpy.abs(got_mean - want_mean).max():.2e}, std by {numpy.abs(got_std - want_std).max():.2e}")
+    numpy.testing.assert_allclose(got_mean, want_mean, **tol)
+    numpy.testing.assert_allclose(got_std, want_std, **tol)
+    # (b) the same bits as calls of their own
+    for a0, a1 in st.first_block_samples() + [(st.ROWS - 128, N)]:
+        part = _moments(x[a0:a1].contiguous(), c, shift, scale, self_offset=r + a0)
+        assert torch.equal(part[0], mean[a0:a1]) and torch.equal(part[1], std[a0:a1]), (a0, a1)
+
+
+@pytest.mark.parametrize("M", st.SLAB_M)
+def test_cohort_moments_at_and_past_the_slab_limit(gpu, long_cohort, M):
+    """M = 16 384 is the last cohort whose slabs hold two tiles (``tiles_m > 128`` is false: 64 slabs of 2); M = 16 385 + 100 gives 129
+    tiles, 3 to a slab, 43 partials.  N = 130 rows, X = C[100 : 230] with its self-pairs dropped: float64 numpy on sc_cosine's products
+    at 2e-6 absolute, and the bits of a call on the last 53 rows alone."""
+    tiles_m, per, slabs = st.slab_rule(M)
+    assert (tiles_m, per, slabs) == ((128, 2, 64) if M == st.SLAB_TILES * st.COHORT_TILE else (129, 3, 43))
+    r, n = st.COHORT_R, st.COHORT_EXTRA
+    c = long_cohort[:M].contiguous()
+    x = c[r:r + n].contiguous()
+    mean, std = _moments(x, c, self_offset=r)
+    want_mean, want_std = st.kept_moments(_cosine(x, c), numpy.arange(n) + r)
+    numpy.testing.assert_allclose(mean.cpu().numpy(), want_mean, rtol=0, atol=2e-6)
+    numpy.testing.assert_allclose(std.cpu().numpy(), want_std, rtol=0, atol=2e-6)
+    part = _moments(x[77:].contiguous(), c, self_offset=r + 77)
+    assert torch.equal(part[0], mean[77:]) and torch.equal(part[1], std[77:])
 
 
 def test_norm_apply(gpu):

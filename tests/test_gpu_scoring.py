@@ -1,5 +1,6 @@
 """Trial scoring on the GPU through the C ABI: golden reference matrices, oracle at the 1M-trial size, EER."""
 import os
+import sys
 
 import numpy
 import pytest
@@ -9,6 +10,9 @@ from oracle import scoring as osc
 from sidekit_amd import iv_scoring
 from sidekit_amd.bosaris import Key, Ndx, rocch, rocch2eer
 from sidekit_amd.statserver import StatServer
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import second_trips as st  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -306,6 +310,37 @@ def test_cosine_histograms_match_the_score_matrix(gpu):
     assert abs(eer_from_histograms(hft, hfn) - eer_x) < 5e-4
     with pytest.raises(AssertionError):
         iv_scoring.cosine_histograms(X, X, lab, lab, bins=10000)
+
+
+def test_cosine_histograms_walk_more_tiles_than_compute_units(gpu):
+    """cosine_hist_kernel<HN_NONE> is one persistent workgroup per compute unit that walks the 256 x 256 tiles ``tile += gridDim.x``; once
+    the tiles outnumber the CUs a workgroup takes a second one: accumulators zeroed again, the LDS operand tiles reused, the prefetch
+    restarted.  N = (t - 1) 256 + 3 with the smallest t whose t x t tiles exceed the CU count (4099 at 256 CUs: 289 tiles, 33 workgroups
+    take two), both edges ragged, D = 8, 40 speakers, the set against itself.  The counts are those of binning sc_cosine's matrix, as in
+    test_cosine_histograms_match_the_score_matrix (binned on the device; every 97th row also with that test's numpy expression).  A row
+    shard of 16 x 17 tiles -- still more than CUs -- starts on another row of the tile."""
+    cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    N, t = st.hist_side(cus, st.HT)
+    ntiles = ((N + st.HT - 1) // st.HT) ** 2
+    assert ntiles == t * t > cus
+    x, lab = st.cosine_corpus(N)
+    X = torch.from_numpy(x).to(gpu)
+    nb = iv_scoring.HIST_BINS
+    S = iv_scoring.cosine_matrix_device(X, X)
+    want_t, want_n, bins = st.device_counts(S, -1.0, 1.0, nb, lab, lab, 0)
+    rows = slice(None, None, 97)
+    host = numpy.clip(numpy.floor((S[rows].cpu().numpy() - numpy.float32(-1.0)) * numpy.float32(nb / 2.0)).astype(numpy.int64), 0, nb - 1)
+    assert numpy.array_equal(bins[rows].cpu().numpy(), host)
+    ht, hn = iv_scoring.cosine_histograms(X, X, lab, lab, self_offset=0)
+    assert ht.dtype == numpy.uint64 and int(ht.sum() + hn.sum()) == N * N - N
+    assert numpy.array_equal(ht, want_t) and numpy.array_equal(hn, want_n)
+    assert int((ht + hn > 0).sum()) > nb // 2                                          # the scores spread over the bins
+    a = 130
+    assert ((N - a + st.HT - 1) // st.HT) * t > cus
+    want_t, want_n, _ = st.device_counts(S[a:], -1.0, 1.0, nb, lab[a:], lab, a)
+    ht, hn = iv_scoring.cosine_histograms(X[a:], X, lab[a:], lab, self_offset=a)
+    assert int(ht.sum() + hn.sum()) == (N - a) * (N - 1)
+    assert numpy.array_equal(ht, want_t) and numpy.array_equal(hn, want_n)
 
 
 def test_sharded_driver_single_rank(gpu, capsys):

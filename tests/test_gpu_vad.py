@@ -16,6 +16,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 
+import second_trips as st  # noqa: E402
 import vad_numpy as vn  # noqa: E402
 from sidekit_amd import _lib  # noqa: E402
 from sidekit_amd import vad as skvad  # noqa: E402
@@ -130,6 +131,50 @@ def test_fusion_boundary_rule_on_a_hand_made_row(gpu):
     for bad in (2, 4, 257, -3):
         with pytest.raises(ValueError):
             skvad.vad_energy_device(d_le, nf, fusion_win=bad)
+
+
+@pytest.mark.parametrize("win", st.VAD_WINDOWS)
+def test_fusion_past_one_tile(gpu, win):
+    """vad_energy_kernel fuses labels VAD_TILE = 2048 frames at a time with a halo of 4 r frames read across the tile's edges (r = win // 2)
+    and scipy's 'reflect' rule at the row's two ends only.  Rows of 2048 (one tile), 2049, 2048 + 4 r + 1 and 4096 + 300 frames (three
+    tiles), each in 24 hand-made patterns (tests/tools/second_trips.py: an isolated frame or a run of r - 1, r or r + 1 frames, of ones or
+    of zeros, ending at, starting at or lying across frames 2048 and 4096, and at both ends of the row), plus a 1-frame and an ordinary
+    row.  The raw labels are the designed pattern; the fused ones are scipy's closing then opening of it; a row alone has the bits it has
+    in the batch.  Windows 3 (the default), 31 and 255 (halo 508).  tests/test_second_trips_cpu.py shows that fusing tile by tile without
+    the halo, or with 'reflect' at a tile's edge, fails this comparison on these rows."""
+    r = win // 2
+    assert st.VAD_TILE == 2048 and win <= st.VAD_MAX_WIN
+    patterns = st.vad_patterns(win)
+    lengths = sorted({p.shape[0] for p in patterns})
+    assert lengths == [1, 25, 2048, 2049, 2048 + 4 * r + 1, 4096 + 300] and lengths[3] > st.VAD_TILE and lengths[-1] > 2 * st.VAD_TILE
+    le, nf = st.vad_log_energies(patterns)
+    d_le, d_nf = torch.from_numpy(le).to(gpu), torch.from_numpy(nf).to(gpu)
+    raw, thr = skvad.vad_energy_device(d_le, d_nf, 8, fusion_win=0, **st.VAD_KW)
+    raw, thr = raw.cpu().numpy(), thr.cpu().numpy()
+    for b, p in enumerate(patterns):
+        if p.shape[0] > 1:
+            assert numpy.array_equal(raw[b, :p.shape[0]], p), "the detector no longer separates the two levels: the test's input needs care"
+        else:
+            assert raw[b, 0] == 1 and numpy.isnan(thr[b])
+        assert not raw[b, p.shape[0]:].any()
+    got, thr = skvad.vad_energy_device(d_le, d_nf, 8, fusion_win=win, **st.VAD_KW)
+    got_h, thr = got.cpu().numpy(), thr.cpu().numpy()
+    changed = 0
+    for b, p in enumerate(patterns):
+        n = p.shape[0]
+        want = scipy.ndimage.grey_opening(scipy.ndimage.grey_closing(p, size=win), size=win)
+        changed += int((want != p).any())
+        if n > 1 and want.any():
+            assert numpy.array_equal(got_h[b, :n], want), (win, b, n, numpy.flatnonzero(got_h[b, :n] != want)[:8])
+            assert numpy.array_equal(vn.label_fusion(p, win), want.astype(bool))
+        else:
+            assert got_h[b, :n].all() and numpy.isnan(thr[b])
+        assert not got_h[b, n:].any()
+    assert changed > len(patterns) // 2                                          # the fusion has work to do on most rows
+    for b in (0, 24, 30, 48, 55, 72, 80, 95, 96, 97):                            # every length; alone: a batch of one, its own width
+        n = patterns[b].shape[0]
+        alone, _ = skvad.vad_energy_device(d_le[b:b + 1, :n].contiguous(), d_nf[b:b + 1], 8, fusion_win=win, **st.VAD_KW)
+        assert torch.equal(alone[0], got[b, :n]), (win, b)
 
 
 def _segments(data):
