@@ -115,6 +115,13 @@ GMM_SCORING_SIGNATURES = {
     "sc_gmm_score_models": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _I32, _P, _P, _I32, _P, _I32, _I64, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/gmm_topc.h (sidekit_amd/gmm_scoring.py, the top-C functions)
+GMM_TOPC_SIGNATURES = {
+    "sc_gmm_top_components": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _I32, _P, _P]),
+    "sc_gmm_score_models_topc": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _I32, _P, _P, _I32, _P, _I32, _I64, _P, _P, _I32, _P, _P]),
+}
+SC_GMM_TOPC_MAX = 32   # include/sidekit_amd/gmm_topc.h: components per frame
+
 # name -> (restype, argtypes); every symbol of include/sidekit_amd/ivector.h (sidekit_amd/factor_analyser.py)
 IVECTOR_SIGNATURES = {
     "sc_tv_gram": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
@@ -167,7 +174,8 @@ def lib():
     cdll = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()) + list(MIXTURE_SIGNATURES.items())
                               + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())
-                              + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items()) + list(SVM_SIGNATURES.items())):
+                              + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items()) + list(SVM_SIGNATURES.items())
+                              + list(GMM_TOPC_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -2,6 +2,8 @@
 // frames that stay on the device, without the N x C posterior matrix.  Two entry points (include/sidekit_amd/mixture.h):
 //   sc_gmm_frame_loglik   pass A: lse[n] = log sum_c exp lp[n][c] (and lp itself on request)
 //   sc_gmm_stats          pass B: per segment, stat0 / stat1 / stat2 = pp' . [1, X, X^2] with pp = exp(lp - lse), and the sum of lse
+// and one of include/sidekit_amd/gmm_topc.h, here because it chooses from pass A's lp:
+//   sc_gmm_top_components per frame, the K components with the largest lp (the lists of top-C scoring, gmm_topc.hip)
 // Both form lp = -0.5 ([X^2, X] . [invcov, -2 mu invcov]' + A) tile by tile on v_mfma_f64_16x16x4_f64 (one GEMM with K = 2 D), by the
 // same function in the same order (gmm_lp_tile), so pass B recomputes the bits pass A saw.  Recomputing costs 4 C D of the 12 C D FLOP
 // per frame; storing lp would cost N C 8 bytes.  float64 throughout, no floating-point atomics, every sum in a fixed order.
@@ -17,6 +19,7 @@
 //   Ps  64 x 65        pass B: the posterior tile, [component][frame], the A operand of the second GEMM
 // pass B at D = 60: 73 KB (two workgroups per CU), at D = 128: 108 KB (one); pass A: 40 KB / 75 KB.  Pass B's accumulator is
 // 16 components x 16 NT columns per wave (NT tiles cover 2 D + 1 columns, or D + 1 for order 1): 4 NT doubles per lane, 32 at D = 60.
+#include "../../include/sidekit_amd/gmm_topc.h"
 #include "gmm_tile.h"
 #include "kernels.h"
 
@@ -139,6 +142,107 @@ __global__ __launch_bounds__(256, 2) void gmm_loglik_kernel(const T* __restrict_
   }
 }
 
+// ---- component lists -----------------------------------------------------------------------------------------------------------------
+// grid: x = frame tile.  The workgroup walks the component tiles in ascending order as pass A does; after gmm_lp_tile the 64 x 64 tile of
+// lp = -0.5 (acc + A) goes through Ps (nan staged as -inf) and is merged into a list of K (value, index) pairs per frame, Lv / Li, that
+// lives in LDS.  The merge has two steps.  All four waves: thread (frame, quarter) compares its 16 components with the value of the
+// list's worst entry as it stood before this tile (thr) and leaves a 16-bit set of candidates; after the first tile or two almost every
+// set is empty.  Then thread f < 64 walks frame f's candidates in ascending component order: components below K fill the list as they
+// are, a later one replaces the worst entry if its lp is larger -- an equal lp loses, it has the higher index -- and the worst entry
+// (the smallest lp, at equal lp the highest index) is found again by a scan of the K pairs.  So a list always holds K distinct components
+// below C, whatever the values are.  At the end entry k of a frame is stored at its rank among the frame's indices: ascending component.
+// A frame's list is a function of its own row of acc alone, which is a function of the frame and the mixture.
+// Bounds: frames beyond N are zero rows whose lists are not stored; components beyond C are never candidates; K <= min(C, 32, 64).
+template <typename T>
+__global__ __launch_bounds__(256, 2) void gmm_topc_kernel(const T* __restrict__ X, long N, int D, const double* __restrict__ mu,
+                                                          const double* __restrict__ invcov, const double* __restrict__ A, int C, int K,
+                                                          int* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double gmm_smem[];
+  const int xld = gmm_xld(D);
+  double* Xs = gmm_smem;
+  double* Gs = Xs + GT * xld;
+  double* Ps = Gs + GT * DLD;               // [component][frame]
+  double* Lv = Ps + GT * PLD;               // [K][GT]
+  double* thr = Lv + K * GT;                // [GT]
+  int* Li = (int*)(thr + GT);               // [K][GT]
+  unsigned* cand = (unsigned*)Gs;           // [4][GT]: Gs is free from the barrier after the tile's last multiply to the next tile's first
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lk = lane >> 4;
+  const long f0 = (long)blockIdx.x * GT;
+  const int nvalid = N - f0 < GT ? (int)(N - f0) : GT;
+  gmm_load_frames(X, D, f0, nvalid, Xs, xld);
+  if (tid < GT) thr[tid] = -INFINITY;
+  double wv = -INFINITY;   // thread f < 64: the worst entry of frame f's list, its value, component and place
+  int wi = 0, wp = 0;
+  auto worst = [&]() {
+    wv = Lv[tid]; wi = Li[tid]; wp = 0;
+    for (int k = 1; k < K; ++k) {
+      const double v = Lv[k * GT + tid];
+      const int i = Li[k * GT + tid];
+      if (v < wv || (v == wv && i > wi)) { wv = v; wi = i; wp = k; }
+    }
+  };
+  for (int c0 = 0; c0 < C; c0 += GT) {
+    f64x4 acc[4];
+    gmm_lp_tile(Xs, xld, Gs, mu, invcov, C, D, c0, acc);
+    {
+      const int c = c0 + wave * 16 + lr;
+      const double a = c < C ? A[c] : 0.0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double v = -0.5 * (acc[i][q] + a);
+          Ps[(wave * 16 + lr) * PLD + i * 16 + lk + 4 * q] = v != v ? -INFINITY : v;
+        }
+    }
+    __syncthreads();   // Ps is complete, every wave is done with Gs
+    {
+      const double t = thr[lane];
+      unsigned m = 0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int c = c0 + wave * 16 + j;
+        const double v = Ps[(wave * 16 + j) * PLD + lane];
+        if (c < C && (c < K || v > t)) m |= 1u << j;
+      }
+      cand[wave * GT + lane] = m;
+    }
+    __syncthreads();
+    if (tid < GT) {
+      for (int q = 0; q < 4; ++q) {
+        unsigned m = cand[q * GT + tid];
+        while (m) {
+          const int j = __ffs(m) - 1;
+          m &= m - 1;
+          const int c = c0 + q * 16 + j;
+          const double v = Ps[(q * 16 + j) * PLD + tid];
+          if (c < K) {
+            Lv[c * GT + tid] = v;
+            Li[c * GT + tid] = c;
+            if (c == K - 1) worst();
+          } else if (v > wv) {
+            Lv[wp * GT + tid] = v;
+            Li[wp * GT + tid] = c;
+            worst();
+          }
+        }
+      }
+      thr[tid] = wv;
+    }
+    // the next tile's first barrier (gmm_lp_tile) comes before anything of Gs, Ps or thr is touched again
+  }
+  __syncthreads();
+  for (int e = tid; e < K * GT; e += 256) {
+    const int f = e & (GT - 1), k = e / GT;
+    if (f >= nvalid) continue;
+    const int me = Li[k * GT + f];
+    int rank = 0;
+    for (int k2 = 0; k2 < K; ++k2) rank += Li[k2 * GT + f] < me;
+    out[(f0 + f) * K + rank] = me;
+  }
+}
+
 // ---- pass B ------------------------------------------------------------------------------------------------------------------------
 // grid: x = segment * nslab + slab, y = component tile.  Per frame tile of its slab (tiles start at the slab's first frame) the workgroup
 // recomputes lp, forms pp = exp(lp - lse[n]) in registers -- 0 by assignment for a frame outside the slab or a component beyond C, whose
@@ -245,6 +349,19 @@ static int launch_gmm_loglik(const T* X, long N, int D, const double* mu, const 
   return SK_OK;
 }
 
+__host__ __device__ inline size_t gmm_topc_lds(int D, int K) {
+  return (size_t)(GT * gmm_xld(D) + GT * DLD + GT * PLD + K * GT + GT) * 8 + (size_t)K * GT * 4;
+}
+
+template <typename T>
+static int launch_gmm_topc(const T* X, long N, int D, const double* mu, const double* invcov, const double* A, int C, int K, int* idx, hipStream_t st) {
+  const size_t lds = gmm_topc_lds(D, K);
+  SK_TRY(gmm_allow_lds(gmm_topc_kernel<T>, lds));
+  hipLaunchKernelGGL(gmm_topc_kernel<T>, dim3((unsigned)((N + GT - 1) / GT)), dim3(256), lds, st, X, N, D, mu, invcov, A, C, K, idx);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
 template <int NT, typename T>
 static int launch_gmm_stats_nt(const T* X, long N, int D, const double* mu, const double* invcov, const double* A, int C, const double* lse,
                                const int* seg_off, int S, long max_len, int nslab, int ncols, double* p0, double* p1, double* p2, hipStream_t st) {
@@ -318,6 +435,15 @@ int sc_gmm_stats(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const d
                             d_llk, (hipStream_t)stream);
   return launch_gmm_stats((const double*)d_X, (long)N, D, d_mu, d_invcov, d_A, C, d_lse, d_seg_off, S, (long)max_len, order, d_stat0, d_stat1, d_stat2,
                           d_llk, (hipStream_t)stream);
+}
+
+int sc_gmm_top_components(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const double* d_mu, const double* d_invcov, const double* d_A,
+                          int32_t C, int32_t K, int32_t* d_idx, void* stream) {
+  SK_TRY(gmm_check_common("sc_gmm_top_components", d_X, x_dtype, N, D, d_mu, d_invcov, d_A, C));
+  SK_CHECK(d_idx, SK_EARG, "sc_gmm_top_components: null argument");
+  SK_CHECK(K >= 1 && K <= C && K <= SC_GMM_TOPC_MAX, SK_EARG, "sc_gmm_top_components: K=%d outside [1, min(C=%d, %d)]", K, C, SC_GMM_TOPC_MAX);
+  if (x_dtype == XT_F32) return launch_gmm_topc((const float*)d_X, (long)N, D, d_mu, d_invcov, d_A, C, K, d_idx, (hipStream_t)stream);
+  return launch_gmm_topc((const double*)d_X, (long)N, D, d_mu, d_invcov, d_A, C, K, d_idx, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// What the diagonal-GMM kernels share (gmm.hip: frame log-likelihoods and statistics; gmm_score.hip: GMM-UBM scoring), one copy of each:
+// What the diagonal-GMM kernels share (gmm.hip: frame log-likelihoods, statistics and top-C lists; gmm_score.hip: GMM-UBM scoring;
+// gmm_topc.hip: the same on the lists), one copy of each:
 // the frame tile and its load; a segment's rows and its cut into slabs (the one place seg_off is read, so a join reads the workspace slots
 // its producer's cut says were written); the online log-sum-exp update and the merge of two states; the argument checks.
 #pragma once
