@@ -831,10 +831,12 @@ static int half_from_feats(xt_handle* h, Lane& ln, const float* feats, long sb, 
   RowSpan rs{nullptr, H4, m.lens, 3, 0};
   ProfScope ps_pool(h, XT_PROF_POOL_TAIL, st);
   SK_TRY(launch_mean_std(X, xbf, D, D, rs, (float*)ln.ws[WS_CTX].p, B, st));
+  SK_TRY(tap(h, "ctx", ln.ws[WS_CTX].p, (size_t)B * 2 * D * 4, st));
   GemmArgs c = gemm_args();  // context term of attention.0: W1[:, 2560:] . [mean | std] + bias, once per utterance
   c.A = ln.ws[WS_CTX].p; c.lda = 2 * D; c.a_rows = B; c.W = h->att_w1c; c.ldw = 2 * D; c.C = (float*)ln.ws[WS_RB].p; c.ldc = 128;
   c.M = B; c.N = 128; c.K = 2 * D; c.bias = h->att_b1; c.splitk_ws = (float*)ln.ws[WS_SPLITK].p;
   SK_TRY(launch_gemm(c, st));
+  SK_TRY(tap(h, "att_rb", ln.ws[WS_RB].p, (size_t)B * 128 * 4, st));
   GemmArgs g1 = gemm_args();  // attention.0 on x + ReLU + BatchNorm1d + tanh
   g1.A = X; g1.a_bf16 = xbf; g1.lda = D; g1.a_rows = R; g1.W = h->att_w1x; g1.ldw = D; g1.C = (float*)ln.ws[WS_H].p; g1.ldc = 128;
   g1.M = R; g1.N = 128; g1.K = D; g1.rowbias = (const float*)ln.ws[WS_RB].p; g1.rows_per_group = H4;
