@@ -6,7 +6,10 @@ The split is ``backend``'s: everything with a frame (N) dimension runs on the de
 matrix of log posteriors only where the reference's method returns it) and ``sc_gmm_stats`` (zeroth, first and second order statistics
 per segment, recomputing the posteriors tile by tile: no ``N x C`` array exists) -- and the ``C x D`` algebra (M-step, variance
 control, the split, ``_compute_all``) stays on the host in the reference's operation order.  The ``*_device`` functions work on
-resident frames (float32 or float64, widened in the load) and copy nothing with an N dimension to the host.  Full covariances
+resident frames (float32 or float64, widened in the load) and copy nothing with an N dimension to the host.  Beside the reference's
+surface stand the top-C forms (Gaussian selection; ``include/sidekit_amd/gmm_topc_stats.h``): ``gmm_topc_posteriors_device`` gives the
+posteriors of every frame over its list of ``top_c`` components (``gmm_scoring.gmm_top_components_device``) and
+``gmm_stats_topc_device`` the statistics accumulated from them, ``K D`` of gather work per frame after the lists.  Full covariances
 (``invcov.ndim == 3``) raise ``NotImplementedError``; ``read_alize``, ``read_htk``, ``write_alize`` and ``merge`` are not built.  There is
 no CPU fallback; importing the module needs neither a GPU nor torch.
 """
@@ -139,6 +142,72 @@ def gmm_stats_device(ubm, frames, seg_off=None, order=2, max_workspace_bytes=1 <
     d_off = torch.as_tensor(off.astype(numpy.int32)).to(dev)
     for a, b in _segment_groups(lens, C * (order * D + 1), max_workspace_bytes):
         _lib.launch("sc_gmm_stats", dev, x, dt, N, D, m, ic, A, C, lse, d_off[a:], b - a, int(lens[a:b].max()), order, stat0[a:], stat1[a:],
+                    None if stat2 is None else stat2[a:], llk[a:])
+    out = (stat0, stat1, stat2, llk)
+    return tuple(None if t is None else t.cpu().numpy() for t in out) if host else out
+
+
+def _topc_posteriors(torch, ubm, x, dt, K, components):
+    """``(idx (N, K) int32, post (N, K), lse (N,))`` on the frames' device: the lists (``sc_gmm_top_components``, or the caller's as they
+    are -- the kernels skip an entry outside [0, C)) and the posteriors over them (``sc_gmm_topc_posteriors``)"""
+    from . import gmm_scoring
+    N, D = x.shape
+    dev = x.device
+    assert D == ubm.dim(), 'dimension of ubm and features differ: {:d} / {:d}'.format(ubm.dim(), D)
+    assert ubm.invcov.ndim == 2 and ubm.mu.shape == ubm.invcov.shape, "a diagonal mixture has (C, D) means and inverse covariances"
+    if components is None:
+        idx = gmm_scoring._lists(torch, ubm, x, dt, K)
+    else:
+        idx = (components if torch.is_tensor(components) else torch.as_tensor(numpy.ascontiguousarray(components))).to(dev).contiguous()
+    C = ubm.mu.shape[0]
+    with numpy.errstate(divide="ignore"):   # a zero weight: log 0, B = inf, posterior 0
+        B = -2.0 * (numpy.log(ubm.w) + numpy.log(ubm.cst))
+    post = torch.empty((N, K), dtype=torch.float64, device=dev)
+    lse = torch.empty(N, dtype=torch.float64, device=dev)
+    _lib.launch("sc_gmm_topc_posteriors", dev, x, dt, N, D, _device_f64(torch, ubm.mu, dev), _device_f64(torch, ubm.invcov, dev),
+                _device_f64(torch, B, dev), C, idx, K, post, lse)
+    return idx, post, lse
+
+
+def gmm_topc_posteriors_device(ubm, frames, top_c=10, components=None):
+    """Sparse posteriors (``sc_gmm_topc_posteriors``, ``include/sidekit_amd/gmm_topc_stats.h``): per frame the ``K = min(top_c, C)``
+    components of its list, their posteriors renormalised over the list (they sum to 1) and ``lse[n] = log sum_k w_c N(x_n; mu_c,
+    Sigma_c)`` over the list.  ``components``: (N, K) int32, host array or CUDA tensor -- an entry outside [0, C) contributes nothing and
+    gets posterior 0, a frame without a valid entry has ``lse = -inf``; ``None``: the lists of ``gmm_top_components_device(ubm, frames,
+    top_c)``.  ``frames``: (N, D) CUDA tensor (float32 or float64) or host array.  Returns ``(idx (N, K) int32, post (N, K) float64, lse
+    (N,) float64)``, on the device when the frames were there.  No ``N x C`` array exists."""
+    from . import gmm_scoring
+    K = gmm_scoring._top_c(ubm, top_c, frames, components)
+    torch = _torch()
+    x, dt, host = _frames(torch, frames)
+    out = _topc_posteriors(torch, ubm, x, dt, K, components)
+    return tuple(t.cpu().numpy() for t in out) if host else out
+
+
+def gmm_stats_topc_device(ubm, frames, seg_off=None, order=2, top_c=10, components=None, max_workspace_bytes=1 << 30):
+    """``gmm_stats_device`` with every frame's posteriors cut to its list of ``min(top_c, C)`` components and renormalised over it
+    (Gaussian selection; ``sc_gmm_topc_posteriors`` then ``sc_gmm_topc_stats``): a component's statistics sum over the frames that list
+    it, ``llk`` sums ``lse`` over the lists.  ``components`` as ``gmm_topc_posteriors_device`` takes them, computed once per call
+    whatever the grouping when ``None``.  The other arguments, the shapes, dtypes and placement of ``(stat0, stat1, stat2 or None, llk)``
+    as ``gmm_stats_device``; the grouping does not change a bit, and a segment's statistics depend on its own frames and lists alone."""
+    from . import gmm_scoring
+    assert order in (1, 2), "order: 1 (stat0, stat1) or 2 (and stat2)"
+    K = gmm_scoring._top_c(ubm, top_c, frames, components)
+    torch = _torch()
+    x, dt, host = _frames(torch, frames)
+    N, D = x.shape
+    dev = x.device
+    off = _offsets(seg_off, N)
+    S, lens = off.shape[0] - 1, numpy.diff(off)
+    idx, post, lse = _topc_posteriors(torch, ubm, x, dt, K, components)
+    C = ubm.mu.shape[0]
+    stat0 = torch.empty((S, C), dtype=torch.float64, device=dev)
+    stat1 = torch.empty((S, C, D), dtype=torch.float64, device=dev)
+    stat2 = torch.empty((S, C, D), dtype=torch.float64, device=dev) if order == 2 else None
+    llk = torch.empty(S, dtype=torch.float64, device=dev)
+    d_off = torch.as_tensor(off.astype(numpy.int32)).to(dev)
+    for a, b in _segment_groups(lens, C * (order * D + 1), max_workspace_bytes):
+        _lib.launch("sc_gmm_topc_stats", dev, x, dt, N, D, C, idx, post, K, lse, d_off[a:], b - a, int(lens[a:b].max()), order, stat0[a:], stat1[a:],
                     None if stat2 is None else stat2[a:], llk[a:])
     out = (stat0, stat1, stat2, llk)
     return tuple(None if t is None else t.cpu().numpy() for t in out) if host else out

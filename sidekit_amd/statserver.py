@@ -193,7 +193,17 @@ class StatServer:
     def accumulate_stat_device(self, ubm, frames, seg_off):
         """Zeroth and first order statistics of every session from resident frames: session i is frames ``[seg_off[i], seg_off[i + 1])``
         of ``frames`` ((N, D) CUDA tensor, float32 or float64).  Fills ``stat0`` (sessions x C) and ``stat1`` (sessions x C D)."""
-        from .mixture import Mixture, gmm_stats_device
+        from .mixture import gmm_stats_device
+        self._accumulate_device(ubm, frames, seg_off, gmm_stats_device)
+
+    def accumulate_stat_topc_device(self, ubm, frames, seg_off, top_c=10):
+        """``accumulate_stat_device`` on the ``top_c`` components per frame that score best under ``ubm`` (between 1 and 32, at most the
+        mixture's own): posteriors renormalised over each frame's list (``mixture.gmm_stats_topc_device``)."""
+        self._accumulate_device(ubm, frames, seg_off, self._stats_topc(ubm, top_c))
+
+    def _accumulate_device(self, ubm, frames, seg_off, gmm_stats_device):
+        """``accumulate_stat_device`` with the statistics from ``gmm_stats_device(ubm, frames, seg_off, order=, max_workspace_bytes=)``"""
+        from .mixture import Mixture
         assert isinstance(ubm, Mixture), 'First parameter has to be a Mixture'
         assert len(seg_off) == self.segset.shape[0] + 1, "seg_off: one offset per session and the end of the last"
         if not ubm.dim() == frames.shape[1]:
@@ -203,12 +213,35 @@ class StatServer:
         self.stat0 = to_host(stat0).astype(STAT_TYPE, copy=False)
         self.stat1 = to_host(stat1).reshape(stat0.shape[0], ubm.sv_size()).astype(STAT_TYPE, copy=False)
 
+    @staticmethod
+    def _stats_topc(ubm, top_c):
+        """``mixture.gmm_stats_topc_device`` at ``top_c`` under ``gmm_stats_device``'s arguments; the mixture and ``top_c`` are checked here"""
+        from . import gmm_scoring
+        from .mixture import Mixture, gmm_stats_topc_device
+        assert isinstance(ubm, Mixture), 'First parameter has to be a Mixture'
+        gmm_scoring._top_c(ubm, top_c)
+
+        def stats(ubm, frames, seg_off, order, max_workspace_bytes):
+            return gmm_stats_topc_device(ubm, frames, seg_off, order=order, top_c=top_c, max_workspace_bytes=max_workspace_bytes)
+        return stats
+
     def accumulate_stat(self, ubm, feature_server, seg_indices=None, channel_extension=("", "_b"), num_thread=1):
         """Statistics of the sessions ``seg_indices`` (all when ``None``) under ``ubm`` (``statserver.py:687-739``).  ``feature_server``: any
         object whose ``load(show, channel=)`` returns ``(cep, vad_label)``; each session is cut to its ``start`` / ``stop`` and to its
         speech frames as in the reference, the sessions are stacked in groups of at most ``ACCUMULATE_BYTES`` of frames and a group is
         one ``gmm_stats_device`` call.  ``num_thread`` is accepted and unused."""
-        from .mixture import Mixture, gmm_stats_device
+        from .mixture import gmm_stats_device
+        self._accumulate(ubm, feature_server, seg_indices, channel_extension, gmm_stats_device)
+
+    def accumulate_stat_topc(self, ubm, feature_server, top_c=10, seg_indices=None, channel_extension=("", "_b"), num_thread=1):
+        """``accumulate_stat`` on the ``top_c`` components per frame that score best under ``ubm`` (between 1 and 32, at most the
+        mixture's own), posteriors renormalised over each frame's list (``mixture.gmm_stats_topc_device``): the same sessions, frames,
+        groups and placement.  ``num_thread`` is accepted and unused."""
+        self._accumulate(ubm, feature_server, seg_indices, channel_extension, self._stats_topc(ubm, top_c))
+
+    def _accumulate(self, ubm, feature_server, seg_indices, channel_extension, gmm_stats_device):
+        """``accumulate_stat`` with a group's statistics from ``gmm_stats_device`` (``_accumulate_group``)"""
+        from .mixture import Mixture
         assert isinstance(ubm, Mixture), 'First parameter has to be a Mixture'
         sessions = self.segset.shape[0]
         if seg_indices is None or self.stat0.shape[0] != sessions or self.stat1.shape[0] != sessions:   # nothing usable is held: every session
