@@ -29,7 +29,7 @@ _LAZY = {
     "mahalanobis_scoring": "iv_scoring", "two_covariance_scoring": "iv_scoring",
     "plda_histograms": "iv_scoring", "plda_range_from_sample": "iv_scoring", "plda_norm_histograms": "iv_scoring",
     "FactorAnalyser": "factor_analyser",
-    "Mixture": "mixture",
+    "Mixture": "mixture", "split_candidates": "mixture", "gmm_topc_refine_device": "mixture", "em_split_topc_device": "mixture",
     "asnorm": "score_normalization", "znorm": "score_normalization", "tnorm": "score_normalization", "ztnorm": "score_normalization",
     "asnorm_trials": "score_normalization", "cohort_stats_device": "score_normalization", "znorm_device": "score_normalization",
     "tnorm_device": "score_normalization", "snorm_device": "score_normalization", "ztnorm_device": "score_normalization",

@@ -128,6 +128,12 @@ GMM_TOPC_STATS_SIGNATURES = {
     "sc_gmm_topc_stats": (ctypes.c_int, [_P, _I32, _I64, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/gmm_topc_em.h (sidekit_amd/mixture.py, top-C EM)
+GMM_TOPC_EM_SIGNATURES = {
+    "sc_gmm_topc_refine": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),
+}
+SC_GMM_TOPC_CAND_MAX = 64   # include/sidekit_amd/gmm_topc_em.h: candidates per frame
+
 # name -> (restype, argtypes); every symbol of include/sidekit_amd/ivector.h (sidekit_amd/factor_analyser.py)
 IVECTOR_SIGNATURES = {
     "sc_tv_gram": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
@@ -181,7 +187,8 @@ def lib():
     for name, (res, args) in (list(SIGNATURES.items()) + list(GAUSSIAN_SIGNATURES.items()) + list(MIXTURE_SIGNATURES.items())
                               + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())
                               + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items()) + list(SVM_SIGNATURES.items())
-                              + list(GMM_TOPC_SIGNATURES.items()) + list(GMM_TOPC_STATS_SIGNATURES.items())):
+                              + list(GMM_TOPC_SIGNATURES.items()) + list(GMM_TOPC_STATS_SIGNATURES.items())
+                              + list(GMM_TOPC_EM_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -9,7 +9,9 @@ control, the split, ``_compute_all``) stays on the host in the reference's opera
 resident frames (float32 or float64, widened in the load) and copy nothing with an N dimension to the host.  Beside the reference's
 surface stand the top-C forms (Gaussian selection; ``include/sidekit_amd/gmm_topc_stats.h``): ``gmm_topc_posteriors_device`` gives the
 posteriors of every frame over its list of ``top_c`` components (``gmm_scoring.gmm_top_components_device``) and
-``gmm_stats_topc_device`` the statistics accumulated from them, ``K D`` of gather work per frame after the lists.  Full covariances
+``gmm_stats_topc_device`` the statistics accumulated from them, ``K D`` of gather work per frame after the lists; and top-C EM
+(``include/sidekit_amd/gmm_topc_em.h``): ``em_split_topc_device`` and ``Mixture.EM_split_topc`` train with the lists handed down the split
+tree (``split_candidates``) and refreshed before every E-step from those candidates alone (``gmm_topc_refine_device``).  Full covariances
 (``invcov.ndim == 3``) raise ``NotImplementedError``; ``read_alize``, ``read_htk``, ``write_alize`` and ``merge`` are not built.  There is
 no CPU fallback; importing the module needs neither a GPU nor torch.
 """
@@ -160,13 +162,17 @@ def _topc_posteriors(torch, ubm, x, dt, K, components):
     else:
         idx = (components if torch.is_tensor(components) else torch.as_tensor(numpy.ascontiguousarray(components))).to(dev).contiguous()
     C = ubm.mu.shape[0]
-    with numpy.errstate(divide="ignore"):   # a zero weight: log 0, B = inf, posterior 0
-        B = -2.0 * (numpy.log(ubm.w) + numpy.log(ubm.cst))
     post = torch.empty((N, K), dtype=torch.float64, device=dev)
     lse = torch.empty(N, dtype=torch.float64, device=dev)
-    _lib.launch("sc_gmm_topc_posteriors", dev, x, dt, N, D, _device_f64(torch, ubm.mu, dev), _device_f64(torch, ubm.invcov, dev),
-                _device_f64(torch, B, dev), C, idx, K, post, lse)
+    _lib.launch("sc_gmm_topc_posteriors", dev, x, dt, N, D, *_topc_model(torch, ubm, dev), C, idx, K, post, lse)
     return idx, post, lse
+
+
+def _topc_model(torch, ubm, dev):
+    """The device operands of the direct-form kernels: ``(mu, invcov, B)``, ``B = -2 (log w + log cst)``"""
+    with numpy.errstate(divide="ignore"):   # a zero weight: log 0, B = inf, posterior 0
+        B = -2.0 * (numpy.log(ubm.w) + numpy.log(ubm.cst))
+    return _device_f64(torch, ubm.mu, dev), _device_f64(torch, ubm.invcov, dev), _device_f64(torch, B, dev)
 
 
 def gmm_topc_posteriors_device(ubm, frames, top_c=10, components=None):
@@ -211,6 +217,105 @@ def gmm_stats_topc_device(ubm, frames, seg_off=None, order=2, top_c=10, componen
                     None if stat2 is None else stat2[a:], llk[a:])
     out = (stat0, stat1, stat2, llk)
     return tuple(None if t is None else t.cpu().numpy() for t in out) if host else out
+
+
+def split_candidates(idx, c_old):
+    """The candidates a split hands down: ``(N, K)`` lists over the ``c_old`` parents -> ``(N, 2 K)`` int32 ``[idx, idx + c_old]``, the
+    children of every listed parent in ``_split_ditribution``'s layout (the lower halves first, then the upper ones); an entry of -1
+    stays -1 in both halves.  A CUDA tensor gives a CUDA tensor, anything else a host array."""
+    if type(idx).__module__.split(".")[0] == "torch":
+        import torch
+        idx = idx.to(torch.int32)
+        return torch.cat((idx, torch.where(idx < 0, idx, idx + int(c_old))), dim=1).contiguous()
+    idx = numpy.asarray(idx, dtype=numpy.int32)
+    return numpy.concatenate((idx, numpy.where(idx < 0, idx, idx + numpy.int32(c_old))), axis=1)
+
+
+def _refine(torch, ubm, x, dt, cand, K, posteriors):
+    """``sc_gmm_topc_refine`` on resident operands -> ``(idx (N, K) int32, post (N, K) or None, lse (N,) or None)``"""
+    N, D = x.shape
+    dev = x.device
+    assert D == ubm.dim(), 'dimension of ubm and features differ: {:d} / {:d}'.format(ubm.dim(), D)
+    assert ubm.invcov.ndim == 2 and ubm.mu.shape == ubm.invcov.shape, "a diagonal mixture has (C, D) means and inverse covariances"
+    idx = torch.empty((N, K), dtype=torch.int32, device=dev)
+    post = torch.empty((N, K), dtype=torch.float64, device=dev) if posteriors else None
+    lse = torch.empty(N, dtype=torch.float64, device=dev) if posteriors else None
+    _lib.launch("sc_gmm_topc_refine", dev, x, dt, N, D, *_topc_model(torch, ubm, dev), ubm.mu.shape[0], cand, cand.shape[1], K, idx, post, lse)
+    return idx, post, lse
+
+
+def gmm_topc_refine_device(ubm, frames, candidates, top_c=10, posteriors=False):
+    """Lists refreshed from candidates (``sc_gmm_topc_refine``, ``include/sidekit_amd/gmm_topc_em.h``): per frame the ``K = min(top_c, C)``
+    entries of its row of ``candidates`` that score best under ``ubm`` (the larger log posterior, at equal values the lower index), in
+    ascending component order, ``2 Kc D`` of work per frame whatever ``C`` is.  ``candidates``: (N, Kc) int32 with ``Kc <= 64``, host
+    array or CUDA tensor; an entry outside [0, C) and the repeat of an earlier entry of its row are ignored, and a row with fewer than
+    ``K`` valid entries gives a list padded with -1.  ``frames``: (N, D) CUDA tensor (float32 or float64) or host array.  Returns ``idx
+    (N, K) int32``, or with ``posteriors`` ``(idx, post (N, K) float64, lse (N,) float64)`` where ``post`` and ``lse`` have the bits of
+    ``gmm_topc_posteriors_device(ubm, frames, top_c, components=idx)``; on the device when the frames were there."""
+    from . import gmm_scoring
+    K = gmm_scoring._top_c(ubm, top_c)
+    shape, dtype = tuple(getattr(candidates, "shape", ())), getattr(candidates, "dtype", type(candidates).__name__)
+    if len(shape) != 2 or shape[0] != numpy.shape(frames)[0] or not 1 <= shape[1] <= _lib.SC_GMM_TOPC_CAND_MAX or str(dtype).split(".")[-1] != "int32":
+        raise ValueError("candidates: ({:d}, Kc) int32 with between 1 and {:d} candidates per frame (got {} {})".format(
+            numpy.shape(frames)[0], _lib.SC_GMM_TOPC_CAND_MAX, shape, dtype))
+    torch = _torch()
+    x, dt, host = _frames(torch, frames)
+    cand = (candidates if torch.is_tensor(candidates) else torch.as_tensor(numpy.ascontiguousarray(candidates))).to(x.device).contiguous()
+    out = _refine(torch, ubm, x, dt, cand, K, posteriors)[:3 if posteriors else 1]
+    if host:
+        out = tuple(t.cpu().numpy() for t in out)
+    return out if posteriors else out[0]
+
+
+class _TopCLevels(object):
+    """The E-steps of ``em_split_topc_device``, one level (the EM steps between two splits) at a time.  It keeps the lists the last level
+    ended with (``None``: every component, the host-side fact after a dense level and before the first split)."""
+
+    def __init__(self, x, top_c, exact_lists_at):
+        self.torch = _torch()
+        self.x, self.dt = x, (_lib.XT_F32 if x.dtype == self.torch.float32 else _lib.XT_F64)
+        self.top_c, self.exact = int(top_c), frozenset(int(c) for c in exact_lists_at)
+        self.idx, self.parents = None, 1
+
+    def _candidates(self, ubm):
+        from . import gmm_scoring
+        C = ubm.mu.shape[0]
+        if C in self.exact:
+            return gmm_scoring.gmm_top_components_device(ubm, self.x, min(2 * self.top_c, _lib.SC_GMM_TOPC_MAX, C))
+        if self.idx is None:
+            everyone = self.torch.arange(self.parents, dtype=self.torch.int32, device=self.x.device)
+            self.idx = everyone.expand(self.x.shape[0], self.parents)
+        return split_candidates(self.idx, self.parents)
+
+    def _expectation(self, ubm, accum, cand):
+        """``Mixture._expectation`` with the posteriors cut to the lists refined from ``cand``: ``sc_gmm_topc_refine``, then
+        ``sc_gmm_topc_stats`` with one segment at order 2"""
+        torch, x, dt = self.torch, self.x, self.dt
+        N, D = x.shape
+        C, dev = ubm.mu.shape[0], x.device
+        idx, post, lse = _refine(torch, ubm, x, dt, cand, self.top_c, True)
+        stat0 = torch.empty((1, C), dtype=torch.float64, device=dev)
+        stat1 = torch.empty((1, C, D), dtype=torch.float64, device=dev)
+        stat2 = torch.empty((1, C, D), dtype=torch.float64, device=dev)
+        llk = torch.empty(1, dtype=torch.float64, device=dev)
+        d_off = torch.as_tensor(numpy.array([0, N], dtype=numpy.int32)).to(dev)
+        _lib.launch("sc_gmm_topc_stats", dev, x, dt, N, D, C, idx, post, self.top_c, lse, d_off, 1, N, 2, stat0, stat1, stat2, llk)
+        accum.w += stat0[0].cpu().numpy()
+        accum.mu += stat1[0].cpu().numpy()
+        accum.invcov += stat2[0].cpu().numpy()
+        return float(llk[0])
+
+    def steps(self, ubm, count, ceil_cov, floor_cov, after_iteration):
+        """``count`` E / M steps of the just-split ``ubm`` -> their log-likelihoods per unit of occupation"""
+        C = ubm.mu.shape[0]
+        if C <= self.top_c:   # dense: Mixture._expectation as it is; afterwards every frame lists 0 .. C - 1
+            self.idx, self.parents = None, C
+            return ubm._em_steps(self.x, count, False, ceil_cov=ceil_cov, floor_cov=floor_cov, after_iteration=after_iteration)
+        cand = self._candidates(ubm)
+        llk = ubm._em_steps(self.x, count, False, ceil_cov=ceil_cov, floor_cov=floor_cov, after_iteration=after_iteration,
+                            expectation=lambda accum, _: self._expectation(ubm, accum, cand))
+        self.idx, self.parents = _refine(self.torch, ubm, self.x, self.dt, cand, self.top_c, False)[0], C   # under the model that is split next
+        return llk
 
 
 class Mixture(object):
@@ -382,14 +487,16 @@ class Mixture(object):
         invcov[0] = 1.0 / invcov[0]
         self._set(numpy.full(distrib_nb, 1.0 / distrib_nb), numpy.stack(means), invcov, 1.0 / invcov)
 
-    def _em_steps(self, x, count, per_frame, stop=None, ceil_cov=10, floor_cov=1e-2, after_iteration=None):
+    def _em_steps(self, x, count, per_frame, stop=None, ceil_cov=10, floor_cov=1e-2, after_iteration=None, expectation=None):
         """``count`` E / M steps on resident frames -> their log-likelihoods, per frame (``per_frame``) or per unit of occupation;
-        ``stop(llk list)`` ends the loop after an M-step"""
+        ``stop(llk list)`` ends the loop after an M-step; ``expectation(accum, x)`` stands in for ``_expectation``"""
         llk = []
         accum = copy.deepcopy(self)
+        if expectation is None:
+            expectation = self._expectation
         for _ in range(count):
             accum._reset()
-            total = self._expectation(accum, x)
+            total = expectation(accum, x)
             llk.append(total / (x.shape[0] if per_frame else accum.w.sum()))
             self._maximization(accum, ceil_cov=ceil_cov, floor_cov=floor_cov)
             if after_iteration is not None:
@@ -412,27 +519,29 @@ class Mixture(object):
         self._set(numpy.ones(1), numpy.zeros((1, D)), numpy.ones((1, D)), numpy.ones((1, D)))
         return self
 
-    def _em_split(self, x, distrib_nb, iterations, init_frames, ceil_cov, floor_cov, before_split=None, after_iteration=None):
+    def _em_split(self, x, distrib_nb, iterations, init_frames, ceil_cov, floor_cov, before_split=None, after_iteration=None, top_c=None,
+                  exact_lists_at=()):
+        """-> the llk list; with ``top_c`` (``em_split_topc_device``) ``(llk list, the lists the last level ended with or None)``"""
         x = _frames(_torch(), x)[0]
         head = x if init_frames is None else x[:init_frames]
         count, first, second, _ = gmm_stats_device(Mixture()._unit(x.shape[1]), head, None, 2)    # sum 1, sum x, sum x^2: no float64 copy of the frames
         self._init_single((first[0, 0] / count[0, 0]).cpu().numpy(), (second[0, 0] / count[0, 0]).cpu().numpy())
+        levels = None if top_c is None else _TopCLevels(x, top_c, exact_lists_at)
         llk = []
         for steps in iterations[:int(numpy.log2(distrib_nb))]:
             if before_split is not None:
                 before_split(self)
             self._split_ditribution()
-            llk += self._em_steps(x, steps, False, ceil_cov=ceil_cov, floor_cov=floor_cov, after_iteration=after_iteration)
-        return llk
+            if levels is None:
+                llk += self._em_steps(x, steps, False, ceil_cov=ceil_cov, floor_cov=floor_cov, after_iteration=after_iteration)
+            else:
+                llk += levels.steps(self, steps, ceil_cov, floor_cov, after_iteration)
+        return llk if levels is None else (llk, levels.idx)
 
-    def EM_split(self, features_server, feature_list, distrib_nb, iterations=(1, 2, 2, 4, 4, 4, 4, 8, 8, 8, 8, 8, 8), num_thread=1,
-                 llk_gain=0.01, save_partial=False, output_file_name="ubm", ceil_cov=10, floor_cov=1e-2):
-        """EM with binary splits (:721-833) -> the list of log-likelihoods per unit of occupation, one per iteration.
-        ``features_server``: any object with ``stack_features(list, start_list=, stop_list=)``; every session is stacked once (the first
-        20, from which the single Gaussian the splits start from is taken, then the rest) and the frames stay on the device over all
-        iterations (``em_split_device``).  An ``IdMap`` feature list gives the sessions (``rightids``) with their starts and stops.
-        ``save_partial`` writes ``<output_file_name>_<C>g.h5`` before every split; ``num_thread`` and ``llk_gain`` are accepted and, as in
-        the reference, unused."""
+    @staticmethod
+    def _stack_for_split(features_server, feature_list):
+        """What ``EM_split`` trains on -> ``(frames, init_frames)``: every session stacked once, the first 20 (from which the single
+        Gaussian the splits start from is taken: ``init_frames`` rows, ``None`` when there are no more sessions) and then the rest"""
         HEAD = 20
         if isinstance(feature_list, IdMap):
             sessions, bounds = feature_list.rightids, (feature_list.start, feature_list.stop)
@@ -448,8 +557,34 @@ class Mixture(object):
         if len(sessions) > HEAD:
             init_frames = features.shape[0]
             features = numpy.concatenate((features, stack(slice(HEAD, None))))
-        save = (lambda m: m.write('{}_{}g.h5'.format(output_file_name, m.get_distrib_nb()), prefix='')) if save_partial else None
-        return self._em_split(features, distrib_nb, iterations, init_frames, ceil_cov, floor_cov, before_split=save)
+        return features, init_frames
+
+    @staticmethod
+    def _save_partial(save_partial, output_file_name):
+        """``before_split`` of ``_em_split``: ``<output_file_name>_<C>g.h5``, or nothing"""
+        return (lambda m: m.write('{}_{}g.h5'.format(output_file_name, m.get_distrib_nb()), prefix='')) if save_partial else None
+
+    def EM_split(self, features_server, feature_list, distrib_nb, iterations=(1, 2, 2, 4, 4, 4, 4, 8, 8, 8, 8, 8, 8), num_thread=1,
+                 llk_gain=0.01, save_partial=False, output_file_name="ubm", ceil_cov=10, floor_cov=1e-2):
+        """EM with binary splits (:721-833) -> the list of log-likelihoods per unit of occupation, one per iteration.
+        ``features_server``: any object with ``stack_features(list, start_list=, stop_list=)``; every session is stacked once (the first
+        20, from which the single Gaussian the splits start from is taken, then the rest) and the frames stay on the device over all
+        iterations (``em_split_device``).  An ``IdMap`` feature list gives the sessions (``rightids``) with their starts and stops.
+        ``save_partial`` writes ``<output_file_name>_<C>g.h5`` before every split; ``num_thread`` and ``llk_gain`` are accepted and, as in
+        the reference, unused."""
+        features, init_frames = self._stack_for_split(features_server, feature_list)
+        return self._em_split(features, distrib_nb, iterations, init_frames, ceil_cov, floor_cov,
+                              before_split=self._save_partial(save_partial, output_file_name))
+
+    def EM_split_topc(self, features_server, feature_list, distrib_nb, iterations=(1, 2, 2, 4, 4, 4, 4, 8, 8, 8, 8, 8, 8), top_c=10, num_thread=1,
+                      llk_gain=0.01, save_partial=False, output_file_name="ubm", ceil_cov=10, floor_cov=1e-2, exact_lists_at=()):
+        """``EM_split`` with Gaussian selection carried down the split tree (``em_split_topc_device``): the same sessions, stacked and
+        saved as ``EM_split`` does, the same start, splits and M-steps; the E-steps of a level with more than ``top_c`` components sum
+        over each frame's ``top_c`` best of the children of the components it listed before the split.  Not in the reference."""
+        _topc_em_arguments(top_c)
+        features, init_frames = self._stack_for_split(features_server, feature_list)
+        return self._em_split(features, distrib_nb, iterations, init_frames, ceil_cov, floor_cov,
+                              before_split=self._save_partial(save_partial, output_file_name), top_c=top_c, exact_lists_at=exact_lists_at)[0]
 
 
 def em_split_device(frames, distrib_nb, iterations=(1, 2, 2, 4, 4, 4, 4, 8, 8, 8, 8, 8, 8), init_frames=None, ceil_cov=10, floor_cov=1e-2,
@@ -460,4 +595,35 @@ def em_split_device(frames, distrib_nb, iterations=(1, 2, 2, 4, 4, 4, 4, 8, 8, 8
     ``llk = sum lse / sum stat0`` per iteration.  ``after_iteration(mixture, llk)`` is called after every M-step."""
     ubm = Mixture()
     llk = ubm._em_split(frames, distrib_nb, iterations, init_frames, ceil_cov, floor_cov, after_iteration=after_iteration)
+    return ubm, llk
+
+
+def _topc_em_arguments(top_c):
+    if not 1 <= int(top_c) <= _lib.SC_GMM_TOPC_MAX:
+        raise ValueError("top_c: between 1 and {:d} components per frame (got {})".format(_lib.SC_GMM_TOPC_MAX, top_c))
+
+
+def em_split_topc_device(frames, distrib_nb, iterations=(1, 2, 2, 4, 4, 4, 4, 8, 8, 8, 8, 8, 8), top_c=10, init_frames=None, ceil_cov=10,
+                         floor_cov=1e-2, exact_lists_at=(), after_iteration=None):
+    """``em_split_device`` with Gaussian selection carried down the split tree -> ``(Mixture, llk list)``: the same start from one
+    Gaussian, the same split, the same host M-step and ``llk = sum lse / sum stat0`` per iteration; only the E-step differs.
+
+    A level (the E / M steps between two splits) with ``C <= top_c`` components runs the dense E-step, so ``top_c >= distrib_nb`` is
+    ``em_split_device`` bit for bit; after it every frame lists all ``C`` components.  A level with ``C > top_c`` takes its candidates
+    once, right after the split: ``split_candidates`` of the lists the previous level ended with -- a split turns component ``c`` into
+    ``c`` and ``c + C / 2``, so the ``top_c`` parents a frame listed give ``2 top_c`` children.  Before every E-step
+    ``sc_gmm_topc_refine`` picks the frame's ``top_c`` best candidates under the current model and forms their posteriors, then
+    ``sc_gmm_topc_stats`` accumulates one segment at order 2: ``2 top_c D`` and ``top_c D`` of gather work per frame whatever ``C`` is,
+    against ``12 C D`` FLOP.  After the level's last M-step the lists are refined once more, so the next split descends from lists made
+    under the model that is split.  ``exact_lists_at``: component counts; at a level whose ``C`` is one of them (and above ``top_c``) the
+    candidates are the ``min(2 top_c, 32, C)`` best of all components under the just-split mixture (``gmm_top_components_device``), not the
+    parents' children: it repairs whatever the lists have drifted by, at the cost of one dense pass per chosen level.
+
+    Nothing with an ``N x C`` footprint exists; resident beside the frames are the candidates (N x 2 top_c int32), the lists, their
+    posteriors and ``lse``.  A component that no frame lists has zero occupation and, as in ``_maximization`` today, is not guarded: its
+    mean and variance become nan.  ``top_c`` between 1 and 32; diagonal covariances.  Not in the reference."""
+    _topc_em_arguments(top_c)
+    ubm = Mixture()
+    llk, _ = ubm._em_split(frames, distrib_nb, iterations, init_frames, ceil_cov, floor_cov, after_iteration=after_iteration, top_c=top_c,
+                           exact_lists_at=exact_lists_at)
     return ubm, llk
