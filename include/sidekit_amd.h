@@ -258,7 +258,8 @@ int sc_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, i
  * that order, so the counts are exactly those of sc_cosine + sc_norm_apply + binning the matrix, which is never formed.  d_mean_e /
  * d_std_e: Ne entries, d_mean_t / d_std_t: Nt entries (sc_cohort_moments or sc_topk_stats produce them); a mean and its std come
  * together and at least one pair is given, anything else is SK_EARG.  A score that normalises to NaN (a zero or non-finite std) has no
- * bin: callers check the stds first (sidekit_amd.iv_scoring.cosine_histograms does).  Everything else -- labels, self_offset, lo / hi /
+ * defined bin (the conversion to an integer comes before the clamp; today it is counted in bin 0, and +-inf in the end bins, as in
+ * sc_cosine_hist): callers check the stds first (sidekit_amd.iv_scoring.cosine_histograms does).  Everything else -- labels, self_offset, lo / hi /
  * nbins, the stream contract -- is sc_cosine_hist's.  zt-norm (t-norm against a z-normalised cohort) is a different chain and not here. */
 int sc_cosine_hist_norm(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, const int32_t* d_labels_e,
                         const int32_t* d_labels_t, int32_t self_offset, const float* d_mean_e, const float* d_std_e,

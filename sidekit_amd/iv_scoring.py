@@ -115,23 +115,34 @@ def _norm_pair(pair, n, side):
 def _histogram_passes(one_pass, lo, hi, bins):
     """``bins`` bins over ``[lo, hi)`` from ``one_pass(a, b)``, which counts every pair into ``HIST_BINS`` bins over ``[a, b)``: one pass for
     ``HIST_BINS`` itself, else ``bins / (HIST_BINS - 2)`` passes, each over a slice of the range with one guard bin either side (bins 0 and
-    ``HIST_BINS - 1`` of a pass hold everything below / above its slice)."""
+    ``HIST_BINS - 1`` of a pass hold everything below / above its slice).
+
+    Every pass bins with its own ``lo`` and scale, so two neighbouring passes round "is this score below the boundary between us"
+    differently: copying the inner bins side by side would count a score within rounding of a boundary twice or not at all.  The passes
+    are therefore joined on CUMULATIVE counts.  Pass ``k`` says how many scores lie below each of its edges (the running sum of its bins:
+    its lower guard at its first edge, guard plus inner bins at its last); at a slice boundary, an edge of two passes, the larger of the
+    two claims stands, and an edge inside a slice never claims less than the boundary under it.  A score that neither pass counted (the
+    upper pass has it in its lower guard, the lower one in its upper guard) thus joins the last inner bin of the lower slice, and one
+    that both counted stays where the lower pass put it and leaves the lowest occupied inner bins of the upper pass.  The fine histogram
+    is the difference of one non-decreasing sequence that starts at 0 and ends at the count of one pass: every score is in exactly one
+    bin, and the bin is a non-decreasing function of the score."""
     if bins == HIST_BINS:
         return one_pass(lo, hi)
     inner = HIST_BINS - 2
     w = (float(hi) - float(lo)) / bins
-    out_t, out_n = numpy.zeros(bins, dtype=numpy.uint64), numpy.zeros(bins, dtype=numpy.uint64)
+    below_t, below_n = numpy.zeros(bins + 1, dtype=numpy.int64), numpy.zeros(bins + 1, dtype=numpy.int64)   # scores under fine edge i
     passes = bins // inner
     for k in range(passes):
         a = float(lo) + k * inner * w
-        ht, hn = one_pass(a - w, a + (inner + 1) * w)
-        for full, part in ((out_t, ht), (out_n, hn)):
-            full[k * inner:(k + 1) * inner] = part[1:-1]
-            if k == 0:
-                full[0] += part[0]
-            if k == passes - 1:
-                full[-1] += part[-1]
-    return out_t, out_n
+        for below, part in zip((below_t, below_n), one_pass(a - w, a + (inner + 1) * w)):
+            claims = numpy.cumsum(part.astype(numpy.int64))                            # claims[j]: scores under the pass's edge j + 1
+            edges = below[k * inner:(k + 1) * inner + 1]                               # a view: fine edges k * inner .. (k + 1) * inner
+            numpy.maximum(edges, claims[:-1], out=edges)
+            below[-1] = claims[-1]                                                     # every pass counts the same scores
+    for below in (below_t, below_n):
+        below[0] = 0                                                                   # what lies under lo is in the first bin
+        numpy.minimum(numpy.maximum.accumulate(below), below[-1], out=below)
+    return numpy.diff(below_t).astype(numpy.uint64), numpy.diff(below_n).astype(numpy.uint64)
 
 
 def _check_bins(bins, exc):
@@ -195,7 +206,12 @@ def cosine_histograms(enroll_vectors, test_vectors, enroll_labels, test_labels, 
     a set scored against itself, a shard's first row for one rank's block of it); ``None`` keeps every pair.  Returns two uint64 arrays of
     ``bins`` equal bins over ``[lo, hi)`` (scores outside land in the end bins); ``bosaris.detplot.eer_from_histograms`` turns them into the
     ROCCH EER.  ``bins``: ``HIST_BINS`` (8192, the kernel's LDS histograms: one pass over the pairs) or a multiple of ``HIST_BINS - 2``: that
-    many finer bins from ``bins / (HIST_BINS - 2)`` passes, each over a slice of the range with one guard bin either side.
+    many finer bins from ``bins / (HIST_BINS - 2)`` passes, each over a slice of the range with one guard bin either side, joined so that
+    every trial is in exactly one bin (``_histogram_passes``).  Scores that are not finite: the rule of the histogram kernels is that a NaN
+    score is in no bin, a raw ``+-inf`` lands in an end bin and a normalised score that is not finite has no bin, and ``plda_histograms``
+    keeps it.  The cosine kernel does NOT yet: it counts ``+-inf`` in the end bins and a NaN in the FIRST bin, normalised or not (a NaN
+    x-vector is a row or column of trials with the lowest possible score) -- through a conversion C++ leaves undefined, kept because the
+    defined one measured slower; ``tests/test_gpu_hist_bins.py`` pins what happens.  Hand over finite vectors.
 
     ``enroll_norm`` / ``test_norm``: ``(mean, std)`` float32 vectors, one entry per enrolment / test row (device tensors are used as
     given; ``score_normalization.cohort_stats_device`` makes them).  The scores are then normalised before they are binned

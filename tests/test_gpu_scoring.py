@@ -295,10 +295,11 @@ def test_cosine_histograms_match_the_score_matrix(gpu):
     eer_h = eer_from_histograms(ht, hn)
     eer_x = rocch2eer(*rocch(S[tar & off].astype(float), S[~tar].astype(float)))
     assert 0.01 < eer_x < 0.4 and abs(eer_h - eer_x) < 5e-4, (eer_h, eer_x)
-    # finer bins (round 6, tests/test_gpu_eer_dtype.py): `bins` a multiple of HIST_BINS - 2 = that many passes of the kernel over slices of [lo, hi)
-    # with one guard bin either side; scores outside the range land in the end bins.  Against numpy on the score matrix with the same edges: a
-    # score within float32 rounding of an edge may sit in the neighbouring bin (the kernel bins (s - lo_pass) * scale in float32; a bin is 4e-5 wide,
-    # so about one score in 400 is that close to an edge) -- each such score moves ONE value of the cumulative counts by one, hence the bound on the
+    # finer bins (tests/test_gpu_eer_dtype.py): `bins` a multiple of HIST_BINS - 2 = that many passes of the kernel over slices of [lo, hi) with one
+    # guard bin either side, joined on cumulative counts (tests/test_gpu_hist_bins.py): every pair is counted exactly once, slice boundaries lose
+    # nothing, and scores outside the range land in the end bins.  Against numpy on the score matrix with the same edges in float64: a score within
+    # float32 rounding of a BIN EDGE may sit in the neighbouring bin (the kernel bins (s - lo_pass) * scale in float32; a bin is 4e-5 wide, so about
+    # one score in 400 is that close to an edge) -- each such score moves ONE value of the cumulative counts by one, hence the bound of 16 on the
     # cumulative difference (observed: 4 of 10^6 pairs), not on the bins
     lo, hi, nf = float(S[off].min()) + 0.05, float(S[off].max()) - 0.02, 3 * (nb - 2)      # some scores below lo and above hi
     hft, hfn = iv_scoring.cosine_histograms(X, X, lab, lab, self_offset=0, lo=lo, hi=hi, bins=nf)
