@@ -29,7 +29,7 @@ SWEEP_M, SWEEP_C = (1, 2, 4, 8, 16, 32, 64), (512, 2048)
 # VGPRs, scratch bytes and LDS of the two kernels (float32 frames): python scripts/kernel_regs.py sidekit_amd/csrc/gmm.hip topc, .../gmm_topc.hip score
 REGISTERS = {"gmm_topc_kernel": {"vgprs": 96, "scratch_bytes": 0, "lds_bytes_D60": {"top_c_5": 77568, "top_c_10": 81408, "top_c_20": 89088},
                                  "workgroups_per_cu_D60": {"top_c_5": 2, "top_c_10": 2, "top_c_20": 1}},
-             "gmm_topc_score_kernel": {"vgprs": 126, "scratch_bytes": 0, "models_per_workgroup": 4,
+             "gmm_topc_score_kernel": {"vgprs": 121, "scratch_bytes": 0, "models_per_workgroup": 4,
                                        "lds_bytes_D60": {"top_c_5": 39680, "top_c_10": 46080, "top_c_20": 58880},
                                        "workgroups_per_cu_D60": {"top_c_5": 4, "top_c_10": 3, "top_c_20": 2}}}
 

@@ -29,7 +29,7 @@ D, GEN_C, HELD_OUT, REPS, STEP_TIMEOUT_S = 60, 1024, 192000, 3, 500
 FRAMES, COMPONENTS, TOP_C = (192000, 2000000), (512, 2048), (10, 20)
 DENSE = ("sc_gmm_frame_loglik", "sc_gmm_stats")
 # VGPRs, scratch bytes and LDS of the kernel (both frame types, -Rpass-analysis=kernel-resource-usage)
-REGISTERS = {"gmm_topc_refine_kernel": {"vgprs": 48, "sgprs": 68, "scratch_bytes": 0, "waves_per_simd": 8,
+REGISTERS = {"gmm_topc_refine_kernel": {"vgprs": 46, "sgprs": 68, "scratch_bytes": 0, "waves_per_simd": 8,
                                         "lds_bytes": {"lists_only": 0, "top_c_10": 5632, "top_c_20": 10752}}}
 
 

@@ -7,10 +7,11 @@
 // Both form lp = -0.5 ([X^2, X] . [invcov, -2 mu invcov]' + A) tile by tile on v_mfma_f64_16x16x4_f64 (one GEMM with K = 2 D), by the
 // same function in the same order (gmm_lp_tile), so pass B recomputes the bits pass A saw.  Recomputing costs 4 C D of the 12 C D FLOP
 // per frame; storing lp would cost N C 8 bytes.  float64 throughout, no floating-point atomics, every sum in a fixed order.
-// gmm_tile.h holds what this file shares with gmm_score.hip, one copy each: the frame load, a segment's rows and slabs (the one place
-// seg_off is read), the log-sum-exp update and merge, the argument checks.  The chunk loop of gmm_lp_tile and the join of a tile's frames
-// at the end of pass A exist a second time in gmm_score.hip, by copy: as shared functions they cost the scoring kernel 0.5 - 1.1 % (DESIGN
-// section 4 "GMM-UBM scoring"), so a change to either is made in both files.
+// gmm_tile.h holds what this file shares with gmm_score.hip and the gmm_topc*.hip files, one copy each: the frame load, a segment's rows
+// and slabs (the one place seg_off is read), the log-sum-exp update, merge and value, the argument checks; it also declares what this
+// file defines for gmm_topc_stats.hip: the segment llk launcher and the two ends of a statistics launcher.  The chunk loop of
+// gmm_lp_tile and the join of a tile's frames at the end of pass A exist a second time in gmm_score.hip, by copy: as shared functions
+// they cost the scoring kernel 0.5 - 1.1 % (DESIGN section 4 "GMM-UBM scoring"), so a change to either is made in both files.
 //
 // One workgroup = 256 threads = 4 waves works on a tile of GT = 64 frames x 64 components; wave w owns components 16 w .. 16 w + 15 of
 // the tile and all 64 frames (four 16 x 16 MFMA tiles, 16 accumulator doubles per lane).  LDS per workgroup, in doubles:
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void gmm_loglik_kernel(const T* __restrict_
     double m = red[tid], s = red[4 * GT + tid];
 #pragma unroll
     for (int w = 1; w < 4; ++w) lse_merge(m, s, red[w * GT + tid], red[(4 + w) * GT + tid]);
-    lse[f0 + tid] = m == -INFINITY ? m : m + log(s);
+    lse[f0 + tid] = lse_value(m, s);
   }
 }
 
@@ -339,6 +340,38 @@ __global__ __launch_bounds__(256) void gmm_seg_llk_kernel(const double* __restri
   if (tid == 0) llk[seg] = red[0];
 }
 
+int launch_gmm_seg_llk(const double* lse, long N, const int* seg_off, int S, long max_len, double* llk, hipStream_t st) {
+  hipLaunchKernelGGL(gmm_seg_llk_kernel, dim3((unsigned)S), dim3(256), 0, st, lse, N, seg_off, max_len, llk);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
+int gmm_stats_lease(hipStream_t st, std::unique_lock<std::mutex>& lock, int S, long max_len, int C, int D, int order, double* stat0,
+                    double* stat1, double* stat2, GmmStatParts* out) {
+  const int nslab = (int)gmm_slabs(max_len);
+  const long n0 = (long)S * C, n1 = n0 * D, n2 = order == 2 ? n1 : 0;
+  *out = {nslab, n0, n1, n2, stat0, stat1, stat2, stat0, stat1, stat2};
+  if (nslab > 1) {
+    void* ws = nullptr;
+    lock.lock();
+    SK_TRY(plda_workspace_locked(st, (size_t)nslab * (n0 + n1 + n2) * 8, &ws));
+    out->p0 = (double*)ws;
+    out->p1 = out->p0 + nslab * n0;
+    out->p2 = out->p1 + nslab * n1;
+  }
+  return SK_OK;
+}
+
+int gmm_stats_finish(const GmmStatParts& p, const double* lse, long N, const int* seg_off, int S, long max_len, double* llk, hipStream_t st) {
+  if (p.nslab > 1) {
+    SK_TRY(launch_slab_reduce(p.p0, p.nslab, p.n0, p.stat0, st));
+    SK_TRY(launch_slab_reduce(p.p1, p.nslab, p.n1, p.stat1, st));
+    if (p.n2) SK_TRY(launch_slab_reduce(p.p2, p.nslab, p.n2, p.stat2, st));
+  }
+  if (llk) SK_TRY(launch_gmm_seg_llk(lse, N, seg_off, S, max_len, llk, st));
+  return SK_OK;
+}
+
 template <typename T>
 static int launch_gmm_loglik(const T* X, long N, int D, const double* mu, const double* invcov, const double* A, int C, double* lse, double* lp,
                              hipStream_t st) {
@@ -377,36 +410,19 @@ template <typename T>
 static int launch_gmm_stats(const T* X, long N, int D, const double* mu, const double* invcov, const double* A, int C, const double* lse,
                             const int* seg_off, int S, long max_len, int order, double* stat0, double* stat1, double* stat2, double* llk,
                             hipStream_t st) {
-  const int nslab = (int)gmm_slabs(max_len), ncols = order == 2 ? 2 * D + 1 : D + 1;
-  const long n0 = (long)S * C, n1 = n0 * D, n2 = order == 2 ? n1 : 0;
-  double *p0 = stat0, *p1 = stat1, *p2 = stat2;
-  std::unique_lock<std::mutex> lock(g_plda_mu, std::defer_lock);
-  if (nslab > 1) {
-    void* ws = nullptr;
-    lock.lock();   // held until the launches that use the workspace are enqueued (see plda_workspace_locked)
-    SK_TRY(plda_workspace_locked(st, (size_t)nslab * (n0 + n1 + n2) * 8, &ws));
-    p0 = (double*)ws;
-    p1 = p0 + nslab * n0;
-    p2 = p1 + nslab * n1;
-  }
-  const int nt = (ncols + 15) / 16;
-#define GMM_STATS(NT) SK_TRY((launch_gmm_stats_nt<NT, T>(X, N, D, mu, invcov, A, C, lse, seg_off, S, max_len, nslab, ncols, p0, p1, p2, st)))
+  const int ncols = order == 2 ? 2 * D + 1 : D + 1, nt = (ncols + 15) / 16;
+  std::unique_lock<std::mutex> lock(g_plda_mu, std::defer_lock);   // held, if gmm_stats_lease takes it, until this function returns
+  GmmStatParts p;
+  SK_TRY(gmm_stats_lease(st, lock, S, max_len, C, D, order, stat0, stat1, stat2, &p));
+#define GMM_STATS(NT) \
+  SK_TRY((launch_gmm_stats_nt<NT, T>(X, N, D, mu, invcov, A, C, lse, seg_off, S, max_len, p.nslab, ncols, p.p0, p.p1, p.p2, st)))
   if (nt <= 2) GMM_STATS(2);
   else if (nt <= 4) GMM_STATS(4);
   else if (nt <= 8) GMM_STATS(8);
   else if (nt <= 12) GMM_STATS(12);
   else GMM_STATS(17);
 #undef GMM_STATS
-  if (nslab > 1) {
-    SK_TRY(launch_slab_reduce(p0, nslab, n0, stat0, st));
-    SK_TRY(launch_slab_reduce(p1, nslab, n1, stat1, st));
-    if (order == 2) SK_TRY(launch_slab_reduce(p2, nslab, n2, stat2, st));
-  }
-  if (llk) {
-    hipLaunchKernelGGL(gmm_seg_llk_kernel, dim3((unsigned)S), dim3(256), 0, st, lse, N, seg_off, max_len, llk);
-    SK_HIP(hipGetLastError());
-  }
-  return SK_OK;
+  return gmm_stats_finish(p, lse, N, seg_off, S, max_len, llk, st);
 }
 
 }  // namespace sk
@@ -441,7 +457,7 @@ int sc_gmm_top_components(const void* d_X, int32_t x_dtype, int64_t N, int32_t D
                           int32_t C, int32_t K, int32_t* d_idx, void* stream) {
   SK_TRY(gmm_check_common("sc_gmm_top_components", d_X, x_dtype, N, D, d_mu, d_invcov, d_A, C));
   SK_CHECK(d_idx, SK_EARG, "sc_gmm_top_components: null argument");
-  SK_CHECK(K >= 1 && K <= C && K <= SC_GMM_TOPC_MAX, SK_EARG, "sc_gmm_top_components: K=%d outside [1, min(C=%d, %d)]", K, C, SC_GMM_TOPC_MAX);
+  SK_TRY(gmm_check_topc("sc_gmm_top_components", K, C));
   if (x_dtype == XT_F32) return launch_gmm_topc((const float*)d_X, (long)N, D, d_mu, d_invcov, d_A, C, K, d_idx, (hipStream_t)stream);
   return launch_gmm_topc((const double*)d_X, (long)N, D, d_mu, d_invcov, d_A, C, K, d_idx, (hipStream_t)stream);
 }

@@ -1,7 +1,7 @@
 // GMM-UBM scoring (sidekit/gmm_scoring.py:53-116): the log-likelihood of every test segment under M mean-adapted models of one diagonal
 // mixture, llk[m][s] = sum_n log sum_c exp lp_m[n][c] (include/sidekit_amd/gmm_scoring.h).  The body is pass A of gmm.hip with a model
-// dimension; the frame load, the segment and its slab, the log-sum-exp update and merge and the argument checks are gmm_tile.h's, the same
-// functions gmm.hip calls; half_gemm and the join of a tile's frames below are copies of gmm.hip's (gmm_lp_tile's chunk loop, pass A's
+// dimension; the frame load, the segment and its slab, the log-sum-exp update, merge and value and the argument checks are gmm_tile.h's,
+// the same functions gmm.hip calls; half_gemm and the join of a tile's frames below are copies of gmm.hip's (gmm_lp_tile's chunk loop, pass A's
 // end), kept identical by hand: lp_m = -0.5 ([X^2, X] . [invcov, -2 mu_m invcov]' + A_m) tile by tile on v_mfma_f64_16x16x4_f64.  The squares' half of that
 // GEMM does not depend on the model, so a workgroup computes it once per component tile for a group of G consecutive models and every
 // model's accumulator starts from it: (1 + G) / 2 G of the FLOP of G separate passes.  float64, no floating-point atomics.
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, G <= 2 ? 2 : 1) void gmm_score_kernel(const T*
         double m = red[tid], s = red[4 * GT + tid];
 #pragma unroll
         for (int w = 1; w < 4; ++w) lse_merge(m, s, red[w * GT + tid], red[(4 + w) * GT + tid]);
-        fl[j * GT + tid] = m == -INFINITY ? m : m + log(s);
+        fl[j * GT + tid] = lse_value(m, s);
       }
     }
     __syncthreads();
@@ -214,17 +214,25 @@ __global__ __launch_bounds__(256, G <= 2 ? 2 : 1) void gmm_score_kernel(const T*
   if (tid < nmod && (!mask || mask[(long)(m0 + tid) * S + seg])) part[((long)slab * M + m0 + tid) * S + seg] = total;
 }
 
-// llk[m][s] = the segment's slab partials in ascending order, for the trials of the mask
+// llk[m][s] = the segment's slab partials in ascending order, for the trials of the mask (gmm_topc.hip's scoring kernel cuts and stores
+// as gmm_score_kernel does and is joined by the same launch)
 __global__ __launch_bounds__(256) void gmm_score_join_kernel(const double* __restrict__ part, long N, const int* __restrict__ seg_off, int S,
                                                              long max_len, long MS, const unsigned char* __restrict__ mask,
                                                              double* __restrict__ llk) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= MS || (mask && !mask[i])) return;
   const int seg = (int)(i % S);
-  const long n = gmm_slabs(gmm_segment(seg_off, seg, N, max_len).len());   // the slots gmm_score_kernel wrote
+  const long n = gmm_slabs(gmm_segment(seg_off, seg, N, max_len).len());   // the slots the scoring kernel wrote
   double s = part[i];
   for (long k = 1; k < n; ++k) s += part[k * MS + i];
   llk[i] = s;
+}
+
+int launch_gmm_score_join(const double* part, long N, const int* seg_off, int S, long max_len, long MS, const unsigned char* mask, double* llk,
+                          hipStream_t st) {
+  hipLaunchKernelGGL(gmm_score_join_kernel, dim3((unsigned)((MS + 255) / 256)), dim3(256), 0, st, part, N, seg_off, S, max_len, MS, mask, llk);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
 }
 
 template <typename T>
@@ -246,10 +254,7 @@ static int launch_gmm_score(const T* X, long N, int D, const double* mus, int M,
   const dim3 grid((unsigned)((long)S * nslab), (unsigned)((M + G - 1) / G));
   hipLaunchKernelGGL((gmm_score_kernel<G, T>), grid, dim3(256), lds, st, X, N, D, mus, M, invcov, A, C, seg_off, S, max_len, nslab, mask, part);
   SK_HIP(hipGetLastError());
-  if (nslab > 1) {
-    hipLaunchKernelGGL(gmm_score_join_kernel, dim3((unsigned)((MS + 255) / 256)), dim3(256), 0, st, part, N, seg_off, S, max_len, MS, mask, llk);
-    SK_HIP(hipGetLastError());
-  }
+  if (nslab > 1) SK_TRY(launch_gmm_score_join(part, N, seg_off, S, max_len, MS, mask, llk, st));
   return SK_OK;
 }
 

@@ -4,23 +4,23 @@
 // K D multiply-adds per frame and model instead of gmm_score.hip's 2 C D: this is gather work for the vector ALU, not for the matrix cores,
 // so lp_m takes the direct form -- no A_m, no cancellation between the squares and the linear half.  float64, no floating-point atomics.
 // The frame load, the segment and its slab, the log-sum-exp update and the argument checks are gmm_tile.h's, the same functions gmm.hip and
-// gmm_score.hip call; the sum of a tile's frames and the join of the slabs are gmm_score.hip's, restated here (that file is not touched).
+// gmm_score.hip call, and so is the join of the slabs (launch_gmm_score_join, gmm_score.hip's kernel); a list entry's operand, its fetch,
+// the lane's terms and the sum over the wave are gmm_topc_tile.h's, the same functions the posteriors and the refinement call at G = 1.
 //
 // One workgroup = 256 threads = 4 waves owns one slab of one segment (gmm_tile.h's cut) and one group of G = 4 consecutive models, and works
 // through the slab's 64-frame tiles in ascending order, a tile in two halves of 32 frames.  Wave w takes frames w, w + 4, ... of the half,
 // one at a time; lane = d (and d + 64 above 64, added to the lane's term before the join).  Per (frame, k) the component c = idx[n][k] is
 // wave-uniform; the lane reads invcov[c][d] and its frame value once and one mean value per model -- a model's row is one coalesced
 // 8 D-byte load -- and the rows of entry k + 1 are fetched while entry k is reduced.  The four models' terms are joined over the 64 lanes
-// by one fixed butterfly that halves the models a lane carries as it goes (xor 32: two of four, xor 16: one of two, then xor 8 .. 1 on
-// that one: 7 exchanges for 4 models; a + b is b + a bit for bit, so every model's sum has the same tree wherever it stands in the group)
-// and lp goes to LDS.  Then thread (frame, model) of the half folds its K values in list order with lse_add: the exponentials, which would
-// otherwise be computed 64 times over by a wave, are computed once.
+// by one fixed butterfly that halves the models a lane carries as it goes (topc_wave_sums) and lp goes to LDS.  Then thread (frame, model)
+// of the half folds its K values in list order with lse_add: the exponentials, which would otherwise be computed 64 times over by a
+// wave, are computed once.
 // LDS, in doubles: Xs 64 x (D | 1), the frame tile, widened;  fl G x 64, the frames' log-likelihoods;  Lp 32 x K x G, a half's lp;  and
 // 64 x K int32, the tile's lists.  At D = 60, K = 10: 46 KB, three workgroups per CU.
 // grid: x = segment * nslab + slab, y = model group: workgroups that are resident together hold different frames and the same group, whose
 // operand (the listed rows of C x D invcov and G x C x D means) then comes from L2.
 #include "../../include/sidekit_amd/gmm_topc.h"
-#include "gmm_tile.h"
+#include "gmm_topc_tile.h"
 #include "kernels.h"
 
 namespace sk {
@@ -32,23 +32,10 @@ __host__ __device__ inline size_t gmm_topc_score_lds(int D, int K) {
   return (size_t)(GT * gmm_xld(D) + TOPC_G * GT + TOPC_H * K * TOPC_G) * 8 + (size_t)GT * K * 4;
 }
 
-// The sums of t[0 .. 4) over the wave's 64 lanes, each in the same fixed order: lane l ends with the sum of t[l >> 4].
-__device__ inline double topc_wave_sums(const double (&t)[4], int lane) {
-  const bool h32 = lane & 32, h16 = lane & 16;
-  double a0 = h32 ? t[2] : t[0], a1 = h32 ? t[3] : t[1];
-  a0 += __shfl_xor(h32 ? t[0] : t[2], 32);
-  a1 += __shfl_xor(h32 ? t[1] : t[3], 32);
-  double v = h16 ? a1 : a0;
-  v += __shfl_xor(h16 ? a0 : a1, 16);
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // Bounds: the slab's rows lie within [0, N] (gmm_segment, gmm_slab) and so do the rows of idx that are read; frames beyond the slab's end
-// are neither read nor added; a component outside [0, C) is skipped before anything is read through it; lanes beyond D read nothing;
-// for models beyond M nothing is read, and what the butterfly carries in their place is neither folded nor stored; Lp is indexed with a
-// frame of the half, k < K and a model of the group; mask and part are indexed with m < M and seg < S only.
+// are neither read nor added; a component outside [0, C) is skipped before anything is read through it and lanes beyond D read nothing
+// (topc_fetch); for models beyond M nothing is read, and what the butterfly carries in their place is neither folded nor stored; Lp is
+// indexed with a frame of the half, k < K and a model of the group; mask and part are indexed with m < M and seg < S only.
 template <int G, typename T>
 __global__ __launch_bounds__(256) void gmm_topc_score_kernel(const T* __restrict__ X, long N, int D, const double* __restrict__ mus, int M,
                                                              const double* __restrict__ invcov, const double* __restrict__ B, int C,
@@ -78,29 +65,8 @@ __global__ __launch_bounds__(256) void gmm_topc_score_kernel(const T* __restrict
   const bool ok0 = lane < D, ok1 = lane + 64 < D;
   const double* mg = mus + (long)m0 * CD;
 
-  // one list entry's operand: the component (-1: nothing to add), its invcov values and the G models' mean values at this lane's d
-  struct Row { int c; double ic0, ic1, mu0[G], mu1[G]; };
-  auto fetch = [&](int f, int k, Row& r) {
-    int c = __builtin_amdgcn_readfirstlane(Is[f * K + k]);
-    if (c < 0 || c >= C) c = -1;
-    r.c = c;
-    r.ic0 = r.ic1 = 0.0;
-#pragma unroll
-    for (int j = 0; j < G; ++j) r.mu0[j] = r.mu1[j] = 0.0;
-    if (c < 0) return;
-    const long row = (long)c * D;
-    if (ok0) {
-      r.ic0 = invcov[row + lane];
-#pragma unroll
-      for (int j = 0; j < G; ++j)
-        if (j < nmod) r.mu0[j] = mg[j * CD + row + lane];
-    }
-    if (two && ok1) {
-      r.ic1 = invcov[row + lane + 64];
-#pragma unroll
-      for (int j = 0; j < G; ++j)
-        if (j < nmod) r.mu1[j] = mg[j * CD + row + lane + 64];
-    }
+  auto fetch = [&](int f, int k, TopcRow<G>& r) {
+    topc_fetch<G>(__builtin_amdgcn_readfirstlane(Is[f * K + k]), C, D, lane, invcov, mg, CD, nmod, r);
   };
 
   double total = 0.0;   // thread j < nmod: model m0 + j's sum over the slab
@@ -115,22 +81,14 @@ __global__ __launch_bounds__(256) void gmm_topc_score_kernel(const T* __restrict
       for (int f = h0 + wave; f < hend; f += 4) {
         const double x0 = ok0 ? Xs[f * xld + lane] : 0.0;
         const double x1 = two && ok1 ? Xs[f * xld + lane + 64] : 0.0;
-        Row cur, nxt;
+        TopcRow<G> cur, nxt;
         fetch(f, 0, cur);
         for (int k = 0; k < K; ++k) {
           if (k + 1 < K) fetch(f, k + 1, nxt);
           double lp = -INFINITY;   // a component outside [0, C): nothing to add
           if (cur.c >= 0) {
             double t[G];
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-              const double e0 = x0 - cur.mu0[j];
-              t[j] = e0 * e0 * cur.ic0;   // 0 for a lane beyond D: x, mu and invcov are 0 there
-              if (two) {
-                const double e1 = x1 - cur.mu1[j];
-                t[j] += e1 * e1 * cur.ic1;
-              }
-            }
+            topc_terms<G>(cur, x0, x1, two, t);
             lp = -0.5 * (topc_wave_sums(t, lane) + B[cur.c]);
           }
           if ((lane & 15) == 0) Lp[((f - h0) * K + k) * G + (lane >> 4)] = lp;   // a model beyond nmod: a value nobody reads
@@ -143,7 +101,7 @@ __global__ __launch_bounds__(256) void gmm_topc_score_kernel(const T* __restrict
         if (f < hend && j < nmod) {
           double m = -INFINITY, s = 0.0;
           for (int k = 0; k < K; ++k) lse_add(m, s, Lp[((f - h0) * K + k) * G + j]);
-          fl[j * GT + f] = m == -INFINITY ? m : m + log(s);
+          fl[j * GT + f] = lse_value(m, s);
         }
       }
       __syncthreads();   // Lp is free
@@ -155,19 +113,6 @@ __global__ __launch_bounds__(256) void gmm_topc_score_kernel(const T* __restrict
     }
   }
   if (tid < nmod && (!mask || mask[(long)(m0 + tid) * S + seg])) part[((long)slab * M + m0 + tid) * S + seg] = total;
-}
-
-// llk[m][s] = the segment's slab partials in ascending order, for the trials of the mask
-__global__ __launch_bounds__(256) void gmm_topc_join_kernel(const double* __restrict__ part, long N, const int* __restrict__ seg_off, int S,
-                                                            long max_len, long MS, const unsigned char* __restrict__ mask,
-                                                            double* __restrict__ llk) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= MS || (mask && !mask[i])) return;
-  const int seg = (int)(i % S);
-  const long n = gmm_slabs(gmm_segment(seg_off, seg, N, max_len).len());   // the slots gmm_topc_score_kernel wrote
-  double s = part[i];
-  for (long k = 1; k < n; ++k) s += part[k * MS + i];
-  llk[i] = s;
 }
 
 template <typename T>
@@ -192,10 +137,7 @@ static int launch_gmm_topc_score(const T* X, long N, int D, const double* mus, i
   hipLaunchKernelGGL((gmm_topc_score_kernel<G, T>), grid, dim3(256), lds, st, X, N, D, mus, M, invcov, B, C, seg_off, S, max_len, nslab, mask, idx, K,
                      part);
   SK_HIP(hipGetLastError());
-  if (nslab > 1) {
-    hipLaunchKernelGGL(gmm_topc_join_kernel, dim3((unsigned)((MS + 255) / 256)), dim3(256), 0, st, part, N, seg_off, S, max_len, MS, mask, llk);
-    SK_HIP(hipGetLastError());
-  }
+  if (nslab > 1) SK_TRY(launch_gmm_score_join(part, N, seg_off, S, max_len, MS, mask, llk, st));
   return SK_OK;
 }
 
@@ -212,7 +154,7 @@ int sc_gmm_score_models_topc(const void* d_X, int32_t x_dtype, int64_t N, int32_
   SK_CHECK(d_seg_off && d_idx && d_llk, SK_EARG, "sc_gmm_score_models_topc: null argument");
   SK_CHECK(M >= 1 && M <= SC_GMM_SCORE_MAX_M, SK_EARG, "sc_gmm_score_models_topc: bad sizes (M=%d with at most %d)", M, SC_GMM_SCORE_MAX_M);
   SK_TRY(gmm_check_segments("sc_gmm_score_models_topc", N, S, max_len));
-  SK_CHECK(K >= 1 && K <= C && K <= SC_GMM_TOPC_MAX, SK_EARG, "sc_gmm_score_models_topc: K=%d outside [1, min(C=%d, %d)]", K, C, SC_GMM_TOPC_MAX);
+  SK_TRY(gmm_check_topc("sc_gmm_score_models_topc", K, C));
   if (x_dtype == XT_F32)
     return launch_gmm_topc_score((const float*)d_X, (long)N, D, d_mus, M, d_invcov, d_B, C, d_seg_off, S, (long)max_len, d_mask, d_idx, K, d_llk,
                                  (hipStream_t)stream);

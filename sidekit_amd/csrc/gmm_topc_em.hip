@@ -2,39 +2,27 @@
 //   sc_gmm_topc_refine   lp[j] = -0.5 (sum_d (X[n][d] - mu[c][d])^2 invcov[c][d] + B[c]), c = cand[n][j] where valid; idx[n] = the K best by
 //                        (lp, then the lower index), ascending; optionally post / lse over idx[n] as sc_gmm_topc_posteriors forms them
 // 2 Kc D of gather work per frame whatever C is: what keeps the lists of EM_split's mixture current between two E-steps (the children of
-// the parents a frame listed) without gmm.hip's pass over all C components.  float64, no atomics, no workspace.  The sum over the 64
-// lanes and the posterior's fold are gmm_topc_stats.hip's (its butterfly restated here, lse_add gmm_tile.h's; that file is not
-// touched): lp, post and lse have the bits gmm_topc_post_kernel forms for the same list.
+// the parents a frame listed) without gmm.hip's pass over all C components.  float64, no atomics, no workspace.  The scoring loop
+// over a row held in a register and the end of a tile of posteriors are gmm_topc_tile.h's, the functions gmm_topc_post_kernel
+// (gmm_topc_stats.hip) calls: lp, post and lse have the bits that kernel forms for the same list.
 //
 // One workgroup = 256 threads = 4 waves owns a tile of GT = 64 frames; wave w takes frames w, w + 4, ... one at a time; lane = d (and
 // d + 64 above 64) in the scoring, lane = candidate in the selection.  The wave holds the frame's row of candidates in a register (lane j:
 // entry j).  An entry is struck out (-1) when it lies outside [0, C) or an earlier lane holds the same value: Kc scalar broadcasts.
-// Scoring is gmm_topc_post_kernel's loop: per entry the component is wave-uniform, a row of invcov and of mu is one coalesced 8 D-byte
+// Scoring is topc_frame_lps: per entry the component is wave-uniform, a row of invcov and of mu is one coalesced 8 D-byte
 // load each, the rows of entry j + 1 are fetched while entry j is reduced; lane j keeps lp[j].  Selection: lane j counts the valid
 // entries that beat its own (Kc broadcasts), the winners are the lanes with fewer than K; a ballot gives them, and a winner's place in
 // the list is the number of winners with a lower component (at most K broadcasts).  With the posteriors, a winner's lp goes to LDS at
 // its place and the tile ends as gmm_topc_post_kernel does: thread f folds frame f's K values in list order, thread (f, k) forms the
 // posterior.  LDS: 64 x K + 64 doubles, 17 KB at K = 32; none without the posteriors.
 #include "../../include/sidekit_amd/gmm_topc_em.h"
-#include "gmm_tile.h"
+#include "gmm_topc_tile.h"
 #include "kernels.h"
 
 namespace sk {
 
-// The sum of t over the wave's 64 lanes in every lane: xor 32, 16, 8 .. 1, gmm_topc_stats.hip's topc_stats_wave_sum bit for bit.
-__device__ inline double topc_em_wave_sum(double t) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-  return t;
-}
-
-// Lane j's double in every lane (j wave-uniform): two scalar broadcasts.
-__device__ inline double topc_em_readlane(double v, int j) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
-}
-
 // Bounds: frames beyond N are neither read nor stored; a frame's row of candidates is read for j < Kc <= 64 only; a candidate outside
-// [0, C) is struck out before anything is read through it; lanes beyond D read nothing; a winner's place is below its frame's number of
+// [0, C) is struck out here (and again by topc_frame_lps) before anything is read through it; a winner's place is below its frame's number of
 // winners <= K, so idx, post and Lp are indexed with a frame of the tile and k < K.
 template <typename T>
 __global__ __launch_bounds__(256) void gmm_topc_refine_kernel(const T* __restrict__ X, long N, int D, const double* __restrict__ mu,
@@ -47,15 +35,11 @@ __global__ __launch_bounds__(256) void gmm_topc_refine_kernel(const T* __restric
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long f0 = (long)blockIdx.x * GT;
   const int nvalid = N - f0 < GT ? (int)(N - f0) : GT;
-  const bool two = D > 64;                      // a second pass over d for lanes d + 64
   const bool ok0 = lane < D, ok1 = lane + 64 < D;
-
-  // one candidate's operand: the component (-1: struck out), its invcov and mean values at this lane's d
-  struct Row { int c; double ic0, ic1, mu0, mu1; };
   for (int f = wave; f < nvalid; f += 4) {
     const long n = f0 + f;
     const double x0 = ok0 ? (double)X[n * D + lane] : 0.0;
-    const double x1 = two && ok1 ? (double)X[n * D + lane + 64] : 0.0;
+    const double x1 = ok1 ? (double)X[n * D + lane + 64] : 0.0;
     int mine = lane < Kc ? cand[n * Kc + lane] : -1;
     if (mine < 0 || mine >= C) mine = -1;
     {
@@ -63,35 +47,11 @@ __global__ __launch_bounds__(256) void gmm_topc_refine_kernel(const T* __restric
       for (int j = 0; j + 1 < Kc; ++j) dup |= j < lane && __builtin_amdgcn_readlane(mine, j) == mine;
       if (dup) mine = -1;
     }
-    auto fetch = [&](int j, Row& r) {
-      const int c = __builtin_amdgcn_readlane(mine, j);
-      r.c = c;
-      r.ic0 = r.ic1 = r.mu0 = r.mu1 = 0.0;
-      if (c < 0) return;
-      const long row = (long)c * D;
-      if (ok0) { r.ic0 = invcov[row + lane]; r.mu0 = mu[row + lane]; }
-      if (two && ok1) { r.ic1 = invcov[row + lane + 64]; r.mu1 = mu[row + lane + 64]; }
-    };
-    double key = -INFINITY, mylp = -INFINITY;   // lane j: the ranking key of entry j (a nan lp ranks as -inf) and its lp as formed
-    Row cur, nxt;
-    fetch(0, cur);
-    for (int j = 0; j < Kc; ++j) {
-      if (j + 1 < Kc) fetch(j + 1, nxt);
-      if (cur.c >= 0) {
-        const double e0 = x0 - cur.mu0;
-        double t = e0 * e0 * cur.ic0;   // 0 for a lane beyond D: x, mu and invcov are 0 there
-        if (two) {
-          const double e1 = x1 - cur.mu1;
-          t += e1 * e1 * cur.ic1;
-        }
-        const double lp = -0.5 * (topc_em_wave_sum(t) + B[cur.c]);
-        if (lane == j) {
-          mylp = lp;
-          key = lp != lp ? -INFINITY : lp;
-        }
-      }
-      if (j + 1 < Kc) cur = nxt;
-    }
+    double mylp = -INFINITY;   // lane j: the lp of entry j as formed, -inf for a struck-out entry
+    topc_frame_lps(x0, x1, mine, Kc, lane, D, mu, invcov, B, C, [&](int j, double lp) {
+      if (lane == j) mylp = lp;
+    });
+    const double key = mylp != mylp ? -INFINITY : mylp;   // its ranking key: a nan lp ranks as -inf
     // how many valid entries beat mine: the larger key, at equal keys the lower component; the valid entries are distinct, so the
     // ranks of the valid lanes are 0 .. (their number) - 1, each once
     int rank = 0;
@@ -117,19 +77,7 @@ __global__ __launch_bounds__(256) void gmm_topc_refine_kernel(const T* __restric
     }
   }
   if (!post) return;   // a kernel argument: the whole workgroup leaves
-  __syncthreads();
-  if (tid < nvalid) {   // the fold over k in list order
-    double m = -INFINITY, s = 0.0;
-    for (int k = 0; k < K; ++k) lse_add(m, s, Lp[tid * K + k]);
-    const double l = m == -INFINITY ? m : m + log(s);
-    fl[tid] = l;
-    lse[f0 + tid] = l;
-  }
-  __syncthreads();
-  for (int e = tid; e < nvalid * K; e += 256) {
-    const double lp = Lp[e], l = fl[e / K];
-    post[f0 * K + e] = lp > -INFINITY && l > -INFINITY ? exp(lp - l) : 0.0;   // -inf and nan: 0 by assignment
-  }
+  topc_fold_and_posteriors(Lp, fl, f0, nvalid, K, post, lse);
 }
 
 template <typename T>
@@ -154,7 +102,7 @@ int sc_gmm_topc_refine(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, c
   SK_CHECK(d_cand && d_idx, SK_EARG, "sc_gmm_topc_refine: null argument");
   SK_CHECK(!d_post == !d_lse, SK_EARG, "sc_gmm_topc_refine: d_post and d_lse are both null or both given");
   SK_CHECK(Kc >= 1 && Kc <= SC_GMM_TOPC_CAND_MAX, SK_EARG, "sc_gmm_topc_refine: Kc=%d outside [1, %d]", Kc, SC_GMM_TOPC_CAND_MAX);
-  SK_CHECK(K >= 1 && K <= C && K <= SC_GMM_TOPC_MAX, SK_EARG, "sc_gmm_topc_refine: K=%d outside [1, min(C=%d, %d)]", K, C, SC_GMM_TOPC_MAX);
+  SK_TRY(gmm_check_topc("sc_gmm_topc_refine", K, C));
   if (x_dtype == XT_F32)
     return launch_gmm_topc_refine((const float*)d_X, (long)N, D, d_mu, d_invcov, d_B, C, d_cand, Kc, K, d_idx, d_post, d_lse, (hipStream_t)stream);
   return launch_gmm_topc_refine((const double*)d_X, (long)N, D, d_mu, d_invcov, d_B, C, d_cand, Kc, K, d_idx, d_post, d_lse, (hipStream_t)stream);

@@ -6,9 +6,10 @@
 //                            and the sum of lse
 // Against gmm.hip's dense route (12 C D FLOP per frame, 8 C D of them pass B) what remains after the lists is K D of gather work per frame
 // for the vector ALU, twice: no N x C array, no matrix cores.  float64, no floating-point atomics (global or LDS), every sum in one
-// fixed order.  The segment and its slab, the log-sum-exp update and the segment checks are gmm_tile.h's; the slab join is kernels.h's
-// launch_slab_reduce, as in gmm.hip; the sum over the 64 lanes is gmm_topc.hip's butterfly for one model and the segment's llk sum is
-// gmm.hip's, both restated here (those files are not touched).
+// fixed order.  The segment and its slab and the argument checks are gmm_tile.h's; the two ends of the statistics launcher (the
+// workspace and its cut, the slab join by launch_slab_reduce and the segment's llk sum) are gmm.hip's, declared there too; the loop over
+// a frame's list and the end of a tile of posteriors are gmm_topc_tile.h's, the same functions gmm_topc_em.hip calls, and their fetch,
+// term and sum over the 64 lanes are the ones gmm_topc.hip's scoring kernel calls for four models.
 //
 // Posteriors.  One workgroup = 256 threads = 4 waves owns a tile of GT = 64 frames; wave w takes frames w, w + 4, ... one at a time;
 // lane = d (and d + 64 above 64, added to the lane's term before the join).  The wave holds the frame's list in a register (lane k:
@@ -26,21 +27,13 @@
 // owning wave alone, whose LDS operations complete in program order: no barrier between hits, no atomics.  Every component block scans
 // the slab's lists (12 K bytes per frame and block, from L2); the frames are read per hit, K rows of D values per frame over all blocks.
 #include "../../include/sidekit_amd/gmm_topc_stats.h"
-#include "gmm_tile.h"
+#include "gmm_topc_tile.h"
 #include "kernels.h"
 
 namespace sk {
 
-// The sum of t over the wave's 64 lanes in every lane: xor 32, 16, 8 .. 1.  This is the tree gmm_topc.hip's topc_wave_sums gives each of
-// its four models (a + b is b + a bit for bit), so a frame's lp has the bits sc_gmm_score_models_topc forms.
-__device__ inline double topc_stats_wave_sum(double t) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-  return t;
-}
-
-// Bounds: frames beyond N are neither read nor stored; a frame's list is read for k < K only; a component outside [0, C) is skipped
-// before anything is read through it; lanes beyond D read nothing; Lp is indexed with a frame of the tile and k < K.
+// Bounds: frames beyond N are neither read nor stored; a frame's list is read for k < K only; what is read through an entry is
+// topc_frame_lps's to bound; Lp is indexed with a frame of the tile and k < K.
 template <typename T>
 __global__ __launch_bounds__(256) void gmm_topc_post_kernel(const T* __restrict__ X, long N, int D, const double* __restrict__ mu,
                                                             const double* __restrict__ invcov, const double* __restrict__ B, int C,
@@ -52,57 +45,17 @@ __global__ __launch_bounds__(256) void gmm_topc_post_kernel(const T* __restrict_
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long f0 = (long)blockIdx.x * GT;
   const int nvalid = N - f0 < GT ? (int)(N - f0) : GT;
-  const bool two = D > 64;                      // a second pass over d for lanes d + 64
   const bool ok0 = lane < D, ok1 = lane + 64 < D;
-
-  // one list entry's operand: the component (-1: nothing to add), its invcov and mean values at this lane's d
-  struct Row { int c; double ic0, ic1, mu0, mu1; };
   for (int f = wave; f < nvalid; f += 4) {
     const long n = f0 + f;
     const double x0 = ok0 ? (double)X[n * D + lane] : 0.0;
-    const double x1 = two && ok1 ? (double)X[n * D + lane + 64] : 0.0;
+    const double x1 = ok1 ? (double)X[n * D + lane + 64] : 0.0;
     const int mine = lane < K ? idx[n * K + lane] : -1;   // K <= 32 < 64
-    auto fetch = [&](int k, Row& r) {
-      int c = __builtin_amdgcn_readlane(mine, k);
-      if (c < 0 || c >= C) c = -1;
-      r.c = c;
-      r.ic0 = r.ic1 = r.mu0 = r.mu1 = 0.0;
-      if (c < 0) return;
-      const long row = (long)c * D;
-      if (ok0) { r.ic0 = invcov[row + lane]; r.mu0 = mu[row + lane]; }
-      if (two && ok1) { r.ic1 = invcov[row + lane + 64]; r.mu1 = mu[row + lane + 64]; }
-    };
-    Row cur, nxt;
-    fetch(0, cur);
-    for (int k = 0; k < K; ++k) {
-      if (k + 1 < K) fetch(k + 1, nxt);
-      double lp = -INFINITY;   // a component outside [0, C): nothing to add
-      if (cur.c >= 0) {
-        const double e0 = x0 - cur.mu0;
-        double t = e0 * e0 * cur.ic0;   // 0 for a lane beyond D: x, mu and invcov are 0 there
-        if (two) {
-          const double e1 = x1 - cur.mu1;
-          t += e1 * e1 * cur.ic1;
-        }
-        lp = -0.5 * (topc_stats_wave_sum(t) + B[cur.c]);
-      }
+    topc_frame_lps(x0, x1, mine, K, lane, D, mu, invcov, B, C, [&](int k, double lp) {
       if (lane == 0) Lp[f * K + k] = lp;
-      if (k + 1 < K) cur = nxt;
-    }
+    });
   }
-  __syncthreads();
-  if (tid < nvalid) {   // the fold over k in list order
-    double m = -INFINITY, s = 0.0;
-    for (int k = 0; k < K; ++k) lse_add(m, s, Lp[tid * K + k]);
-    const double l = m == -INFINITY ? m : m + log(s);
-    fl[tid] = l;
-    lse[f0 + tid] = l;
-  }
-  __syncthreads();
-  for (int e = tid; e < nvalid * K; e += 256) {
-    const double lp = Lp[e], l = fl[e / K];
-    post[f0 * K + e] = lp > -INFINITY && l > -INFINITY ? exp(lp - l) : 0.0;   // -inf and nan: 0 by assignment
-  }
+  topc_fold_and_posteriors(Lp, fl, f0, nvalid, K, post, lse);
 }
 
 __host__ __device__ inline int gmm_topc_stats_ld(int D, int order) { return order * D + 1; }
@@ -173,23 +126,6 @@ __global__ __launch_bounds__(256) void gmm_topc_stats_kernel(const T* __restrict
   }
 }
 
-// llk[s] = sum of lse over segment s: thread t adds frames t, t + 256, ... of the segment, then a tree over the 256 threads (gmm.hip's).
-__global__ __launch_bounds__(256) void gmm_topc_seg_llk_kernel(const double* __restrict__ lse, long N, const int* __restrict__ seg_off,
-                                                               long max_len, double* __restrict__ llk) {
-  __shared__ double red[256];
-  const int tid = threadIdx.x, seg = blockIdx.x;
-  const GmmRows rows = gmm_segment(seg_off, seg, N, max_len);
-  double s = 0.0;
-  for (long i = rows.begin + tid; i < rows.end; i += 256) s += lse[i];
-  red[tid] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) llk[seg] = red[0];
-}
-
 template <typename T>
 static int launch_gmm_topc_post(const T* X, long N, int D, const double* mu, const double* invcov, const double* B, int C, const int* idx, int K,
                                 double* post, double* lse, hipStream_t st) {
@@ -203,33 +139,16 @@ template <typename T>
 static int launch_gmm_topc_stats(const T* X, long N, int D, int C, const int* idx, const double* post, int K, const double* lse,
                                  const int* seg_off, int S, long max_len, int order, double* stat0, double* stat1, double* stat2, double* llk,
                                  hipStream_t st) {
-  const int nslab = (int)gmm_slabs(max_len);
-  const long n0 = (long)S * C, n1 = n0 * D, n2 = order == 2 ? n1 : 0;
-  double *p0 = stat0, *p1 = stat1, *p2 = stat2;
-  std::unique_lock<std::mutex> lock(g_plda_mu, std::defer_lock);
-  if (nslab > 1) {
-    void* ws = nullptr;
-    lock.lock();   // held until the launches that use the workspace are enqueued (see plda_workspace_locked)
-    SK_TRY(plda_workspace_locked(st, (size_t)nslab * (n0 + n1 + n2) * 8, &ws));
-    p0 = (double*)ws;
-    p1 = p0 + nslab * n0;
-    p2 = p1 + nslab * n1;
-  }
+  std::unique_lock<std::mutex> lock(g_plda_mu, std::defer_lock);   // held, if gmm_stats_lease takes it, until this function returns
+  GmmStatParts p;
+  SK_TRY(gmm_stats_lease(st, lock, S, max_len, C, D, order, stat0, stat1, stat2, &p));
   const size_t lds = (size_t)GT * gmm_topc_stats_ld(D, order) * 8;
   SK_TRY(gmm_allow_lds(gmm_topc_stats_kernel<T>, lds));
-  const dim3 grid((unsigned)((long)S * nslab), (unsigned)((C + GT - 1) / GT));
-  hipLaunchKernelGGL(gmm_topc_stats_kernel<T>, grid, dim3(256), lds, st, X, N, D, C, idx, post, K, seg_off, S, max_len, nslab, order, p0, p1, p2);
+  const dim3 grid((unsigned)((long)S * p.nslab), (unsigned)((C + GT - 1) / GT));
+  hipLaunchKernelGGL(gmm_topc_stats_kernel<T>, grid, dim3(256), lds, st, X, N, D, C, idx, post, K, seg_off, S, max_len, p.nslab, order, p.p0, p.p1,
+                     p.p2);
   SK_HIP(hipGetLastError());
-  if (nslab > 1) {
-    SK_TRY(launch_slab_reduce(p0, nslab, n0, stat0, st));
-    SK_TRY(launch_slab_reduce(p1, nslab, n1, stat1, st));
-    if (order == 2) SK_TRY(launch_slab_reduce(p2, nslab, n2, stat2, st));
-  }
-  if (llk) {
-    hipLaunchKernelGGL(gmm_topc_seg_llk_kernel, dim3((unsigned)S), dim3(256), 0, st, lse, N, seg_off, max_len, llk);
-    SK_HIP(hipGetLastError());
-  }
-  return SK_OK;
+  return gmm_stats_finish(p, lse, N, seg_off, S, max_len, llk, st);
 }
 
 }  // namespace sk
@@ -242,7 +161,7 @@ int sc_gmm_topc_posteriors(const void* d_X, int32_t x_dtype, int64_t N, int32_t 
                            int32_t C, const int32_t* d_idx, int32_t K, double* d_post, double* d_lse, void* stream) {
   SK_TRY(gmm_check_common("sc_gmm_topc_posteriors", d_X, x_dtype, N, D, d_mu, d_invcov, d_B, C));
   SK_CHECK(d_idx && d_post && d_lse, SK_EARG, "sc_gmm_topc_posteriors: null argument");
-  SK_CHECK(K >= 1 && K <= C && K <= SC_GMM_TOPC_MAX, SK_EARG, "sc_gmm_topc_posteriors: K=%d outside [1, min(C=%d, %d)]", K, C, SC_GMM_TOPC_MAX);
+  SK_TRY(gmm_check_topc("sc_gmm_topc_posteriors", K, C));
   if (x_dtype == XT_F32)
     return launch_gmm_topc_post((const float*)d_X, (long)N, D, d_mu, d_invcov, d_B, C, d_idx, K, d_post, d_lse, (hipStream_t)stream);
   return launch_gmm_topc_post((const double*)d_X, (long)N, D, d_mu, d_invcov, d_B, C, d_idx, K, d_post, d_lse, (hipStream_t)stream);
@@ -251,11 +170,11 @@ int sc_gmm_topc_posteriors(const void* d_X, int32_t x_dtype, int64_t N, int32_t 
 int sc_gmm_topc_stats(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, int32_t C, const int32_t* d_idx, const double* d_post, int32_t K,
                       const double* d_lse, const int32_t* d_seg_off, int32_t S, int64_t max_len, int32_t order, double* d_stat0, double* d_stat1,
                       double* d_stat2, double* d_llk, void* stream) {
-  SK_TRY(gmm_check_common("sc_gmm_topc_stats", d_X, x_dtype, N, D, d_post, d_post, d_post, C));   // no mixture operand here: post stands in
+  SK_TRY(gmm_check_frames("sc_gmm_topc_stats", d_X, x_dtype, N, D, C));
   SK_CHECK(order == 1 || order == 2, SK_EARG, "sc_gmm_topc_stats: order must be 1 or 2 (got %d)", order);
-  SK_CHECK(d_idx && d_lse && d_seg_off && d_stat0 && d_stat1 && (order == 1 || d_stat2), SK_EARG, "sc_gmm_topc_stats: null argument");
+  SK_CHECK(d_idx && d_post && d_lse && d_seg_off && d_stat0 && d_stat1 && (order == 1 || d_stat2), SK_EARG, "sc_gmm_topc_stats: null argument");
   SK_TRY(gmm_check_segments("sc_gmm_topc_stats", N, S, max_len));
-  SK_CHECK(K >= 1 && K <= C && K <= SC_GMM_TOPC_MAX, SK_EARG, "sc_gmm_topc_stats: K=%d outside [1, min(C=%d, %d)]", K, C, SC_GMM_TOPC_MAX);
+  SK_TRY(gmm_check_topc("sc_gmm_topc_stats", K, C));
   if (x_dtype == XT_F32)
     return launch_gmm_topc_stats((const float*)d_X, (long)N, D, C, d_idx, d_post, K, d_lse, d_seg_off, S, (long)max_len, order, d_stat0, d_stat1,
                                  d_stat2, d_llk, (hipStream_t)stream);

@@ -80,7 +80,9 @@ def _refine(ubm, x, cand, K, posteriors=True):
 SHAPES = [(130, 60, 150, 20, 10),    # two component tiles, two frame tiles plus two rows
           (1, 1, 2, 1, 1),
           (67, 128, 70, 64, 32),     # the second d trip, a full wave of candidates, SC_GMM_TOPC_MAX
-          (130, 65, 40, 7, 10)]      # K > Kc: padding
+          (130, 65, 40, 7, 10),      # K > Kc: padding
+          (70, 64, 70, 10, 5),       # the last D a wave's 64 lanes cover in one pass; a full tile and six frames
+          (70, 65, 70, 10, 5)]       # the first D with a second pass, one lane wide
 
 
 @pytest.mark.parametrize("dtype", [numpy.float32, numpy.float64], ids=["f32", "f64"])

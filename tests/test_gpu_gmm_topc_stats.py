@@ -197,6 +197,24 @@ def test_second_trips_against_the_restatement(gpu):
     assert o2 is None and torch.equal(o0, s0) and torch.equal(o1, s1) and torch.equal(ol, llk)
 
 
+@pytest.mark.parametrize("D", [64, 65])
+def test_posteriors_at_the_second_lane_pass_against_the_restatement(gpu, D):
+    """D = 64: the last size a wave's 64 lanes cover in one pass; D = 65: the first with a second pass, one lane wide.  70 frames (a full
+    tile and six frames), C = 70, K = 5"""
+    import torch
+    from sidekit_amd import mixture
+    ubm, ref, X = _synthetic(D, 70, D, 70)
+    off = numpy.array([0, 70])
+    x = torch.as_tensor(X).to(gpu)
+    idx, post, lse = mixture.gmm_topc_posteriors_device(ubm, x, top_c=5)
+    s0, s1, s2, llk = mixture.gmm_stats_topc_device(ubm, x, off, order=2, top_c=5, components=idx)
+    lists = _np(idx)
+    assert lists.shape == (70, 5) and lists.min() >= 0 and lists.max() < 70
+    r0, r1, r2, rl, rpost, rlse = gsn.stats(ref, X, lists, off)
+    _check({"post": mxn.rel(_np(post), rpost), "lse": mxn.rel(_np(lse), rlse), "stat0": mxn.rel(_np(s0), r0), "stat1": mxn.rel(_np(s1), r1),
+            "stat2": mxn.rel(_np(s2), r2), "llk": mxn.rel(_np(llk), rl), "rows of post sum to 1": numpy.abs(_np(post).sum(1) - 1.0).max()})
+
+
 # ---- 6. the caller's lists --------------------------------------------------------------------------------------------------------------
 def test_callers_lists_invalid_entries_and_zero_weight(gpu):
     import torch
