@@ -2,7 +2,7 @@
 
 Sub-modules mirror the reference package layout for the hot path only:
 ``sidekit_amd.nnet.xvector.Xtractor``, ``sidekit_amd.iv_scoring``, ``sidekit_amd.factor_analyser``, ``sidekit_amd.statserver``,
-``sidekit_amd.bosaris``, ``sidekit_amd.score_normalization``, ``sidekit_amd.lid_utils``, ``sidekit_amd.mixture``, ``sidekit_amd.gmm_scoring``, ``sidekit_amd.jfa_scoring``, ``sidekit_amd.sidekit_io``, ``sidekit_amd.frontend.vad``,
+``sidekit_amd.bosaris``, ``sidekit_amd.score_normalization``, ``sidekit_amd.lid_utils``, ``sidekit_amd.mixture``, ``sidekit_amd.mixture_full``, ``sidekit_amd.gmm_scoring``, ``sidekit_amd.jfa_scoring``, ``sidekit_amd.sidekit_io``, ``sidekit_amd.frontend.vad``,
 ``sidekit_amd.features_server``, ``sidekit_amd.frontend.normfeat``, ``sidekit_amd.frontend.features``, ``sidekit_amd.features_extractor``,
 ``sidekit_amd.svm_training``, ``sidekit_amd.svm_scoring``, ``sidekit_amd.sv_utils``.
 ``install_as_sidekit()`` registers them under the ``sidekit`` names so that reference-style drivers
@@ -30,6 +30,8 @@ _LAZY = {
     "plda_histograms": "iv_scoring", "plda_range_from_sample": "iv_scoring", "plda_norm_histograms": "iv_scoring",
     "FactorAnalyser": "factor_analyser",
     "Mixture": "mixture", "split_candidates": "mixture", "gmm_topc_refine_device": "mixture", "em_split_topc_device": "mixture",
+    "FullMixture": "mixture_full", "frame_loglik_full_device": "mixture_full", "gmm_stats_full_device": "mixture_full",
+    "em_diag2full_device": "mixture_full",
     "asnorm": "score_normalization", "znorm": "score_normalization", "tnorm": "score_normalization", "ztnorm": "score_normalization",
     "asnorm_trials": "score_normalization", "cohort_stats_device": "score_normalization", "znorm_device": "score_normalization",
     "tnorm_device": "score_normalization", "snorm_device": "score_normalization", "ztnorm_device": "score_normalization",
@@ -45,7 +47,7 @@ _LAZY = {
 
 # every module of the mirror, by its reference name
 SUBMODULES = ("bosaris", "bosaris.idmap", "bosaris.ndx", "bosaris.key", "bosaris.scores", "bosaris.detplot", "statserver", "iv_scoring", "factor_analyser",
-              "score_normalization", "lid_utils", "mixture", "gmm_scoring", "jfa_scoring", "sidekit_io", "nnet", "nnet.xvector", "nnet.preprocessor", "frontend", "frontend.vad",
+              "score_normalization", "lid_utils", "mixture", "mixture_full", "gmm_scoring", "jfa_scoring", "sidekit_io", "nnet", "nnet.xvector", "nnet.preprocessor", "frontend", "frontend.vad",
               "features_server", "frontend.normfeat", "frontend.features", "features_extractor", "sv_utils", "svm_training", "svm_scoring")
 
 

@@ -134,6 +134,13 @@ GMM_TOPC_EM_SIGNATURES = {
 }
 SC_GMM_TOPC_CAND_MAX = 64   # include/sidekit_amd/gmm_topc_em.h: candidates per frame
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/gmm_full.h (sidekit_amd/mixture_full.py)
+GMM_FULL_SIGNATURES = {
+    "sc_gmm_full_frame_loglik": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    "sc_gmm_full_stats": (ctypes.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P]),
+}
+SC_GMM_FULL_MAX_D, SC_GMM_FULL_SLAB_TARGET = 96, 1024   # include/sidekit_amd/gmm_full.h
+
 # name -> (restype, argtypes); every symbol of include/sidekit_amd/ivector.h (sidekit_amd/factor_analyser.py)
 IVECTOR_SIGNATURES = {
     "sc_tv_gram": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
@@ -188,7 +195,7 @@ def lib():
                               + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())
                               + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items()) + list(SVM_SIGNATURES.items())
                               + list(GMM_TOPC_SIGNATURES.items()) + list(GMM_TOPC_STATS_SIGNATURES.items())
-                              + list(GMM_TOPC_EM_SIGNATURES.items())):
+                              + list(GMM_TOPC_EM_SIGNATURES.items()) + list(GMM_FULL_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

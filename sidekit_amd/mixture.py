@@ -12,7 +12,7 @@ posteriors of every frame over its list of ``top_c`` components (``gmm_scoring.g
 ``gmm_stats_topc_device`` the statistics accumulated from them, ``K D`` of gather work per frame after the lists; and top-C EM
 (``include/sidekit_amd/gmm_topc_em.h``): ``em_split_topc_device`` and ``Mixture.EM_split_topc`` train with the lists handed down the split
 tree (``split_candidates``) and refreshed before every E-step from those candidates alone (``gmm_topc_refine_device``).  Full covariances
-(``invcov.ndim == 3``) raise ``NotImplementedError``; ``read_alize``, ``read_htk``, ``write_alize`` and ``merge`` are not built.  There is
+(``invcov.ndim == 3``) raise ``NotImplementedError`` here (``mixture_full.FullMixture`` is their class); ``read_alize``, ``read_htk``, ``write_alize`` and ``merge`` are not built.  There is
 no CPU fallback; importing the module needs neither a GPU nor torch.
 """
 import copy
@@ -35,7 +35,8 @@ def _torch():
 
 
 def _full_covariance():
-    return NotImplementedError("full-covariance mixtures (invcov.ndim == 3) are not built: sidekit_amd.mixture is diagonal only")
+    return NotImplementedError("full-covariance mixtures (invcov.ndim == 3) are not built: sidekit_amd.mixture is diagonal only "
+                               "(sidekit_amd.mixture_full.FullMixture is the full-covariance class)")
 
 
 def _frames(torch, frames):

@@ -201,10 +201,16 @@ class StatServer:
         mixture's own): posteriors renormalised over each frame's list (``mixture.gmm_stats_topc_device``)."""
         self._accumulate_device(ubm, frames, seg_off, self._stats_topc(ubm, top_c))
 
-    def _accumulate_device(self, ubm, frames, seg_off, gmm_stats_device):
-        """``accumulate_stat_device`` with the statistics from ``gmm_stats_device(ubm, frames, seg_off, order=, max_workspace_bytes=)``"""
-        from .mixture import Mixture
-        assert isinstance(ubm, Mixture), 'First parameter has to be a Mixture'
+    def accumulate_stat_full_device(self, ubm, frames, seg_off):
+        """``accumulate_stat_device`` under a full-covariance ``mixture_full.FullMixture`` (``gmm_stats_full_device``); nothing else is
+        accepted."""
+        from .mixture_full import FullMixture, gmm_stats_full_device
+        self._accumulate_device(ubm, frames, seg_off, gmm_stats_full_device, accepted=FullMixture)
+
+    def _accumulate_device(self, ubm, frames, seg_off, gmm_stats_device, accepted=None):
+        """``accumulate_stat_device`` with the statistics from ``gmm_stats_device(ubm, frames, seg_off, order=, max_workspace_bytes=)``;
+        ``accepted``: the class ``ubm`` has to be (``None``: ``Mixture``)"""
+        self._check_ubm(ubm, accepted)
         assert len(seg_off) == self.segset.shape[0] + 1, "seg_off: one offset per session and the end of the last"
         if not ubm.dim() == frames.shape[1]:
             raise Exception('dimension of ubm and features differ: {:d} / {:d}'.format(ubm.dim(), frames.shape[1]))
@@ -239,10 +245,23 @@ class StatServer:
         groups and placement.  ``num_thread`` is accepted and unused."""
         self._accumulate(ubm, feature_server, seg_indices, channel_extension, self._stats_topc(ubm, top_c))
 
-    def _accumulate(self, ubm, feature_server, seg_indices, channel_extension, gmm_stats_device):
-        """``accumulate_stat`` with a group's statistics from ``gmm_stats_device`` (``_accumulate_group``)"""
-        from .mixture import Mixture
-        assert isinstance(ubm, Mixture), 'First parameter has to be a Mixture'
+    def accumulate_stat_full(self, ubm, feature_server, seg_indices=None, channel_extension=("", "_b"), num_thread=1):
+        """``accumulate_stat`` under a full-covariance ``mixture_full.FullMixture`` (``statserver.py:731-739`` with ``invcov.ndim == 3``;
+        ``gmm_stats_full_device``): the same sessions, frames, groups and placement; nothing else is accepted.  ``num_thread`` is accepted
+        and unused."""
+        from .mixture_full import FullMixture, gmm_stats_full_device
+        self._accumulate(ubm, feature_server, seg_indices, channel_extension, gmm_stats_full_device, accepted=FullMixture)
+
+    @staticmethod
+    def _check_ubm(ubm, accepted=None):
+        if accepted is None:
+            from .mixture import Mixture as accepted
+        assert isinstance(ubm, accepted), 'First parameter has to be a {}'.format(accepted.__name__)
+
+    def _accumulate(self, ubm, feature_server, seg_indices, channel_extension, gmm_stats_device, accepted=None):
+        """``accumulate_stat`` with a group's statistics from ``gmm_stats_device`` (``_accumulate_group``); ``accepted``: the class ``ubm``
+        has to be (``None``: ``Mixture``)"""
+        self._check_ubm(ubm, accepted)
         sessions = self.segset.shape[0]
         if seg_indices is None or self.stat0.shape[0] != sessions or self.stat1.shape[0] != sessions:   # nothing usable is held: every session
             self.stat0 = numpy.zeros((sessions, ubm.distrib_nb()), dtype=STAT_TYPE)
