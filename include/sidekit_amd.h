@@ -222,7 +222,8 @@ int sk_collect_segments(const void* d_src, int32_t dtype, int64_t src_ld, const 
 /* ---- trial scoring ------------------------------------------------------------------------- */
 
 /* sidekit.iv_scoring.cosine_scoring, the einsum of sidekit/iv_scoring.py:108-109: rows already
- * L2-normalised by the caller (StatServer.norm_stat1).  d_out[i][j] = <E_i, T_j>, float32. */
+ * L2-normalised by the caller (StatServer.norm_stat1).  d_out[i][j] = <E_i, T_j>, float32.  D % 4 == 0, and d_E / d_T on 16-byte
+ * boundaries (rows are read with 16-byte loads): SK_EARG otherwise, here and in sc_cosine_hist, sc_cosine_hist_norm and sc_cohort_moments. */
 int sc_cosine(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, float* d_out, void* stream);
 
 /* sidekit.iv_scoring.fast_PLDA_scoring, sidekit/iv_scoring.py:448-462:

@@ -175,6 +175,9 @@ int plda_workspace_locked(hipStream_t st, size_t bytes, void** out);
 struct PldaPrep { double *epsi, *qe, *qt, *extra; int nparts; };
 int plda_prep_locked(const double* d_E, int32_t Ne, const double* d_T, int32_t Nt, int32_t D, const double* d_Phi, const double* d_Psi,
                      hipStream_t st, PldaPrep* out, size_t extra_doubles = 0);
+// sc_cosine, the cosine histograms and sc_cohort_moments read their float32 rows with 16-byte loads: D % 4 == 0 keeps every row on such a
+// boundary only if the base pointer is on one (a view that starts 4 bytes into a larger buffer is not)
+inline bool aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15u) == 0; }
 
 // ---- plda_train.hip -------------------------------------------------------------------------
 // The cut of a TN product (sc_gemm_tn, sc_scatter_within; sc_class_scatter: `batch` products of the same M x N whose longest K is given):

@@ -263,8 +263,9 @@ __global__ __launch_bounds__(256) void col_moments_kernel(const float* __restric
 
 // ---- adaptive s-norm support (sidekit/score_normalization.py:120-140) -----------------------------------------
 // Mean and unbiased std of the k largest values of every row: an exact radix select on the order-preserving
-// integer image of the floats (four 8-bit passes narrow the k-th largest key), then one pass of sums.  Ties at the
-// threshold contribute exactly the copies torch.topk would keep, so the statistics equal those of any valid top-k.
+// integer image of the floats (four 8-bit passes narrow the k-th largest key), then one pass for the mean and one for the
+// variance centred on it.  Ties at the threshold contribute exactly the copies torch.topk would keep, so the statistics
+// equal those of any valid top-k.
 // sc_topk_stats_f64 is the same kernel at double: eight 8-bit passes over the 64-bit image.
 __device__ inline unsigned fkey(float f) {
   const unsigned u = __builtin_bit_cast(unsigned, f);
@@ -314,29 +315,47 @@ __global__ __launch_bounds__(256) void topk_stats_kernel(const T* __restrict__ x
     mask |= (K)255u << shift;
     __syncthreads();
   }
-  // prefix == key of the k-th largest value; `remaining` copies of it are inside the top-k
-  double s1 = 0.0, s2 = 0.0;
+  // prefix == key of the k-th largest value; `remaining` copies of it are inside the top-k.  The mean first: the values above the
+  // threshold as 256 strided partials added in thread order, then the copies of the threshold.
+  double s1 = 0.0;
   T tval = 0;
   for (int i = tid; i < ncols; i += 256) {
     const T v = row[i];
     const K key = fkey(v);
-    if (key > prefix) { s1 += (double)v; s2 += (double)v * (double)v; }
+    if (key > prefix) s1 += (double)v;
     if (key == prefix) tval = v;
   }
-  red[tid] = s1; red[256 + tid] = s2;
+  red[tid] = s1;
   __shared__ T s_tval;
+  __shared__ double s_mean;
   if (fkey(tval) == prefix) s_tval = tval;   // every writer holds the same value
   __syncthreads();
+  double tv = 0.0;
   if (tid == 0) {
-    double a = 0.0, b = 0.0;
-    for (int q = 0; q < 256; ++q) { a += red[q]; b += red[256 + q]; }
-    const double tv = (double)s_tval;
+    double a = 0.0;
+    for (int q = 0; q < 256; ++q) a += red[q];
+    tv = (double)s_tval;
     a += tv * (double)remaining;
-    b += tv * tv * (double)remaining;
-    const double m = a / (double)k;
-    mean[blockIdx.x] = (T)m;
-    const double var = (b - (double)k * m * m) / (double)(k - 1);
-    stdv[blockIdx.x] = (T)sqrt(var > 0.0 ? var : 0.0);
+    s_mean = a / (double)k;
+    mean[blockIdx.x] = (T)s_mean;
+  }
+  __syncthreads();
+  // The variance CENTRED on that mean, in a second pass over the same keys: sum (v - m)^2 has no cancellation, where the one-pass
+  // (sum v^2 - k m^2) / (k - 1) lost every digit of a double std once mean^2 / var reached 1 / eps (scores of -600 +- 1: 3e-8 relative).
+  const double m = s_mean;
+  double s2 = 0.0;
+  for (int i = tid; i < ncols; i += 256) {
+    const T v = row[i];
+    if (fkey(v) > prefix) { const double d = (double)v - m; s2 += d * d; }
+  }
+  red[256 + tid] = s2;
+  __syncthreads();
+  if (tid == 0) {
+    double b = 0.0;
+    for (int q = 0; q < 256; ++q) b += red[256 + q];
+    const double d = tv - m;
+    b += d * d * (double)remaining;
+    stdv[blockIdx.x] = (T)sqrt(b / (double)(k - 1));
   }
 }
 
@@ -377,6 +396,7 @@ int sc_cohort_moments(const float* d_X, int32_t N, const float* d_C, int32_t M, 
   SK_CHECK(!(M == 1 && self_offset == 0 && N > 0), SK_EARG, "sc_cohort_moments: row 0 keeps no pair (M = 1 and self_offset = 0)");
   if (N == 0) return SK_OK;
   SK_CHECK(d_X && d_C && d_mean && d_std, SK_EARG, "sc_cohort_moments: null pointer");
+  SK_CHECK(aligned16(d_X, d_C), SK_EARG, "sc_cohort_moments: operands must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   // the slab size is a function of M alone (at most 64 slabs, at least two cohort tiles each): N = 1000 against M = 20 000 is
   // 8 row tiles x 53 slabs of workgroups, and a row's summation order is the same whatever N it arrives with

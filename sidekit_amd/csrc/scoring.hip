@@ -496,6 +496,7 @@ extern "C" {
 
 int sc_cosine(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, int32_t D, float* d_out, void* stream) {
   SK_CHECK(d_E && d_T && d_out && Ne > 0 && Nt > 0 && D > 0 && D % 4 == 0, SK_EARG, "sc_cosine: bad arguments (D must be a multiple of 4)");
+  SK_CHECK(aligned16(d_E, d_T), SK_EARG, "sc_cosine: operands must be 16-byte aligned");
   GemmArgs g = gemm_args();
   g.A = d_E; g.lda = D; g.a_rows = Ne; g.W = d_T; g.ldw = D; g.C = d_out; g.ldc = Nt; g.M = Ne; g.N = Nt; g.K = D;
   return launch_gemm(g, (hipStream_t)stream);
@@ -572,6 +573,7 @@ int sc_cosine_hist(const float* d_E, int32_t Ne, const float* d_T, int32_t Nt, i
   SK_CHECK(hist_args_ok(d_E, d_T, d_labels_e, d_labels_t, d_hist_tar, d_hist_non, Ne, Nt, D) && D % 4 == 0, SK_EARG,
            "sc_cosine_hist: bad arguments (D must be a multiple of 4)");
   SK_CHECK(nbins == HB && hi > lo, SK_EARG, "sc_cosine_hist: nbins must be %d and hi > lo", HB);
+  SK_CHECK(aligned16(d_E, d_T), SK_EARG, "sc_cosine_hist: operands must be 16-byte aligned");
   return launch_cosine_hist<HN_NONE>(d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, HistNorm{nullptr, nullptr, nullptr, nullptr}, lo, hi,
                                      d_hist_tar, d_hist_non, (hipStream_t)stream);
 }
@@ -586,6 +588,7 @@ int sc_cosine_hist_norm(const float* d_E, int32_t Ne, const float* d_T, int32_t 
   SK_CHECK((d_mean_e == nullptr) == (d_std_e == nullptr) && (d_mean_t == nullptr) == (d_std_t == nullptr), SK_EARG,
            "sc_cosine_hist_norm: a mean and its std come together");
   SK_CHECK(e || t, SK_EARG, "sc_cosine_hist_norm: need at least one (mean, std) pair");
+  SK_CHECK(aligned16(d_E, d_T), SK_EARG, "sc_cosine_hist_norm: operands must be 16-byte aligned");
   const HistNorm nrm{d_mean_e, d_std_e, d_mean_t, d_std_t};
   hipStream_t st = (hipStream_t)stream;
   if (e && t) return launch_cosine_hist<HN_BOTH>(d_E, Ne, d_T, Nt, D, d_labels_e, d_labels_t, self_offset, nrm, lo, hi, d_hist_tar, d_hist_non, st);

@@ -46,9 +46,11 @@ def _device(device):
 
 
 def _to_device(x, dtype, device):
-    """numpy array or torch tensor (any device) -> contiguous tensor of `dtype` on `device`; a tensor already there is used as is."""
+    """numpy array or torch tensor (any device) -> contiguous tensor of `dtype` on `device`; a tensor already there is used as is, unless
+    it starts off a 16-byte boundary (a view into a larger buffer): the kernels read rows with 16-byte loads, so that one is copied."""
     if torch.is_tensor(x):
-        return x.to(device=device, dtype=dtype).contiguous()
+        x = x.to(device=device, dtype=dtype).contiguous()
+        return x.clone() if x.data_ptr() % 16 else x
     return torch.as_tensor(numpy.ascontiguousarray(x, dtype=numpy.float32 if dtype == torch.float32 else numpy.float64)).to(device)
 
 

@@ -6,7 +6,8 @@ restatement of the normalised scores within the project's +-0.05 % absolute.
 The corpus is the one of tests/test_gpu_scoring.py::test_cosine_histograms_match_the_score_matrix (RandomState(11), 40 speakers, N = 1000,
 D = 256, noise 1.7, unit rows) with a cohort built the same way (RandomState(12), 60 speakers, M = 200).  On the host, in float64, with
 8192 bins over the widened range: exact EER of the whole-cohort s-normalised scores 1.67 %, binned 1.9e-5 away; top-50 adaptive s-norm
-1.74 %, binned 1.7e-5 away; no score in an end bin."""
+1.74 %, binned 1.7e-5 away; no score in an end bin.  sc_cosine, whose products the counts are held to, is itself judged against float64
+in tests/test_gpu_scoring_kernels.py (off D = 256 too: k-tails, the padding branch, both tile forms)."""
 import ctypes
 import json
 import os

@@ -1,5 +1,7 @@
 """Cohort score normalisation on the GPU: sc_cohort_moments / sc_norm_apply / sc_matrix_moments and the Python surface over them
-(sidekit_amd.score_normalization), against the reference's golden results and float64 numpy."""
+(sidekit_amd.score_normalization), against the reference's golden results and float64 numpy.  Where a statistic is held to the device's
+own cohort scores, sc_cosine is the root of trust: tests/test_gpu_scoring_kernels.py is where sc_cosine itself (and sc_topk_stats) is judged
+against float64."""
 import ctypes
 import os
 import sys

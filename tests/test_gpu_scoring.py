@@ -217,8 +217,9 @@ def test_asnorm_golden_and_large(gpu, golden_dir):
 def test_f64_mfma_gemm_ragged_shapes(gpu):
     """sc_plda_fast on sizes that are not multiples of the 64 x 64 x 16 tile (v_mfma_f64_16x16x4_f64 path) vs float64 numpy."""
     rs = numpy.random.RandomState(8)
-    # (2900, 2950, 36) takes the 128 x 128-tile kernel (>= 512 such tiles), the others the 64 x 64 one; odd D = scalar loads
-    for Ne, Nt, D in ((100, 77, 50), (1, 1, 4), (65, 130, 256), (64, 64, 17), (2900, 2950, 36), (2817, 2900, 33)):
+    # (2900, 2950, 36) takes the 128 x 128-tile kernel (>= 512 such tiles), the others the 64 x 64 one; odd D = scalar loads;
+    # D = 65 and 129: plda_prep_kernel's second and third 64-column partial is one column wide
+    for Ne, Nt, D in ((100, 77, 50), (1, 1, 4), (65, 130, 256), (64, 64, 17), (2900, 2950, 36), (2817, 2900, 33), (70, 90, 65), (40, 50, 129)):
         E, T = rs.randn(Ne, D), rs.randn(Nt, D)
         A = rs.randn(D, D)
         Phi, Psi = -(A @ A.T) / D, rs.randn(D, D) / D
