@@ -175,6 +175,12 @@ CEPSTRUM_SIGNATURES = {
 }
 SC_MFCC_MAX_FILT = 128
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/plp.h (sidekit_amd/plp.py)
+PLP_SIGNATURES = {
+    "sc_plp_cepstra": (ctypes.c_int, [_P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+}
+SC_PLP_MIN_BANDS, SC_PLP_MAX_BANDS = 4, 32   # include/sidekit_amd/plp.h: critical bands of a frame
+
 _lib = None
 
 
@@ -195,7 +201,7 @@ def lib():
                               + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())
                               + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items()) + list(SVM_SIGNATURES.items())
                               + list(GMM_TOPC_SIGNATURES.items()) + list(GMM_TOPC_STATS_SIGNATURES.items())
-                              + list(GMM_TOPC_EM_SIGNATURES.items()) + list(GMM_FULL_SIGNATURES.items())):
+                              + list(GMM_TOPC_EM_SIGNATURES.items()) + list(GMM_FULL_SIGNATURES.items()) + list(PLP_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -13,8 +13,10 @@ Differences from the reference:
   * the arithmetic is float32 whatever the signal's type (the reference computes a float64 signal in float64);
   * the energy VAD keeps every frame of a degenerate signal (``sidekit_amd.vad.vad_energy_device``);
   * ``extract`` returns arrays, not an HDF5 handle.
-Not built, refused with ``NotImplementedError``: ``feature_type='plp'``, the ``'snr'``, ``'percentil'``, ``'lbl'`` and ``'dnn'`` detectors,
-noise and reverberation files, ``.sph`` input, and the HDF5 writers ``save``, ``save_list`` and ``save_multispeakers``.
+PLP and RASTA-PLP features come from a class of its own, ``sidekit_amd.plp.PlpExtractor``, which derives from this one;
+``FeaturesExtractor(feature_type='plp')`` itself is refused with ``NotImplementedError``, in a message that names that class.
+Not built, refused with ``NotImplementedError``: the ``'snr'``, ``'percentil'``, ``'lbl'`` and ``'dnn'`` detectors, noise and
+reverberation files, ``.sph`` input, and the HDF5 writers ``save``, ``save_list`` and ``save_multispeakers``.
 """
 import collections
 import os
@@ -45,12 +47,13 @@ def _in_samples(seconds, rate):
     return None if None in (seconds, rate) else int(seconds * rate)
 
 
-def _device_tables(torch, key):
-    """The tables of ``host_tables(*key[1:])`` on device ``key[0]``, from a cache of the ``MAX_TABLES`` most recently used sets"""
+def _device_tables(torch, key, make=None):
+    """The tables of ``make(*key[1:])`` (``host_tables`` unless given) on device ``key[0]``, from a cache of the ``MAX_TABLES`` most
+    recently used sets; the makers take different numbers of arguments, so their keys cannot meet"""
     if key in _tables:
         _tables.move_to_end(key)
     else:
-        _tables[key] = tuple(torch.from_numpy(t).to(key[0]) for t in host_tables(*key[1:]))
+        _tables[key] = tuple(torch.from_numpy(t).to(key[0]) for t in (make or host_tables)(*key[1:]))
         while len(_tables) > MAX_TABLES:
             _tables.popitem(last=False)
     return _tables[key]
@@ -87,6 +90,33 @@ def to_device(signal):
     return wav, torch.tensor([sig.shape[1]], dtype=torch.int32, device=dev)
 
 
+def _resident_batch(torch, wav):
+    """``wav`` (B, L) or (L,) float32 or int16 CUDA with contiguous rows -> the (B, L) tensor; anything else is refused"""
+    if not torch.is_tensor(wav) or not wav.is_cuda:
+        raise RuntimeError("sidekit_amd.features_extractor computes on the GPU only (no CPU fallback): pass a CUDA tensor")
+    if wav.dim() == 1:
+        wav = wav.unsqueeze(0)
+    if wav.dim() != 2 or wav.dtype not in (torch.float32, torch.int16) or wav.stride(1) != 1 or wav.shape[0] < 1 or wav.shape[1] < 1:
+        raise ValueError(f"expected a (B, L) float32 or int16 batch with contiguous rows, got {tuple(wav.shape)} {wav.dtype}")
+    return wav
+
+
+def _frame_offsets(torch, wav, nsamples, window_length, shift_sample):
+    """-> ``(lens int32 (B,), off int64 (B + 1,), N)``: the samples of each row (``nsamples`` or None = L, at most L), the row offsets of
+    the stacked frames, ``max((n_b - window) // shift + 1, 0)`` an utterance, and their number, read back once"""
+    B, L = wav.shape
+    if nsamples is None:
+        lens = torch.full((B,), L, dtype=torch.int32, device=wav.device)
+    else:
+        lens = torch.as_tensor(nsamples).to(device=wav.device, dtype=torch.int32).contiguous()
+        if lens.shape != (B,):
+            raise ValueError(f"nsamples must have shape ({B},)")
+    lens = lens.clamp(max=L)
+    count = (torch.div(lens.to(torch.int64) - window_length, shift_sample, rounding_mode='floor') + 1).clamp(min=0)
+    off = torch.cat((torch.zeros(1, dtype=torch.int64, device=wav.device), count.cumsum(0))).contiguous()
+    return lens, off, int(off[-1].item())
+
+
 def mfcc_device(wav, nsamples=None, *, fs=16000, lowfreq=100, maxfreq=8000, nlinfilt=0, nlogfilt=24, nwin=0.025, nceps=13, shift=0.01, prefac=0.97,
                 scale=1.0, get_spec=False):
     """The cepstral front end of a resident batch: ``wav`` (B, L) float32 or int16 CUDA, ``nsamples`` (B,) or None = L ->
@@ -95,12 +125,7 @@ def mfcc_device(wav, nsamples=None, *, fs=16000, lowfreq=100, maxfreq=8000, nlin
     ``[seg_off[b], seg_off[b + 1])``, ``max((n_b - window) // shift + 1, 0)`` of them.  A sample is multiplied by ``scale`` on load: the
     reference works at the int16 scale, so a float signal in [-1, 1) wants ``scale=32768``."""
     torch = _torch()
-    if not torch.is_tensor(wav) or not wav.is_cuda:
-        raise RuntimeError("sidekit_amd.features_extractor computes on the GPU only (no CPU fallback): pass a CUDA tensor")
-    if wav.dim() == 1:
-        wav = wav.unsqueeze(0)
-    if wav.dim() != 2 or wav.dtype not in (torch.float32, torch.int16) or wav.stride(1) != 1 or wav.shape[0] < 1 or wav.shape[1] < 1:
-        raise ValueError(f"expected a (B, L) float32 or int16 batch with contiguous rows, got {tuple(wav.shape)} {wav.dtype}")
+    wav = _resident_batch(torch, wav)
     B, L = wav.shape
     dev = wav.device
     window_length, shift_sample, n_fft = frame_shape(fs, nwin, shift)
@@ -109,16 +134,7 @@ def mfcc_device(wav, nsamples=None, *, fs=16000, lowfreq=100, maxfreq=8000, nlin
         raise ValueError(f"mfcc: a window of {window_length} samples (n_fft {n_fft}; 256 and 512 are built), a shift of {shift_sample}, {nfilt} filters "
                          f"(1 to {MAX_FILT}) and {nceps} cepstra (1 to filters - 1) are outside what sc_mfcc supports")
     window, bank, lo, hi, dct = _device_tables(torch, (dev, fs, n_fft, window_length, lowfreq, maxfreq, nlinfilt, nlogfilt, nceps))
-    if nsamples is None:
-        lens = torch.full((B,), L, dtype=torch.int32, device=dev)
-    else:
-        lens = torch.as_tensor(nsamples).to(device=dev, dtype=torch.int32).contiguous()
-        if lens.shape != (B,):
-            raise ValueError(f"nsamples must have shape ({B},)")
-    lens = lens.clamp(max=L)
-    count = (torch.div(lens.to(torch.int64) - window_length, shift_sample, rounding_mode='floor') + 1).clamp(min=0)
-    off = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), count.cumsum(0))).contiguous()
-    N = int(off[-1].item())
+    lens, off, N = _frame_offsets(torch, wav, nsamples, window_length, shift_sample)
     D = 1 + nceps + nfilt
     frames = torch.empty((N, D), dtype=torch.float32, device=dev)
     spec = torch.empty((N, n_fft // 2 + 1), dtype=torch.float32, device=dev) if get_spec else None
@@ -188,9 +204,18 @@ class FeaturesExtractor(object):
         return _REPR.format(**vars(self))
 
     # ---- what is refused ---------------------------------------------------------------------------------------------------------------
-    def _check_options(self, noise_file_name=None, reverb_file_name=None):
+    def _check_feature_type(self):
+        if self.feature_type == 'plp':
+            raise NotImplementedError("feature_type='plp' is not built here: sidekit_amd.plp.PlpExtractor extracts plp and RASTA-plp features")
         if self.feature_type != 'mfcc':
             raise NotImplementedError("feature_type={!r} is not built (only 'mfcc')".format(self.feature_type))
+
+    def _check_filter_bank(self):
+        if self.filter_bank not in ("lin", "log"):
+            raise ValueError("filter_bank must be 'lin' or 'log' (got {!r})".format(self.filter_bank))
+
+    def _check_options(self, noise_file_name=None, reverb_file_name=None):
+        self._check_feature_type()
         if self.vad in _UNBUILT_VAD:
             raise NotImplementedError("vad={!r} is not built (None and 'energy' are)".format(self.vad))
         if self.vad not in (None, 'energy'):
@@ -199,8 +224,7 @@ class FeaturesExtractor(object):
             raise NotImplementedError("noise_file_name: adding noise from a file is not built")
         if reverb_file_name is not None:
             raise NotImplementedError("reverb_file_name: adding reverberation from a file is not built")
-        if self.filter_bank not in ("lin", "log"):
-            raise ValueError("filter_bank must be 'lin' or 'log' (got {!r})".format(self.filter_bank))
+        self._check_filter_bank()
 
     def _mfcc_options(self):
         size = {"lin": 0, "log": 0}       # _check_options has let only these two through
@@ -208,13 +232,17 @@ class FeaturesExtractor(object):
         return dict(fs=self.sampling_frequency, lowfreq=self.lower_frequency, maxfreq=self.higher_frequency, nlinfilt=size["lin"], nlogfilt=size["log"],
                     nwin=self.window_size, nceps=self.ceps_number, shift=self.shift, prefac=self.pre_emphasis)
 
+    def _front_end_device(self, wav, nsamples):
+        """-> ``(frames, seg_off)`` of a resident batch, columns energy | cep | fb: the part a subclass with other cepstra replaces"""
+        return mfcc_device(wav, nsamples, **self._mfcc_options())
+
     # ---- the resident batch ------------------------------------------------------------------------------------------------------------
     def extract_batch_device(self, wav, nsamples=None):
         """``wav`` (B, L) float32 or int16 CUDA at the int16 scale, ``nsamples`` (B,) -> ``(frames (N, 1 + ceps_number + filter_bank_size),
         seg_off int64 (B + 1,), labels bool (N,))`` on the device, all columns, no dither: what ``post_process_device`` takes."""
         self._check_options()
         _torch()
-        frames, off = mfcc_device(wav, nsamples, **self._mfcc_options())
+        frames, off = self._front_end_device(wav, nsamples)
         return frames, off, self.vad_labels_device(frames, off)[0]
 
     def vad_labels_device(self, frames, off):

@@ -1,6 +1,7 @@
 """``sidekit.frontend.features``: ``compute_delta`` (``sidekit/frontend/features.py:133-166``, ``sc_feat_delta``) and the cepstral front
 end -- ``mfcc`` and ``power_spectrum`` (:363-477) computed on the GPU (``sc_mfcc``, csrc/cepstrum.hip) from the host-made tables of the
-reference: ``trfbank`` (:226-305), the symmetric Hann window and the orthonormal DCT-II basis.  The reference's PLP extraction is not
+reference: ``trfbank`` (:226-305), the symmetric Hann window and the orthonormal DCT-II basis.  ``plp`` (:888-966) is computed on the GPU
+too (``sidekit_amd.plp``), from the host-made ``fft2barkmx`` bank (:480-522); ``lpc2spec``, whose output the reference discards, is not
 built.  There is no CPU fallback; importing the module needs neither a GPU nor torch."""
 import numpy
 
@@ -19,6 +20,36 @@ def mel2hz(z, htk=True):
     if not htk:
         raise NotImplementedError("mel2hz: htk=False (Slaney's mel scale) is not built")
     return 700. * (10**(z / 2595.) - 1)
+
+
+def hz2bark(f):
+    """Hertz -> bark, the reference's ``6 asinh(f / 600)``"""
+    return 6. * numpy.arcsinh(f / 600.)
+
+
+def bark2hz(z):
+    """bark -> Hertz"""
+    return 600. * numpy.sinh(z / 6.)
+
+
+def fft2barkmx(n_fft, fs, nfilts=0, width=1., minfreq=0., maxfreq=8000):
+    """The weights that sum FFT bins into critical bands -> float64 ``(nfilts, n_fft)`` whose columns above ``n_fft / 2`` are zero:
+    ``nfilts`` bands (0: one per bark and one more) whose centres are equally spaced in bark from ``minfreq`` to ``min(maxfreq, fs / 2)``,
+    each ``10 ** (min(0, d + 0.5, -2.5 (d - 0.5)) / width)`` at a bin ``d`` bark above its centre, computed on the host."""
+    maxfreq = min(maxfreq, fs / 2.)
+    lowest = hz2bark(minfreq)
+    span = hz2bark(maxfreq) - lowest
+    if nfilts == 0:
+        nfilts = numpy.ceil(span) + 1
+    nfilts = int(nfilts)
+    step = span / (nfilts - 1)
+    bins = hz2bark(numpy.arange(n_fft // 2 + 1) * fs / n_fft)
+    wts = numpy.zeros((nfilts, n_fft))
+    for i in range(nfilts):
+        centre = lowest + i * step
+        rising, falling = bins - centre + 0.5, -2.5 * (bins - centre - 0.5)
+        wts[i, :n_fft // 2 + 1] = 10 ** (numpy.minimum(0., numpy.minimum(rising, falling) / width))
+    return wts
 
 
 def _band_edges(lowfreq, maxfreq, nlinfilt, nlogfilt, midfreq):
@@ -137,6 +168,28 @@ def mfcc(input_sig,
     frames = got[0].cpu().numpy().astype(PARAM_TYPE)
     return [frames[:, 1:1 + nceps], frames[:, 0], got[2].cpu().numpy().astype(PARAM_TYPE) if get_spec else None,
             frames[:, 1 + nceps:] if get_mspec else None]
+
+
+def plp(input_sig,
+        nwin=0.025,
+        fs=16000,
+        plp_order=13,
+        shift=0.01,
+        get_spec=False,
+        get_mspec=False,
+        prefac=0.97,
+        rasta=True):
+    """-> ``[cepstra (frames, plp_order), log_energy (frames,), spec or None, post_spectrum or None]``, float32: the liftered cepstra of
+    the LPC model of order ``plp_order - 1`` fitted to the compressed critical-band spectrum (``sidekit_amd.plp``: ``sc_mfcc`` under the
+    ``fft2barkmx`` bank, ``sc_feat_rasta`` with ``rasta``, ``sc_plp_cepstra``), the log-energy, and on request the power spectrum and
+    the compressed critical-band spectrum.  ``rasta=True`` filters with ``normfeat.rasta_filt``, the function the reference means and
+    does not import."""
+    from ..features_extractor import to_device
+    from ..plp import plp_device
+    wav, nsamples = to_device(_signal(input_sig))
+    frames = plp_device(wav, nsamples, fs=fs, nwin=nwin, nceps=plp_order, shift=shift, prefac=prefac, rasta=rasta)[0].cpu().numpy().astype(PARAM_TYPE)
+    spec = power_spectrum(input_sig, fs=fs, win_time=nwin, shift=shift, prefac=prefac)[0] if get_spec else None
+    return [frames[:, 1:1 + plp_order], frames[:, 0], spec, frames[:, 1 + plp_order:] if get_mspec else None]
 
 
 def compute_delta(features, win=3, method='filter', filt=numpy.array([.25, .5, .25, 0, -.25, -.5, -.25])):
