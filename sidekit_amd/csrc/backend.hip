@@ -42,26 +42,17 @@ __global__ __launch_bounds__(256, 2) void whiten_rows_kernel(const TX* __restric
   double2 rx[PX], rr[PR];
   auto fetch = [&](int k0) {
 #pragma unroll
-    for (int q = 0; q < PX; ++q) {   // X: 64 rows x 8 pairs along k, less the centre
-      const int idx = tid + 256 * q, row = idx >> 3, k = k0 + (idx & 7) * 2;
-      const long m = r0 + row;
-      double2 v = {0.0, 0.0};
-      if (m < N) {
-        v = fetch_pair(X + m * D + k, vec_x, k, D);
-        if (mu) {
-          const double2 c = fetch_pair(mu + k, vec_mu, k, D);
-          v.x -= c.x; v.y -= c.y;
-        }
+    for (int q = 0; q < PX; ++q) {   // X: 64 rows along k, less the centre (mu: one row, the same pair of it)
+      const int idx = tid + 256 * q;
+      double2 v = fetch_along_k(X, vec_x, r0, N, k0, D, idx);
+      if (mu && r0 + along_k_row(idx) < N) {
+        const double2 c = fetch_along_k(mu, vec_mu, 0, 1, k0, D, idx & 7);
+        v.x -= c.x; v.y -= c.y;
       }
       rx[q] = v;
     }
 #pragma unroll
-    for (int q = 0; q < PR; ++q) {   // R [D][P]: 16 k x TC/2 pairs along the columns
-      const int idx = tid + 256 * q, kk = idx / (TC / 2), n = n0 + (idx % (TC / 2)) * 2, k = k0 + kk;
-      double2 v = {0.0, 0.0};
-      if (k < D) v = fetch_pair(R + (long)k * P + n, vec_r, n, P);
-      rr[q] = v;
-    }
+    for (int q = 0; q < PR; ++q) rr[q] = fetch_across<TC>(R, vec_r, k0, D, n0, P, tid + 256 * q);   // R [D][P]
   };
   f64x4 acc[4][CT];
 #pragma unroll
@@ -73,13 +64,13 @@ __global__ __launch_bounds__(256, 2) void whiten_rows_kernel(const TX* __restric
     __syncthreads();   // every wave is done reading the previous k-tile
 #pragma unroll
     for (int q = 0; q < PX; ++q) {
-      const int idx = tid + 256 * q, row = idx >> 3, kp = (idx & 7) * 2;
-      As[row * DLD + kp] = rx[q].x; As[row * DLD + kp + 1] = rx[q].y;
+      const int at = along_k_at(tid + 256 * q);
+      As[at] = rx[q].x; As[at + 1] = rx[q].y;
     }
 #pragma unroll
     for (int q = 0; q < PR; ++q) {
-      const int idx = tid + 256 * q, kk = idx / (TC / 2), np = (idx % (TC / 2)) * 2;
-      Bs[np * DLD + kk] = rr[q].x; Bs[(np + 1) * DLD + kk] = rr[q].y;
+      const int idx = tid + 256 * q, kk = across_k<TC>(idx), np = across_col<TC>(idx);   // across_at's places, spelled as before: through
+      Bs[np * DLD + kk] = rr[q].x; Bs[(np + 1) * DLD + kk] = rr[q].y;                      // across_at, CT = 4 takes one register more
     }
     __syncthreads();
     if (k0 + DK < D) fetch(k0 + DK);

@@ -1,4 +1,7 @@
-// The f64 MFMA GEMM tile shared by trial scoring (scoring.hip) and PLDA training (plda_train.hip).
+// The f64 MFMA GEMM tile of the float64 back end (scoring.hip, score_norm.hip, plda_train.hip, gaussian_backend.hip, ivector.hip, jfa.hip)
+// and what its users share beside it: the pair loader (fetch_pair), the two operand layouts and their LDS places (fetch_along_k / along_k_at,
+// fetch_across / across_at; whiten_rows_kernel of backend.hip, whose wave grid is its own, stands on these too), the accumulators' lane map
+// (dgemm_lanes) and the plain guarded store of a tile (dgemm_store_tile).
 #pragma once
 #include "common.h"
 
@@ -26,7 +29,7 @@ template <typename T> struct pair_of;
 template <> struct pair_of<double> { typedef double2 type; };
 template <> struct pair_of<float> { typedef float2 type; };
 
-// elements i, i + 1 of a row of n (zero beyond it); vec: the pair may be read with one load
+// elements i, i + 1 of a row of n (zero beyond it); vec: the pair may be read with one load.  The one place a pair is read.
 template <typename T>
 __device__ inline double2 fetch_pair(const T* __restrict__ src, bool vec, int i, int n) {
   double2 v = {0.0, 0.0};
@@ -38,6 +41,68 @@ __device__ inline double2 fetch_pair(const T* __restrict__ src, bool vec, int i,
     if (i + 1 < n) v.y = (double)src[1];
   }
   return v;
+}
+
+// The two operand layouts of a k-tile, by the thread's pair number idx: which pair it fetches, and where the pair goes in the LDS image
+// ([row][k], DLD doubles per row).
+//   "along k": src is [rows][K]; 8 threads take the 8 pairs of row r0 + along_k_row(idx); zero beyond `rows` and K.  I: the type of the
+//   row numbers (int, or long where a row number times K passes 2^31).
+__device__ inline int along_k_row(int idx) { return idx >> 3; }
+
+template <typename T, typename I>
+__device__ inline double2 fetch_along_k(const T* __restrict__ src, bool vec, I r0, I rows, int k0, int K, int idx) {
+  const I r = r0 + along_k_row(idx);
+  const int k = k0 + (idx & 7) * 2;
+  double2 v = {0.0, 0.0};
+  if (r < rows) v = fetch_pair(src + (long)r * K + k, vec, k, K);
+  return v;
+}
+
+__device__ inline int along_k_at(int idx) { return along_k_row(idx) * DLD + (idx & 7) * 2; }   // the pair's place in LDS: [at], [at + 1]
+
+//   "across": src is [K][cols]; TC / 2 threads take the pairs of k-row k0 + across_k(idx), from column c0 + across_col(idx) on; zero
+//   beyond K and `cols`.  TC: the columns of the tile.
+template <int TC> __device__ inline int across_k(int idx) { return idx / (TC / 2); }
+template <int TC> __device__ inline int across_col(int idx) { return (idx % (TC / 2)) * 2; }
+
+template <int TC, typename T>
+__device__ inline double2 fetch_across(const T* __restrict__ src, bool vec, int k0, int K, int c0, int cols, int idx) {
+  const int k = k0 + across_k<TC>(idx), c = c0 + across_col<TC>(idx);
+  double2 v = {0.0, 0.0};
+  if (k < K) v = fetch_pair(src + (long)k * cols + c, vec, c, cols);
+  return v;
+}
+
+template <int TC> __device__ inline int across_at(int idx) { return across_col<TC>(idx) * DLD + across_k<TC>(idx); }   // [at], [at + DLD]
+
+// Where a lane's accumulators lie in dgemm_tile's workgroup tile (four waves, 2 x 2): acc[i][j][q] is row row(i, q), column col(j).
+template <int WT>
+struct dgemm_lanes {
+  int wm, wn, lr, lk;
+  __device__ dgemm_lanes() {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    wm = wave >> 1; wn = wave & 1; lr = lane & 15; lk = lane >> 4;
+  }
+  __device__ int row(int i, int q) const { return wm * 16 * WT + i * 16 + lk + 4 * q; }
+  __device__ int col(int j) const { return wn * 16 * WT + j * 16 + lr; }
+};
+
+// dst[m][n] = the tile's element (m, n) for m < M and n < N; ld doubles per row of dst
+template <int WT>
+__device__ inline void dgemm_store_tile(const f64x4 (&acc)[WT][WT], const dgemm_lanes<WT>& at, double* __restrict__ dst, int ld, int m0, int n0,
+                                        int M, int N) {
+#pragma unroll
+  for (int i = 0; i < WT; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int m = m0 + at.row(i, q);
+      if (m >= M) continue;
+#pragma unroll
+      for (int j = 0; j < WT; ++j) {
+        const int n = n0 + at.col(j);
+        if (n < N) dst[(long)m * ld + n] = acc[i][j][q];
+      }
+    }
 }
 
 template <int WT, bool B_KN, bool A_KM = false, typename TA = double, typename TB = double, bool ROWC = false>
@@ -66,16 +131,8 @@ __device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict
 #pragma unroll
     for (int q = 0; q < PA; ++q) {
       const int idx = tid + 256 * q;
-      if constexpr (!A_KM) {  // A: T rows x 8 pairs along k
-        const int row = idx >> 3, kp = (idx & 7) * 2, m = m0 + row, k = k0 + kp;
-        double2 v = {0.0, 0.0};
-        if (m < M) {
-          const double* src = A + (long)m * K + k;
-          if (vec_a && k + 1 < K) v = *reinterpret_cast<const double2*>(src);
-          else { if (k < K) v.x = src[0]; if (k + 1 < K) v.y = src[1]; }
-        }
-        ra[q] = v;
-      } else if constexpr (ROWC) {  // A [K][M] and the same rows again as B, each less its class's mean (rows of ca are M long: N = M)
+      if constexpr (ROWC) {  // A [K][M] and the same rows again as B, each less its class's mean (rows of ca are M long: N = M).
+        // The "across" layout in its own spelling, here and in stage: through the shared functions sc_scatter_within measured slower.
         const int kk = idx / (T / 2), mp = (idx % (T / 2)) * 2, m = m0 + mp, n = n0 + mp, k = k0 + kk;
         double2 va = {0.0, 0.0}, vb = {0.0, 0.0};
         double wk = 0.0;
@@ -90,37 +147,16 @@ __device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict
           }
         }
         ra[q] = va; rb[q] = vb; rw[q] = wk;
-      } else {  // A [K][M]: 16 k x T/2 pairs along m
-        const int kk = idx / (T / 2), mp = (idx % (T / 2)) * 2, m = m0 + mp, k = k0 + kk;
-        double2 v = {0.0, 0.0};
-        if (k < K) v = fetch_pair(A + (long)k * M + m, vec_a, m, M);
-        ra[q] = v;
-        rw[q] = k < K ? (w ? w[k] : 1.0) : 0.0;
-      }
-      if constexpr (!B_KN) {
-        const int row = idx >> 3, kp = (idx & 7) * 2, n = n0 + row, k = k0 + kp;
-        double2 v = {0.0, 0.0};
-        if (n < N) {
-          const double* src = B + (long)n * K + k;
-          if (vec_b && k + 1 < K) v = *reinterpret_cast<const double2*>(src);
-          else { if (k < K) v.x = src[0]; if (k + 1 < K) v.y = src[1]; }
-        }
-        rb[q] = v;
-      } else if constexpr (ROWC) {  // fetched with A above
-      } else if constexpr (!A_KM) {  // B [K][N]: 16 k x T/2 pairs along n
-        const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2, n = n0 + np, k = k0 + kk;
-        double2 v = {0.0, 0.0};
-        if (k < K) {
-          const double* src = B + (long)k * N + n;
-          if (vec_b && n + 1 < N) v = *reinterpret_cast<const double2*>(src);
-          else { if (n < N) v.x = src[0]; if (n + 1 < N) v.y = src[1]; }
-        }
-        rb[q] = v;
       } else {
-        const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2, n = n0 + np, k = k0 + kk;
-        double2 v = {0.0, 0.0};
-        if (k < K) v = fetch_pair(B + (long)k * N + n, vec_b, n, N);
-        rb[q] = v;
+        if constexpr (A_KM) {
+          const int k = k0 + across_k<T>(idx);
+          ra[q] = fetch_across<T>(A, vec_a, k0, K, m0, M, idx);
+          rw[q] = k < K ? (w ? w[k] : 1.0) : 0.0;
+        } else {
+          ra[q] = fetch_along_k(A, vec_a, m0, M, k0, K, idx);
+        }
+        if constexpr (B_KN) rb[q] = fetch_across<T>(B, vec_b, k0, K, n0, N, idx);
+        else rb[q] = fetch_along_k(B, vec_b, n0, N, k0, K, idx);
       }
     }
   };
@@ -128,14 +164,19 @@ __device__ inline void dgemm_tile(const TA* __restrict__ A, const TB* __restrict
 #pragma unroll
     for (int q = 0; q < PA; ++q) {
       const int idx = tid + 256 * q;
-      const int row = idx >> 3, kp = (idx & 7) * 2;
-      const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2;
-      if constexpr (!A_KM) { As[row * DLD + kp] = ra[q].x; As[row * DLD + kp + 1] = ra[q].y; }
-      else if constexpr (ROWC) { As[np * DLD + kk] = ra[q].x * rw[q]; As[(np + 1) * DLD + kk] = ra[q].y * rw[q]; }
-      else { As[np * DLD + kk] = (ra[q].x - cs[np]) * rw[q]; As[(np + 1) * DLD + kk] = (ra[q].y - cs[np + 1]) * rw[q]; }
-      if constexpr (!B_KN) { Bs[row * DLD + kp] = rb[q].x; Bs[row * DLD + kp + 1] = rb[q].y; }
-      else if constexpr (!A_KM || ROWC) { Bs[np * DLD + kk] = rb[q].x; Bs[(np + 1) * DLD + kk] = rb[q].y; }
-      else { Bs[np * DLD + kk] = rb[q].x - cs[T + np]; Bs[(np + 1) * DLD + kk] = rb[q].y - cs[T + np + 1]; }
+      if constexpr (ROWC) {   // in its own spelling, as in fetch
+        const int kk = idx / (T / 2), np = (idx % (T / 2)) * 2;
+        As[np * DLD + kk] = ra[q].x * rw[q]; As[(np + 1) * DLD + kk] = ra[q].y * rw[q];
+        Bs[np * DLD + kk] = rb[q].x; Bs[(np + 1) * DLD + kk] = rb[q].y;
+      } else {
+        const int along = along_k_at(idx), x = across_at<T>(idx), y = x + DLD;
+        const int c = across_col<T>(idx);   // the column whose centre cs holds (A_KM)
+        if constexpr (!A_KM) { As[along] = ra[q].x; As[along + 1] = ra[q].y; }
+        else { As[x] = (ra[q].x - cs[c]) * rw[q]; As[y] = (ra[q].y - cs[c + 1]) * rw[q]; }
+        if constexpr (!B_KN) { Bs[along] = rb[q].x; Bs[along + 1] = rb[q].y; }
+        else if constexpr (!A_KM) { Bs[x] = rb[q].x; Bs[y] = rb[q].y; }
+        else { Bs[x] = rb[q].x - cs[T + c]; Bs[y] = rb[q].y - cs[T + c + 1]; }
+      }
     }
   };
 #pragma unroll

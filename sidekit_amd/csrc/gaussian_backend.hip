@@ -30,8 +30,7 @@ __global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void class_scatter_kernel(con
   __shared__ __attribute__((aligned(16))) double As[TL * DLD];
   __shared__ __attribute__((aligned(16))) double Bs[TL * DLD];
   __shared__ double cs[2 * TL];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const dgemm_lanes<WT> at;
   const int m0 = blockIdx.y * TL, n0 = blockIdx.x * TL;
   const int c = blockIdx.z % C, s = blockIdx.z / C;
   long r0 = class_off[c], r1 = class_off[c + 1];
@@ -43,19 +42,7 @@ __global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void class_scatter_kernel(con
   const double* mean = Mc + (long)c * D;
   f64x4 acc[WT][WT];
   dgemm_tile<WT, true, true, T, T>(rows, rows, D, D, kl, m0, n0, As, Bs, acc, nullptr, mean, mean, cs);
-  double* dst = out + (long)blockIdx.z * D * D;
-#pragma unroll
-  for (int i = 0; i < WT; ++i)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int m = m0 + wm * 16 * WT + i * 16 + lk + 4 * q;
-      if (m >= D) continue;
-#pragma unroll
-      for (int j = 0; j < WT; ++j) {
-        const int n = n0 + wn * 16 * WT + j * 16 + lr;
-        if (n < D) dst[(long)m * D + n] = acc[i][j][q];
-      }
-    }
+  dgemm_store_tile(acc, at, out + (long)blockIdx.z * D * D, D, m0, n0, D, D);
 }
 
 // ---- heteroscedastic log-likelihoods -----------------------------------------------------------------------------------------------
@@ -88,8 +75,8 @@ __global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void gauss_loglik_kernel(cons
   __shared__ __attribute__((aligned(16))) double As[T * DLD];
   __shared__ __attribute__((aligned(16))) double Bs[T * DLD];
   __shared__ double red[WT][T];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const dgemm_lanes<WT> at;
+  const int tid = threadIdx.x, wn = at.wn, lr = at.lr;
   const int c = blockIdx.y, m0 = blockIdx.x * T;
   const double* Wc = W + (long)c * D * D;
   const double* Vc = V + (long)c * D;
@@ -103,7 +90,7 @@ __global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void gauss_loglik_kernel(cons
     dgemm_tile<WT, true>(Xt, Wt, N, Dt, Dt, mt, n0, As, Bs, acc);
 #pragma unroll
     for (int h = 0; h < G; ++h) {   // the wave's 32-column groups
-      const int na = n0 + wn * 16 * WT + h * 32 + lr, nb = na + 16;
+      const int na = n0 + at.col(2 * h), nb = na + 16;
       const double off0 = na < D ? Vc[na] : 0.0, off1 = nb < D ? Vc[nb] : 0.0;
 #pragma unroll
       for (int i = 0; i < WT; ++i)
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void gauss_loglik_kernel(cons
           s += y1 * y1;
 #pragma unroll
           for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
-          if (lr == 0) red[wn * G + h][wm * 16 * WT + i * 16 + lk + 4 * q] = s;
+          if (lr == 0) red[wn * G + h][at.row(i, q)] = s;
         }
     }
     __syncthreads();   // the next tile's k loop has barriers between this read of `red` and its next write

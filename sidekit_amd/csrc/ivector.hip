@@ -113,8 +113,7 @@ __global__ __launch_bounds__(256, 4) void tv_gram_kernel(const double* __restric
   __shared__ __attribute__((aligned(16))) double As[TL * DLD];
   __shared__ __attribute__((aligned(16))) double Bs[TL * DLD];
   __shared__ double cs[2 * TL];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const dgemm_lanes<WT> at;
   const int nt = (R + TL - 1) / TL;
   int t = blockIdx.y, tm = 0;
   while (tm < nt - 1 && t >= nt - tm) { t -= nt - tm; ++tm; }
@@ -127,11 +126,11 @@ __global__ __launch_bounds__(256, 4) void tv_gram_kernel(const double* __restric
   for (int i = 0; i < WT; ++i)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int m = m0 + wm * 16 * WT + i * 16 + lk + 4 * q;
+      const int m = m0 + at.row(i, q);
       if (m >= R) continue;
 #pragma unroll
       for (int j = 0; j < WT; ++j) {
-        const int n = n0 + wn * 16 * WT + j * 16 + lr;
+        const int n = n0 + at.col(j);
         if (n < R && n >= m) Gc[tv_rb(m, R) + n] = acc[i][j][q];
       }
     }

@@ -27,8 +27,7 @@ __global__ __launch_bounds__(256, 2) void jfa_shift_kernel(const double* stat1, 
   constexpr int WT = 4, TL = 32 * WT;
   __shared__ __attribute__((aligned(16))) double As[TL * DLD];
   __shared__ __attribute__((aligned(16))) double Bs[TL * DLD];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const dgemm_lanes<WT> at;
   const int m0 = blockIdx.x * TL, n0 = blockIdx.y * TL, CD = C * D;
   f64x4 acc[WT][WT];
   if (R > 0) {
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(256, 2) void jfa_shift_kernel(const double* stat1, 
   double mu[WT], sc[WT];
 #pragma unroll
   for (int j = 0; j < WT; ++j) {
-    const int n = n0 + wn * 16 * WT + j * 16 + lr;
+    const int n = n0 + at.col(j);
     const bool in = n < CD;
     comp[j] = in ? n / D : 0;
     mu[j] = in && mean ? mean[n] : 0.0;
@@ -53,13 +52,13 @@ __global__ __launch_bounds__(256, 2) void jfa_shift_kernel(const double* stat1, 
   for (int i = 0; i < WT; ++i)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int m = m0 + wm * 16 * WT + i * 16 + lk + 4 * q;
+      const int m = m0 + at.row(i, q);
       if (m >= N) continue;
       const double* cnt = stat0 + (long)m * C;
       const long base = (long)m * CD;
 #pragma unroll
       for (int j = 0; j < WT; ++j) {
-        const int n = n0 + wn * 16 * WT + j * 16 + lr;
+        const int n = n0 + at.col(j);
         if (n >= CD) continue;
         const double v = stat1[base + n] - cnt[comp[j]] * (mu[j] + acc[i][j][q]);
         out[base + n] = v * sc[j];

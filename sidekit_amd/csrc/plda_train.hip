@@ -64,38 +64,34 @@ __global__ __launch_bounds__(256) void column_sum_kernel(const double* __restric
 // ---- TN product ------------------------------------------------------------------------------------------------------------------
 // grid: x = column tile, y = row tile, z = row slab [z * slab, z * slab + slab) of K; out = G (one slab) or the slab's partial tile
 // part[z][M][N].  Bounds: the tile zero-fills beyond M, N and the slab's end; stores are guarded by m < M, n < N.
+// The operands of either TN kernel.  With cls: the centre of row k is gathered through its class number (scatter_within_kernel: B = A,
+// N = M, ca = the [C][M] class means, w = the [C] class weights; cb is unused).
+template <typename T>
+struct TnOperands {
+  const T *A, *B;
+  const double *w, *ca, *cb;
+  const int* cls;
+  int C;
+};
+
 template <int WT, typename T>
-__global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void dgemm_tn_kernel(const T* __restrict__ A, const T* __restrict__ B, long K, int M, int N,
-                                                                        int slab, const double* __restrict__ w, const double* __restrict__ ca,
-                                                                        const double* __restrict__ cb, double* __restrict__ out) {
+__global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void dgemm_tn_kernel(TnOperands<T> o, long K, int M, int N, int slab, double* __restrict__ out) {
   constexpr int TL = 32 * WT;
   __shared__ __attribute__((aligned(16))) double As[TL * DLD];
   __shared__ __attribute__((aligned(16))) double Bs[TL * DLD];
   __shared__ double cs[2 * TL];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const dgemm_lanes<WT> at;
   const int m0 = blockIdx.y * TL, n0 = blockIdx.x * TL;
   const long k_begin = (long)blockIdx.z * slab;
   const int kl = (int)(K - k_begin < (long)slab ? K - k_begin : (long)slab);
   f64x4 acc[WT][WT];
-  dgemm_tile<WT, true, true, T, T>(A + k_begin * M, B + k_begin * N, M, N, kl, m0, n0, As, Bs, acc, w ? w + k_begin : nullptr, ca, cb, cs);
-  double* dst = out + (long)blockIdx.z * M * N;
-#pragma unroll
-  for (int i = 0; i < WT; ++i)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int m = m0 + wm * 16 * WT + i * 16 + lk + 4 * q;
-      if (m >= M) continue;
-#pragma unroll
-      for (int j = 0; j < WT; ++j) {
-        const int n = n0 + wn * 16 * WT + j * 16 + lr;
-        if (n < N) dst[(long)m * N + n] = acc[i][j][q];
-      }
-    }
+  dgemm_tile<WT, true, true, T, T>(o.A + k_begin * M, o.B + k_begin * N, M, N, kl, m0, n0, As, Bs, acc, o.w ? o.w + k_begin : nullptr, o.ca, o.cb, cs);
+  dgemm_store_tile(acc, at, out + (long)blockIdx.z * M * N, N, m0, n0, M, N);
 }
 
 // The same grid and slabs with the centre of row k gathered through its class number (dgemm_tile's ROWC form): A = B = X, M = N = D.
-// Bounds: as above; a class number outside [0, C) gives its row weight 0 and reads no centre.
+// Bounds: as above; a class number outside [0, C) gives its row weight 0 and reads no centre.  Its own kernel with dgemm_lanes' map written
+// out, as it was before dgemm_tn_kernel took TnOperands: as dgemm_tn_kernel<WT, T, ROWC> sc_scatter_within measured slower.
 template <int WT, typename T>
 __global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void scatter_within_kernel(const T* __restrict__ X, long K, int D, int slab,
                                                                               const int* __restrict__ cls, const double* __restrict__ Mc,
@@ -142,8 +138,7 @@ __global__ __launch_bounds__(256, 4) void dgemm_nn_kernel(const double* __restri
   constexpr int WT = 2, TL = 64;
   __shared__ __attribute__((aligned(16))) double As[TL * DLD];
   __shared__ __attribute__((aligned(16))) double Bs[TL * DLD];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const dgemm_lanes<WT> at;
   const int m0 = blockIdx.y * TL, n0 = blockIdx.x * TL;
   f64x4 acc[WT][WT];
   dgemm_tile<WT, true>(A, B, M, N, K, m0, n0, As, Bs, acc);
@@ -151,12 +146,12 @@ __global__ __launch_bounds__(256, 4) void dgemm_nn_kernel(const double* __restri
   for (int i = 0; i < WT; ++i)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int m = m0 + wm * 32 + i * 16 + lk + 4 * q;
+      const int m = m0 + at.row(i, q);
       if (m >= M) continue;
       const double rv = rowv ? rowv[m] : 0.0;
 #pragma unroll
       for (int j = 0; j < WT; ++j) {
-        const int n = n0 + wn * 32 + j * 16 + lr;
+        const int n = n0 + at.col(j);
         if (n >= N) continue;
         const double t = rowv ? rv * colv[n] : 0.0, v = alpha * acc[i][j][q];
         C[(long)m * N + n] = epilogue == SC_EPI_POSTERIOR ? v / (1.0 + t) : v - t;
@@ -205,21 +200,25 @@ static int launch_tn_slabs(long K, int M, int N, double* G, hipStream_t st, Laun
   return SK_OK;
 }
 
-template <typename T>
-static int launch_gemm_tn(const T* A, const T* B, long K, int M, int N, const double* w, const double* ca, const double* cb, double* G,
-                          hipStream_t st) {
+template <bool ROWC, typename T>
+static int launch_gemm_tn(const TnOperands<T>& o, long K, int M, int N, double* G, hipStream_t st) {
   return launch_tn_slabs(K, M, N, G, st, [&](bool big, dim3 grid, int slab, double* out) {
-    if (big) hipLaunchKernelGGL((dgemm_tn_kernel<4, T>), grid, dim3(256), 0, st, A, B, K, M, N, slab, w, ca, cb, out);
-    else hipLaunchKernelGGL((dgemm_tn_kernel<2, T>), grid, dim3(256), 0, st, A, B, K, M, N, slab, w, ca, cb, out);
+    if constexpr (ROWC) {
+      if (big) hipLaunchKernelGGL((scatter_within_kernel<4, T>), grid, dim3(256), 0, st, o.A, K, M, slab, o.cls, o.ca, o.w, o.C, out);
+      else hipLaunchKernelGGL((scatter_within_kernel<2, T>), grid, dim3(256), 0, st, o.A, K, M, slab, o.cls, o.ca, o.w, o.C, out);
+    } else {
+      if (big) hipLaunchKernelGGL((dgemm_tn_kernel<4, T>), grid, dim3(256), 0, st, o, K, M, N, slab, out);
+      else hipLaunchKernelGGL((dgemm_tn_kernel<2, T>), grid, dim3(256), 0, st, o, K, M, N, slab, out);
+    }
   });
 }
 
-template <typename T>
-static int launch_scatter_within(const T* X, long K, int D, const int* cls, const double* Mc, const double* w, int C, double* G, hipStream_t st) {
-  return launch_tn_slabs(K, D, D, G, st, [&](bool big, dim3 grid, int slab, double* out) {
-    if (big) hipLaunchKernelGGL((scatter_within_kernel<4, T>), grid, dim3(256), 0, st, X, K, D, slab, cls, Mc, w, C, out);
-    else hipLaunchKernelGGL((scatter_within_kernel<2, T>), grid, dim3(256), 0, st, X, K, D, slab, cls, Mc, w, C, out);
-  });
+// the operands of either dtype, and the launch
+template <bool ROWC>
+static int launch_gemm_tn(const void* A, const void* B, int32_t dtype, long K, int M, int N, const double* w, const double* ca, const double* cb,
+                          const int* cls, int C, double* G, hipStream_t st) {
+  if (dtype == XT_F32) return launch_gemm_tn<ROWC>(TnOperands<float>{(const float*)A, (const float*)B, w, ca, cb, cls, C}, K, M, N, G, st);
+  return launch_gemm_tn<ROWC>(TnOperands<double>{(const double*)A, (const double*)B, w, ca, cb, cls, C}, K, M, N, G, st);
 }
 
 }  // namespace sk
@@ -256,8 +255,7 @@ int sc_gemm_tn(const void* d_A, const void* d_B, int32_t dtype, int64_t K, int32
   SK_CHECK(d_A && d_B && d_G, SK_EARG, "sc_gemm_tn: null argument");
   SK_CHECK(dtype == XT_F32 || dtype == XT_F64, SK_EARG, "sc_gemm_tn: operands must be XT_F32 or XT_F64 (got %d)", dtype);
   SK_CHECK(K > 0 && M > 0 && Nn > 0 && (int64_t)M * Nn <= (1LL << 28), SK_EARG, "sc_gemm_tn: bad sizes (K=%lld, M=%d, Nn=%d)", (long long)K, M, Nn);
-  if (dtype == XT_F32) return launch_gemm_tn((const float*)d_A, (const float*)d_B, (long)K, M, Nn, d_w, d_ca, d_cb, d_G, (hipStream_t)stream);
-  return launch_gemm_tn((const double*)d_A, (const double*)d_B, (long)K, M, Nn, d_w, d_ca, d_cb, d_G, (hipStream_t)stream);
+  return launch_gemm_tn<false>(d_A, d_B, dtype, (long)K, M, Nn, d_w, d_ca, d_cb, nullptr, 0, d_G, (hipStream_t)stream);
 }
 
 int sc_scatter_within(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, const int32_t* d_cls, const double* d_Mc, const double* d_w,
@@ -266,8 +264,7 @@ int sc_scatter_within(const void* d_X, int32_t x_dtype, int64_t N, int32_t D, co
   SK_CHECK(x_dtype == XT_F32 || x_dtype == XT_F64, SK_EARG, "sc_scatter_within: X must be XT_F32 or XT_F64 (got %d)", x_dtype);
   SK_CHECK(N > 0 && N <= 0x7fffffffLL && D > 0 && D <= 16384 && C > 0, SK_EARG, "sc_scatter_within: bad sizes (N=%lld, D=%d, C=%d)",
            (long long)N, D, C);
-  if (x_dtype == XT_F32) return launch_scatter_within((const float*)d_X, (long)N, D, d_cls, d_Mc, d_w, C, d_G, (hipStream_t)stream);
-  return launch_scatter_within((const double*)d_X, (long)N, D, d_cls, d_Mc, d_w, C, d_G, (hipStream_t)stream);
+  return launch_gemm_tn<true>(d_X, d_X, x_dtype, (long)N, D, D, d_w, d_Mc, nullptr, d_cls, C, d_G, (hipStream_t)stream);
 }
 
 int sc_dgemm_nn(const double* d_A, const double* d_B, int32_t M, int32_t N, int32_t K, double alpha, const double* d_rowv,

@@ -146,8 +146,8 @@ __global__ __launch_bounds__(256, 2) void plda_cohort_moments_kernel(const doubl
   __shared__ __attribute__((aligned(16))) double Bs[PCT * DLD];
   __shared__ double term[2 * PCT];   // [0, PCT): the tile's cohort terms, [PCT, 2 PCT): the workgroup's X terms
   __shared__ double red[PCT][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;   // wm: cohort side, wn: X side
+  const dgemm_lanes<WT> at;   // wm: cohort side, wn: X side
+  const int tid = threadIdx.x, wm = at.wm, lk = at.lk;
   const int n0 = blockIdx.x * PCT;
   const int tiles_m = (M + PCT - 1) / PCT, t0 = blockIdx.y * tiles_per_slab, t1 = t0 + tiles_per_slab < tiles_m ? t0 + tiles_per_slab : tiles_m;
   if (tid >= PCT) {   // rows past the end are never written
@@ -171,14 +171,14 @@ __global__ __launch_bounds__(256, 2) void plda_cohort_moments_kernel(const doubl
     // (a dropped value enters the sums as an exact zero: the kept values' additions are unchanged by it)
 #pragma unroll
     for (int j = 0; j < WT; ++j) {
-      const int ln_ = wn * 16 * WT + j * 16 + lr;
+      const int ln_ = at.col(j);
       const long drop = self_off >= 0 ? (long)(n0 + ln_) + self_off : -1L;
       const double xt = term[PCT + ln_];
 #pragma unroll
       for (int i = 0; i < WT; ++i)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int lm = wm * 16 * WT + i * 16 + lk + 4 * q, m = c0 + lm;
+          const int lm = at.row(i, q), m = c0 + lm;
           double v = alpha * (acc[i][j][q] + xt + term[lm] + cst);   // dgemm_nt_kernel's expression: X is sc_plda_fast's row side
           v = (m < M && (long)m != drop) ? v : 0.0;
           s1[j] += v;
@@ -193,14 +193,14 @@ __global__ __launch_bounds__(256, 2) void plda_cohort_moments_kernel(const doubl
     s2[j] += __shfl_xor(s2[j], 16);
     s1[j] += __shfl_xor(s1[j], 32);
     s2[j] += __shfl_xor(s2[j], 32);
-    const int row = wn * 16 * WT + j * 16 + lr;
+    const int row = at.col(j);
     if (wm == 1 && lk == 0) { red[row][0] = s1[j]; red[row][1] = s2[j]; }
   }
   __syncthreads();
   if (wm == 0 && lk == 0) {
 #pragma unroll
     for (int j = 0; j < WT; ++j) {
-      const int row = wn * 16 * WT + j * 16 + lr, n = n0 + row;
+      const int row = at.col(j), n = n0 + row;
       if (n >= N) continue;
       double* o = part + ((long)blockIdx.y * N + n) * 2;
       o[0] = s1[j] + red[row][0];

@@ -30,6 +30,7 @@ __global__ __launch_bounds__(256, WT == 4 ? 2 : 4) void dgemm_nt_kernel(const do
   constexpr int T = 32 * WT;
   __shared__ __attribute__((aligned(16))) double As[T * DLD];
   __shared__ __attribute__((aligned(16))) double Bs[T * DLD];
+  // dgemm_lanes' map, written out: through the struct, WT = 4 takes one register more
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
   const int m0 = blockIdx.y * T, n0 = blockIdx.x * T;
@@ -79,39 +80,27 @@ __global__ __launch_bounds__(256) void plda_prep_kernel(const double* __restrict
   const double* X = is_t ? Tm : E;
   const int M = is_t ? Nt : Ne;
   const int m0 = (is_t ? (int)blockIdx.y - etiles : (int)blockIdx.y) * T, p = psi ? (int)blockIdx.x - ctiles : (int)blockIdx.x, n0 = p * T;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const dgemm_lanes<WT> at;
   f64x4 acc[WT][WT];
   dgemm_tile<WT, true>(X, psi ? Psi : Phi, M, D, D, m0, n0, As, Bs, acc);
   if (psi) {
-#pragma unroll
-    for (int i = 0; i < WT; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int m = m0 + wm * 32 + i * 16 + lk + 4 * q;
-        if (m >= M) continue;
-#pragma unroll
-        for (int j = 0; j < WT; ++j) {
-          const int n = n0 + wn * 32 + j * 16 + lr;
-          if (n < D) EPsi[(long)m * D + n] = acc[i][j][q];
-        }
-      }
+    dgemm_store_tile(acc, at, EPsi, D, m0, n0, M, D);
     return;
   }
 #pragma unroll
   for (int i = 0; i < WT; ++i)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int r = wm * 32 + i * 16 + lk + 4 * q, m = m0 + r;
+      const int r = at.row(i, q), m = m0 + r;
       double s = 0.0;
 #pragma unroll
       for (int j = 0; j < WT; ++j) {
-        const int n = n0 + wn * 32 + j * 16 + lr;
+        const int n = n0 + at.col(j);
         if (m < M && n < D) s = fma(acc[i][j][q], X[(long)m * D + n], s);
       }
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);   // the 16 lanes that share lk hold this row's 16 columns of each tile
-      if (lr == 0) red[wn][r] = s;
+      if (at.lr == 0) red[at.wn][r] = s;
     }
   __syncthreads();
   if (threadIdx.x < T && m0 + (int)threadIdx.x < M)
@@ -305,8 +294,8 @@ __global__ __launch_bounds__(PTHREADS) void plda_hist_kernel(const double* __res
     __shared__ double stat_lds[4 * PT];
     stat = stat_lds;
   }
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lk = lane >> 4;
+  const dgemm_lanes<WT> at;
+  const int tid = threadIdx.x;
   for (int i = tid; i < 2 * HB; i += PTHREADS) hist[i] = 0u;
   const long tiles_n = (Nt + PT - 1) / PT, ntiles = (long)((Ne + PT - 1) / PT) * tiles_n;
   auto flush = [&]() {   // LDS counts -> the global 64-bit counters
@@ -342,7 +331,7 @@ __global__ __launch_bounds__(PTHREADS) void plda_hist_kernel(const double* __res
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < WT; ++j) {
-      const int ln_ = wn * 16 * WT + j * 16 + lr, n = n0 + ln_;
+      const int ln_ = at.col(j), n = n0 + ln_;
       if (n >= Nt) continue;
       const int labn = lt[n];
       const double ct = term[PT + ln_];
@@ -352,7 +341,7 @@ __global__ __launch_bounds__(PTHREADS) void plda_hist_kernel(const double* __res
       for (int i = 0; i < WT; ++i)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int lm = wm * 16 * WT + i * 16 + lk + 4 * q, m = m0 + lm;
+          const int lm = at.row(i, q), m = m0 + lm;
           if (m >= Ne || (self_offset >= 0 && m + self_offset == n)) continue;
           double v = alpha * (acc[i][j][q] + term[lm] + ct + cst);
           if constexpr (NORM == HN_ENROL) v = (v - stat[lm]) / stat[2 * PT + lm];

@@ -344,6 +344,19 @@ def test_the_existing_entry_points_give_the_bits_they_gave(gpu, golden_dir):
     assert not changed, f"bits changed: {changed}"
 
 
+def test_the_f64_tile_users_give_the_bits_they_gave(gpu, golden_dir):
+    """Every other user of csrc/dgemm_tile.h (the scatters, the Gram, the whitening, the log-likelihoods, the JFA shift, the PLDA histograms
+    and cohort moments) on fixed inputs against the digests recorded with the library of the commit before the tile's loaders, lane map and
+    tile store were consolidated (tests/tools/plda_bits.py, tile_digests).  A digest that differs is a changed kernel, not a fixture to
+    record again."""
+    with open(os.path.join(golden_dir, "f64_tile_bits.json")) as f:
+        recorded = json.load(f)
+    now = plda_bits.tile_digests(gpu)
+    assert sorted(now) == sorted(recorded)
+    changed = [k for k in recorded if now[k] != recorded[k]]
+    assert not changed, f"bits changed: {changed}"
+
+
 # ---- 5. the driver -------------------------------------------------------------------------------------------------------------------
 
 def test_driver_applies_lda_and_sphnorm_on_the_device(gpu, capsys):

@@ -1,5 +1,5 @@
 """The float64 back end one entry point at a time: the TN, NN and gathered-centre forms of csrc/dgemm_tile.h behind sc_gemm_tn,
-sc_scatter_within, sc_class_scatter, sc_tv_gram, sc_dgemm_nn and sc_gauss_loglik, and sc_whiten_rows' hand copy of the tile, each against a
+sc_scatter_within, sc_class_scatter, sc_tv_gram, sc_dgemm_nn and sc_gauss_loglik, and sc_whiten_rows' tile on the same loaders, each against a
 numpy.longdouble evaluation of the SAME operands under a per-element bound (tests/tools/f64_forms.py, where operands, references, criteria
 and shapes are stated).  tests/test_f64_forms_reference_cpu.py shows on these operands that float64 numpy passes every criterion and that
 the wrong kernels listed there do not.

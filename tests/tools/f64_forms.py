@@ -1,6 +1,6 @@
 """numpy.longdouble references of the float64 back end one entry point at a time: the TN, NN and gathered-centre forms of csrc/dgemm_tile.h
-behind sc_gemm_tn, sc_scatter_within, sc_class_scatter, sc_tv_gram, sc_dgemm_nn and sc_gauss_loglik, and the hand copy of the tile in
-sc_whiten_rows.  Operands, references, criteria, the shapes, float64 numpy stand-ins of the kernels (with the wrong kernels the criteria must
+behind sc_gemm_tn, sc_scatter_within, sc_class_scatter, sc_tv_gram, sc_dgemm_nn and sc_gauss_loglik, and sc_whiten_rows' tile of its own
+on the same loaders.  Operands, references, criteria, the shapes, float64 numpy stand-ins of the kernels (with the wrong kernels the criteria must
 reject) -- CPU only, numpy only.  tests/test_gpu_f64_forms.py judges the kernels by this file; tests/test_f64_forms_reference_cpu.py shows
 on the same operands that a float64 numpy evaluation passes every criterion and that the wrong kernels do not.
 
