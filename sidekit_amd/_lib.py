@@ -147,6 +147,14 @@ IVECTOR_SIGNATURES = {
     "sc_tv_posterior": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/ivector_wide.h (sidekit_amd/factor_analyser_wide.py)
+IVECTOR_WIDE_SIGNATURES = {
+    "sc_tvw_gram": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
+    "sc_tvw_workspace": (ctypes.c_int, [_I32, _I32, _P]),
+    "sc_tvw_posterior": (ctypes.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _P, _I64, _P]),
+}
+SC_TVW_MAX_RANK = 1024   # include/sidekit_amd/ivector_wide.h
+
 # name -> (restype, argtypes); every symbol of include/sidekit_amd/jfa.h (sidekit_amd/jfa_scoring.py)
 JFA_SIGNATURES = {
     "sc_jfa_shift": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -201,7 +209,8 @@ def lib():
                               + list(IVECTOR_SIGNATURES.items()) + list(GMM_SCORING_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())
                               + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items()) + list(SVM_SIGNATURES.items())
                               + list(GMM_TOPC_SIGNATURES.items()) + list(GMM_TOPC_STATS_SIGNATURES.items())
-                              + list(GMM_TOPC_EM_SIGNATURES.items()) + list(GMM_FULL_SIGNATURES.items()) + list(PLP_SIGNATURES.items())):
+                              + list(GMM_TOPC_EM_SIGNATURES.items()) + list(GMM_FULL_SIGNATURES.items()) + list(PLP_SIGNATURES.items())
+                              + list(IVECTOR_WIDE_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -33,13 +33,11 @@
 
 #include "../../include/sidekit_amd/ivector.h"
 #include "dgemm_tile.h"
+#include "tv_common.h"
 
 namespace sk {
 
 constexpr int TV_THREADS = 256, TV_MAX_CHUNKS = 16;
-
-__host__ __device__ inline long tv_packed(int R) { return (long)R * (R + 1) / 2; }
-__device__ inline int tv_rb(int i, int R) { return (int)(__umul24(i, 2 * R - i - 1) >> 1); }   // i R - i (i + 1) / 2: (i, k), i <= k, is at tv_rb(i) + k
 
 // s + c = the sum so far as if added in twice the precision (the file is built with -ffp-contract=off: nothing here is fused or reordered)
 struct Dot2 {
@@ -254,6 +252,13 @@ __global__ __launch_bounds__(TV_THREADS) void tv_posterior_kernel(const double* 
   if (diag && tid < R) diag[session * R + tid] = T[tv_rb(tid, R) + tid];
 }
 
+// the launch of both Gram entries (sc_tv_gram here, sc_tvw_gram of ivector_wide.hip)
+int tv_gram_launch(const double* d_F, int C, int D, int R, int nt, double* d_G, hipStream_t stream) {
+  hipLaunchKernelGGL(tv_gram_kernel, dim3((unsigned)C, (unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, stream, d_F, D, R, d_G);
+  SK_HIP(hipGetLastError());
+  return SK_OK;
+}
+
 }  // namespace sk
 
 using namespace sk;
@@ -265,9 +270,7 @@ int sc_tv_gram(const double* d_F, int32_t C, int32_t D, int32_t R, double* d_G, 
   SK_CHECK(C >= 1 && D >= 1 && R >= 1 && R <= SC_TV_MAX_RANK, SK_EARG, "sc_tv_gram: bad sizes (C=%d, D=%d, R=%d with at most %d)", C, D, R,
            SC_TV_MAX_RANK);
   const int nt = cdiv(R, 64);
-  hipLaunchKernelGGL(tv_gram_kernel, dim3((unsigned)C, (unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, (hipStream_t)stream, d_F, D, R, d_G);
-  SK_HIP(hipGetLastError());
-  return SK_OK;
+  return tv_gram_launch(d_F, C, D, R, nt, d_G, (hipStream_t)stream);
 }
 
 int sc_tv_posterior(const double* d_Lp, const double* d_B, int32_t N, int32_t R, double* d_Eh, double* d_Ehh, double* d_diag, void* stream) {

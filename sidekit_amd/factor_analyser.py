@@ -21,8 +21,9 @@ from the whole ``C D x R`` loading matrix per session; here the four large produ
 ``G[c] = F_c' F_c`` (``sc_tv_gram``, once per iteration), the projections ``S_w . F`` and the accumulators (``sc_dgemm_nn``, ``sc_gemm_tn``)
 -- and the per-session step between them (``Lambda = I + sum``, its inverse, ``e_h``, ``E_hh``) is one kernel, ``sc_tv_posterior``
 (``include/sidekit_amd/ivector.h``), a workgroup per session with the packed matrix in LDS.  The M-step (``C`` solves of ``R x R`` systems, one
-Cholesky factor) stays on the host in the reference's operation order.  Ranks above ``TV_MAX_RANK`` (a blocked factorisation outside
-LDS), ``total_variability_raw``, full-covariance UBMs and ``weighted_likelihood_plda`` are not built.
+Cholesky factor) stays on the host in the reference's operation order.  Ranks above ``TV_MAX_RANK`` are ``factor_analyser_wide``'s (a
+blocked factorisation outside LDS, ``WideFactorAnalyser``); ``total_variability_raw``, full-covariance UBMs and
+``weighted_likelihood_plda`` are not built.
 There is no CPU fallback for training or extraction; importing the module, ``write`` and ``read`` work on any host.
 """
 import copy
@@ -210,7 +211,8 @@ def _unpack(p, rank):
 def _check_rank(tv_rank):
     if not 1 <= tv_rank <= TV_MAX_RANK:
         raise ValueError("tv_rank = {} is outside [1, {}]: sc_tv_posterior keeps one packed triangle of the rank in LDS "
-                         "(SC_TV_MAX_RANK = {})".format(tv_rank, TV_MAX_RANK, TV_MAX_RANK))
+                         "(SC_TV_MAX_RANK = {}); sidekit_amd.factor_analyser_wide (WideFactorAnalyser) takes ranks up to 1024"
+                         .format(tv_rank, TV_MAX_RANK, TV_MAX_RANK))
 
 
 def _check_ubm(ubm):
@@ -293,18 +295,34 @@ def tv_m_step(_A, _C, _R, nb_sessions, min_div=True):
     return F
 
 
-def _tv_e_step(torch, stat0, stat1, whitener, F_d, rows):
-    """The accumulators of one E-step over all sessions, added in batch order -> host ``(_A, _C, _R)``"""
+GEMM_TN_MAX_OUTPUT = 1 << 28  # sc_gemm_tn: M * Nn doubles at most in one call
+
+
+def _count_weighted_sums(stat0, e_hh):
+    """``stat0' . e_hh`` (C, P), the accumulator ``_A``.  One ``sc_gemm_tn`` while ``C P`` is within its bound, as ever; beyond it
+    (C = 2 048 at rank 600 is 3.7e8) one call per block of components, each on a copy of the block's columns of ``stat0``."""
+    C, P = stat0.shape[1], e_hh.shape[1]
+    if C * P <= GEMM_TN_MAX_OUTPUT:
+        return gemm_tn_device(stat0, e_hh)
+    step = max(1, GEMM_TN_MAX_OUTPUT // P)
+    return _torch().cat([gemm_tn_device(stat0[:, c:c + step], e_hh) for c in range(0, C, step)])
+
+
+def _tv_e_step(torch, stat0, stat1, whitener, F_d, rows, posterior=tv_posterior_device, gram=tv_gram_device, to_host=True):
+    """The accumulators of one E-step over all sessions, added in batch order -> host ``(_A, _C, _R)``; device tensors (``_R`` as
+    (1, P)) when not ``to_host``.  ``posterior`` / ``gram``: the two calls of another rank range (``factor_analyser_wide``)."""
     N, C = stat0.shape
-    G = tv_gram_device(F_d, C)
+    G = gram(F_d, C)
     ones = torch.ones((rows, 1), dtype=torch.float64, device=stat0.device)
     acc = None
     for a in range(0, N, rows):
         s0 = stat0[a:a + rows]
         sw = _whiten(s0, stat1[a:a + rows], whitener)
-        e_h, e_hh = tv_posterior_device(s0, sw, F_d, G)
-        part = (gemm_tn_device(s0, e_hh), gemm_tn_device(e_h, sw), gemm_tn_device(ones[:s0.shape[0]], e_hh))
+        e_h, e_hh = posterior(s0, sw, F_d, G)
+        part = (_count_weighted_sums(s0, e_hh), gemm_tn_device(e_h, sw), gemm_tn_device(ones[:s0.shape[0]], e_hh))
         acc = part if acc is None else tuple(t.add_(p) for t, p in zip(acc, part))
+    if not to_host:
+        return acc
     return acc[0].cpu().numpy(), acc[1].cpu().numpy(), acc[2].cpu().numpy()[0]
 
 
@@ -335,19 +353,21 @@ def total_variability_device(stat0, stat1, ubm, tv_rank, nb_iter=20, min_div=Tru
     return F
 
 
-def _extract(stat0, stat1, whitener, F, uncertainty, max_workspace_bytes):
-    """i-vectors (and the diagonal of ``E_hh``) of resident statistics; ``whitener=None``: ``stat1`` is whitened already"""
+def _extract(stat0, stat1, whitener, F, uncertainty, max_workspace_bytes, posterior=tv_posterior_device, gram=tv_gram_device,
+             batch_rows=_batch_rows):
+    """i-vectors (and the diagonal of ``E_hh``) of resident statistics; ``whitener=None``: ``stat1`` is whitened already.
+    ``posterior`` / ``gram`` / ``batch_rows``: those of another rank range (``factor_analyser_wide``)."""
     torch = _torch()
     N, C = stat0.shape
     R = F.shape[1]
     F_d = _f64(torch, F, stat0.device)
-    G = tv_gram_device(F_d, C)
+    G = gram(F_d, C)
     iv = torch.empty((N, R), dtype=torch.float64, device=stat0.device)
     iv_sigma = torch.empty_like(iv)
-    rows = _batch_rows(N, C, stat1.shape[1] // C, R, max_workspace_bytes)
+    rows = batch_rows(N, C, stat1.shape[1] // C, R, max_workspace_bytes)
     for a in range(0, N, rows):
         s0, s1 = stat0[a:a + rows], stat1[a:a + rows]
-        iv[a:a + rows], iv_sigma[a:a + rows] = tv_posterior_device(s0, s1 if whitener is None else _whiten(s0, s1, whitener), F_d, G, want="diag")
+        iv[a:a + rows], iv_sigma[a:a + rows] = posterior(s0, s1 if whitener is None else _whiten(s0, s1, whitener), F_d, G, want="diag")
     return (iv, iv_sigma) if uncertainty else iv
 
 
@@ -443,6 +463,12 @@ class FactorAnalyser:
 
     # ---- total variability (sidekit_amd/csrc/ivector.hip): no CPU fallback ---------------------------------------------------------------
 
+    # what depends on the rank range; factor_analyser_wide.WideFactorAnalyser replaces these four and inherits the methods
+    _check_rank = staticmethod(_check_rank)
+    _train_device = staticmethod(total_variability_device)
+    _extract_whitened = staticmethod(_extract)
+    _extract_device = staticmethod(extract_ivectors_device)
+
     def total_variability(self, stat_server_filename, ubm, tv_rank, nb_iter=20, min_div=True, tv_init=None, batch_size=300, save_init=False,
                           output_file_name=None, num_thread=1):
         """Train a total variability model (:539-686).  ``stat_server_filename``: the name of a ``StatServer`` file (read with
@@ -454,7 +480,7 @@ class FactorAnalyser:
         every iteration but the last and ``<output_file_name>.h5`` after the last; ``save_init`` writes ``<output_file_name>_init.h5``
         and needs ``output_file_name`` (the reference raises a ``TypeError`` without it)."""
         C, D = _check_ubm(ubm)
-        _check_rank(tv_rank)
+        self._check_rank(tv_rank)
         assert isinstance(nb_iter, int) and 0 < nb_iter, "nb_iter must be a positive integer"
         assert not save_init or output_file_name is not None, "save_init needs output_file_name"
         torch = _torch()
@@ -474,7 +500,7 @@ class FactorAnalyser:
             if output_file_name is not None:
                 self.write(output_file_name + ("_it-{}.h5".format(it) if it < nb_iter - 1 else ".h5"))
 
-        self.F = total_variability_device(stat0, stat1, ubm, tv_rank, nb_iter, min_div, self.F, after_iteration=save)
+        self.F = self._train_device(stat0, stat1, ubm, tv_rank, nb_iter, min_div, self.F, after_iteration=save)
 
     def total_variability_single(self, stat_server_filename, ubm, tv_rank, nb_iter=20, min_div=True, tv_init=None, batch_size=300,
                                  save_init=False, output_file_name=None):
@@ -487,13 +513,13 @@ class FactorAnalyser:
         reference the caller's ``stat_server`` is left whitened in place (``whiten_stat1``)."""
         assert isinstance(stat_server, StatServer) and stat_server.validate(), "First argument must be a proper StatServer"
         C, D = _check_ubm(ubm)
-        _check_rank(self.F.shape[1])
+        self._check_rank(self.F.shape[1])
         torch = _torch()
         stat_server.whiten_stat1(ubm.get_mean_super_vector(), 1. / ubm.get_invcov_super_vector())
         dev = torch.device("cuda", torch.cuda.current_device())
         stat0, stat1 = _statistics(torch, *(torch.as_tensor(numpy.ascontiguousarray(x, dtype=STAT_TYPE)).to(dev)
                                             for x in (stat_server.stat0, stat_server.stat1)), C, D)
-        iv, iv_sigma = _extract(stat0, stat1, None, self.F, True, 1 << 30)
+        iv, iv_sigma = self._extract_whitened(stat0, stat1, None, self.F, True, 1 << 30)
         out = _ivector_server(stat_server, iv.cpu().numpy())
         return (out, iv_sigma.cpu().numpy()) if uncertainty else out
 
@@ -503,11 +529,11 @@ class FactorAnalyser:
         budget).  One deviation on purpose: ``prefix`` applies to every dataset that is read; the reference forgets it on ``stat0`` /
         ``stat1`` (:808)."""
         C, D = _check_ubm(ubm)
-        _check_rank(self.F.shape[1])
+        self._check_rank(self.F.shape[1])
         torch = _torch()
         server = _read_statistics(stat_server_filename, prefix)
         dev = torch.device("cuda", torch.cuda.current_device())
         stat0, stat1 = (torch.as_tensor(numpy.ascontiguousarray(x, dtype=STAT_TYPE)).to(dev) for x in (server.stat0, server.stat1))
-        iv, iv_sigma = extract_ivectors_device(stat0, stat1, ubm, self.F, uncertainty=True)
+        iv, iv_sigma = self._extract_device(stat0, stat1, ubm, self.F, uncertainty=True)
         out = _ivector_server(server, iv.cpu().numpy())
         return (out, iv_sigma.cpu().numpy()) if uncertainty else out
