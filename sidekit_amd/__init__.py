@@ -3,7 +3,7 @@
 Sub-modules mirror the reference package layout for the hot path only:
 ``sidekit_amd.nnet.xvector.Xtractor``, ``sidekit_amd.iv_scoring``, ``sidekit_amd.factor_analyser``, ``sidekit_amd.statserver``,
 ``sidekit_amd.bosaris``, ``sidekit_amd.score_normalization``, ``sidekit_amd.lid_utils``, ``sidekit_amd.mixture``, ``sidekit_amd.mixture_full``, ``sidekit_amd.gmm_scoring``, ``sidekit_amd.jfa_scoring``, ``sidekit_amd.sidekit_io``, ``sidekit_amd.frontend.vad``,
-``sidekit_amd.features_server``, ``sidekit_amd.frontend.normfeat``, ``sidekit_amd.frontend.features``, ``sidekit_amd.features_extractor``, ``sidekit_amd.plp``,
+``sidekit_amd.features_server``, ``sidekit_amd.frontend.normfeat``, ``sidekit_amd.frontend.features``, ``sidekit_amd.features_extractor``, ``sidekit_amd.plp``, ``sidekit_amd.features_context``,
 ``sidekit_amd.svm_training``, ``sidekit_amd.svm_scoring``, ``sidekit_amd.sv_utils``.
 ``install_as_sidekit()`` registers them under the ``sidekit`` names so that reference-style drivers
 (``extract_xvectors.py``, scoring scripts) import them unchanged.
@@ -43,13 +43,14 @@ _LAZY = {
     "FeaturesServer": "features_server",
     "FeaturesExtractor": "features_extractor",
     "PlpExtractor": "plp", "plp_device": "plp",
+    "ContextFeaturesServer": "features_context",
     "write_matrix_hdf5": "sidekit_io", "read_plda_hdf5": "sidekit_io", "write_plda_hdf5": "sidekit_io",
 }
 
 # every module of the mirror, by its reference name
 SUBMODULES = ("bosaris", "bosaris.idmap", "bosaris.ndx", "bosaris.key", "bosaris.scores", "bosaris.detplot", "statserver", "iv_scoring", "factor_analyser",
               "score_normalization", "lid_utils", "mixture", "mixture_full", "gmm_scoring", "jfa_scoring", "sidekit_io", "nnet", "nnet.xvector", "nnet.preprocessor", "frontend", "frontend.vad",
-              "features_server", "frontend.normfeat", "frontend.features", "features_extractor", "plp", "sv_utils", "svm_training", "svm_scoring")
+              "features_server", "frontend.normfeat", "frontend.features", "features_extractor", "plp", "features_context", "sv_utils", "svm_training", "svm_scoring")
 
 
 def __getattr__(name):

@@ -177,6 +177,14 @@ FEATURES_SIGNATURES = {
 }
 SC_FEAT_CENTER, SC_FEAT_CENTER_REDUCE, SC_FEAT_SLIDING_CENTER, SC_FEAT_SLIDING_CENTER_REDUCE, SC_FEAT_WARP = 0, 1, 2, 3, 4
 
+# name -> (restype, argtypes); every symbol of include/sidekit_amd/context.h (sidekit_amd/features_context.py)
+CONTEXT_SIGNATURES = {
+    "sc_ctx_gather": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _I64, _P, _P, _I32, _I32, _I32, _P, _I64, _P]),
+    "sc_ctx_basis": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _I64, _P, _I32, _I32, _I32, _P, _I64, _P]),
+    "sc_ctx_project": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _I64, _P, _I32, _I32, _I32, _P, _I64, _P]),
+}
+SC_CTX_MAX_BLOCKS, SC_CTX_MAX_SPAN, SC_CTX_MAX_W, SC_CTX_PROJ_MAX_D, SC_CTX_PROJ_MAX_Q = 256, 256, 64, 128, 512   # include/sidekit_amd/context.h
+
 # name -> (restype, argtypes); every symbol of include/sidekit_amd/cepstrum.h (sidekit_amd/features_extractor.py)
 CEPSTRUM_SIGNATURES = {
     "sc_mfcc": (ctypes.c_int, [_P, _I32, _I64, _F64, _P, _P, _I32, _I64, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _I32, _P, _I32, _P, _I64, _P, _I64, _P]),
@@ -210,7 +218,7 @@ def lib():
                               + list(CEPSTRUM_SIGNATURES.items()) + list(JFA_SIGNATURES.items()) + list(SVM_SIGNATURES.items())
                               + list(GMM_TOPC_SIGNATURES.items()) + list(GMM_TOPC_STATS_SIGNATURES.items())
                               + list(GMM_TOPC_EM_SIGNATURES.items()) + list(GMM_FULL_SIGNATURES.items()) + list(PLP_SIGNATURES.items())
-                              + list(IVECTOR_WIDE_SIGNATURES.items())):
+                              + list(IVECTOR_WIDE_SIGNATURES.items()) + list(CONTEXT_SIGNATURES.items())):
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -21,9 +21,12 @@ Where this differs from the reference, on purpose:
   * the values are float32 device results, whatever the dtype they are returned in;
   * ``load`` always reads one source through ``get_features``; the reference does so only with a ``dataset_list`` and takes the tandem
     route (``sources``) without one, which is not built;
-  * the HDF5 feature-file route, ``sources`` (tandem features), ``dct_pca``, ``sdc``, ``context``, TRAPs,
-    ``get_features_per_speaker`` and, for ``stack_features_device`` only, ``global_cmvn`` with the shows' own mean / std vectors
-    (``stack_features`` applies them) are not built and raise ``NotImplementedError``.
+  * the HDF5 feature-file route, ``sources`` (tandem features), ``get_features_per_speaker`` and, for ``stack_features_device`` only,
+    ``global_cmvn`` with the shows' own mean / std vectors (``stack_features`` applies them) are not built and raise
+    ``NotImplementedError``;
+  * ``dct_pca``, ``sdc``, ``context`` and TRAPs are built beside this class, not in it: ``FeaturesServer`` raises ``NotImplementedError``
+    for them and names ``sidekit_amd.features_context.ContextFeaturesServer``, the same server with the temporal-context slot filled
+    (``sc_ctx_gather``, ``sc_ctx_basis``, ``sc_ctx_project``).
 """
 import logging
 import re
@@ -336,6 +339,8 @@ class FeaturesServer(object):
     def __repr__(self):
         return _REPR.format(**vars(self))
 
+    _BUILDS_CONTEXT = False     # features_context.ContextFeaturesServer: dct_pca, sdc, context and TRAPs
+
     def _unbuilt(self):
         """The options of the reference this server does not build"""
         if self.features_extractor is None:
@@ -345,8 +350,13 @@ class FeaturesServer(object):
             raise NotImplementedError("sources (tandem features from several servers) are not built")
         for name, on in (("dct_pca", self.dct_pca), ("sdc", self.sdc), ("context", tuple(self.context) != (0, 0)),
                          ("traps_dct_nb (TRAPs)", self.traps_dct_nb)):
-            if on:
-                raise NotImplementedError(f"{name} is not built: sidekit_amd.features_server does RASTA, deltas, the mask and the normalisations")
+            if on and not self._BUILDS_CONTEXT:
+                raise NotImplementedError(f"{name} is not built: sidekit_amd.features_server does RASTA, deltas, the mask and the normalisations "
+                                          f"(sidekit_amd.features_context.ContextFeaturesServer builds it)")
+
+    def _process(self, frames, seg_off, labels, **options):
+        """``post_process_device``; what a subclass that fills the temporal-context slot replaces"""
+        return post_process_device(frames, seg_off, labels, **options)
 
     def _options(self, global_mean=None, global_std=None):
         return dict(rasta=bool(self.rasta), delta=bool(self.delta), double_delta=bool(self.double_delta), delta_filter=self.delta_filter,
@@ -362,10 +372,10 @@ class FeaturesServer(object):
         """RASTA, deltas, the mask, the normalisation and the selection of the speech frames of one utterance (:201-245) ->
         ``(feat, label)``.  ``label`` is updated in place by RASTA as in the reference; the result is float64 once RASTA ran, of the
         input's dtype otherwise."""
-        if self.dct_pca and not (self.delta or self.double_delta):
-            raise NotImplementedError("dct_pca is not built")
-        if self.sdc and not (self.delta or self.double_delta or self.dct_pca):
-            raise NotImplementedError("sdc is not built")
+        if self.dct_pca and not (self.delta or self.double_delta or self._BUILDS_CONTEXT):
+            raise NotImplementedError("dct_pca is not built (sidekit_amd.features_context.ContextFeaturesServer builds it)")
+        if self.sdc and not (self.delta or self.double_delta or self.dct_pca or self._BUILDS_CONTEXT):
+            raise NotImplementedError("sdc is not built (sidekit_amd.features_context.ContextFeaturesServer builds it)")
         torch = _torch()
         feat = numpy.asarray(feat)
         label = numpy.ones(feat.shape[0], dtype=bool) if label is None else label
@@ -374,8 +384,8 @@ class FeaturesServer(object):
         if label.shape[0] == 2 and numpy.all(label):     # the reference's label_fusion reads two frames as two channels that overlap
             label[...] = False
         dtype = numpy.float64 if self.rasta or not numpy.issubdtype(feat.dtype, numpy.floating) else feat.dtype
-        out, lab, _ = post_process_device(numpy.asarray(feat, dtype=numpy.float32), None, torch.as_tensor(numpy.array(label, dtype=bool)),
-                                          keep_all_features=True, **self._options(global_mean, global_std))
+        out, lab, _ = self._process(numpy.asarray(feat, dtype=numpy.float32), None, torch.as_tensor(numpy.array(label, dtype=bool)),
+                                    keep_all_features=True, **self._options(global_mean, global_std))
         label[...] = lab.cpu().numpy()
         feat = out.cpu().numpy().astype(dtype)
         if not self.keep_all_features:
@@ -505,6 +515,6 @@ class FeaturesServer(object):
         off = numpy.concatenate(([0], numpy.cumsum([f.shape[0] for f in feats]))).astype(numpy.int64)
         if self.global_cmvn and any(m is not None for m in means):
             raise NotImplementedError("global_cmvn with per-show vectors is not built for the stacked batch: use stack_features")
-        out, _, soff = post_process_device(numpy.vstack(feats), off, torch.as_tensor(numpy.concatenate(labels)),
-                                           keep_all_features=self.keep_all_features, **self._options())
+        out, _, soff = self._process(numpy.vstack(feats), off, torch.as_tensor(numpy.concatenate(labels)),
+                                     keep_all_features=self.keep_all_features, **self._options())
         return out, soff.cpu().numpy()

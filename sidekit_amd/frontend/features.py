@@ -2,7 +2,8 @@
 end -- ``mfcc`` and ``power_spectrum`` (:363-477) computed on the GPU (``sc_mfcc``, csrc/cepstrum.hip) from the host-made tables of the
 reference: ``trfbank`` (:226-305), the symmetric Hann window and the orthonormal DCT-II basis.  ``plp`` (:888-966) is computed on the GPU
 too (``sidekit_amd.plp``), from the host-made ``fft2barkmx`` bank (:480-522); ``lpc2spec``, whose output the reference discards, is not
-built.  There is no CPU fallback; importing the module needs neither a GPU nor torch."""
+built.  ``pca_dct`` (:169-194) and ``shifted_delta_cepstral`` (:197-223) run on the GPU through ``sidekit_amd.features_context``.
+There is no CPU fallback; importing the module needs neither a GPU nor torch."""
 import numpy
 
 from .. import PARAM_TYPE
@@ -207,3 +208,22 @@ def compute_delta(features, win=3, method='filter', filt=numpy.array([.25, .5, .
     if filt.shape[0] != 2 * win + 1:
         raise ValueError('the delta filter has {} taps, the window 2 * {} + 1'.format(filt.shape[0], win))
     return delta_device(numpy.asarray(features, dtype=numpy.float32), None, filt).cpu().numpy().astype(PARAM_TYPE)
+
+
+def pca_dct(cep, left_ctx=12, right_ctx=12, p=None):
+    """DCT-PCA (McLaren and Lei, 2015) of ``cep`` (frames x coefficients) -> float64 holding the float32 device values: the DCT over
+    time of each coefficient's window of ``left_ctx + 1 + right_ctx`` frames (the stream's first and last frame repeated past its ends),
+    ``(frames, D W)``, projected by ``p`` (``(D W, Q)``) when given -- as one product, on the f64 matrix cores
+    (``sidekit_amd.features_context.pca_dct_device``)."""
+    from ..features_context import pca_dct_device
+    return pca_dct_device(numpy.asarray(cep, dtype=numpy.float32), None, left_ctx, right_ctx, p).cpu().numpy().astype(numpy.float64)
+
+
+def shifted_delta_cepstral(cep, d=1, p=3, k=7):
+    """``cep`` with its shifted delta cepstra appended -> float64 ``(frames, D (k + 1))`` holding the float32 device values: block ``b``
+    is frame ``t + b p - d`` less frame ``t + b p + d`` (what the reference computes: its difference filter is flipped by
+    ``numpy.convolve``), the stream's first and last frame repeated past its ends.  ``ValueError`` while ``(k - 1) p > 3 k``: the
+    reference pads ``3 k + d`` frames whatever ``p`` is and past that bound reads zeros, then wraps its index
+    (``sidekit_amd.features_context.sdc_device``)."""
+    from ..features_context import sdc_device
+    return sdc_device(numpy.asarray(cep, dtype=numpy.float32), None, d, p, k).cpu().numpy().astype(numpy.float64)
